@@ -21,9 +21,19 @@ Workloads (``--workload``):
 
 One JSON line is printed by rank 0 with the metric of BASELINE.json plus
   roofline     : dominant kernel, algorithmic bytes / measured kernel time (HIP events on the library's stream)
-  cpu_baseline : the numpy oracle timed on a bounded sample of the same workload on this host (N = 1 only)
-and, at N = 1 (skipped with --no-extras): the exclusive time of the reference-pixel pre-pass, the production-representative
-variants (f64 ipc4d, 16 groups, P_ORDER 10) and the 18-slot batch of config 4.
+A plain run does nothing else: set-up, warm-up, the K timed steps, --dump-outputs if given, the line.  With --full, at N = 1,
+the line also carries
+  cpu_baseline : the numpy oracle timed on a bounded sample of the same workload on this host (skipped with --no-cpu-baseline)
+and (skipped with --no-extras) the exclusive time of the reference-pixel pre-pass, the host-array path, the
+production-representative variants (f64 ipc4d, 16 groups, P_ORDER 10) and the 18-slot batch of config 4, each timed by runs of
+its own after the headline steps.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, the arrays a caller of
+the calibration call receives, as DIR/<name>.npy (slope, err_read, err_poisson f32; pixeldq f64 from its uint32 flag words; groupdq
+f32 from uint8); for --workload realizations the (8, ny, nx) statistics planes as DIR/planes.npy.  Planes of up to
+DUMP_MAX_PIXELS pixels are written whole; larger ones as the same fixed sample of pixels
+(``np.sort(np.random.default_rng(DUMP_SEED).choice(ny * nx, DUMP_MAX_PIXELS, replace=False))``, row-major flat indices) taken
+from every plane.  The inputs are seeded, so the same arguments give the same inputs run after run.
 """
 
 import argparse
@@ -51,6 +61,9 @@ PROFILE_EVERY = max(1, int(os.environ.get("BENCH_PROFILE_EVERY", "15")))
 # lies above the HBM floor (16 groups) the HBM fraction alone misstates the bound: the variants carry both.
 VALU_FLOOR_MS = {("f32", 8): 0.407, ("f64", 8): 0.520, ("f32", 16): 0.787, ("f64", 16): 1.024}
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s achievable)
+# --dump-outputs: 2^19 pixels of a 4096 x 4096 frame are 26 MB of outputs at 8 groups and 42 MB at 16 (cap: 64 MB)
+DUMP_MAX_PIXELS = 1 << 19
+DUMP_SEED = 20250101
 
 
 def alg_bytes(G, ny, nx, nb, nplanes, gain_size=4, ipc_size=4, data_size=2):
@@ -86,6 +99,21 @@ def kernel_source_hash():
         with open(os.path.join(REPO, "romanimpreprocess_amd", "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(dirname, planes):
+    """``planes``: name -> array or tensor whose last two axes are (ny, nx).  Writes dirname/<name>.npy in f32 / f64 (integer
+    flag words as their unsigned values), whole or as the fixed sample of DUMP_MAX_PIXELS pixels (see the module docstring)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in planes.items():
+        a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        if a.dtype.kind in "iu":
+            a = a.view(f"u{a.dtype.itemsize}").astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)
+        ny, nx = a.shape[-2:]
+        if ny * nx > DUMP_MAX_PIXELS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(ny * nx, DUMP_MAX_PIXELS, replace=False))
+            a = a.reshape(a.shape[:-2] + (ny * nx,))[..., idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 # --------------------------------------------------------------------------------------------- CPU baseline
@@ -385,6 +413,8 @@ def run_realizations(args, cb, torch, dist, fence, rank, world, local_rank, cdev
         ok = good > n // 2
         if not (ok.mean() > 0.5 and np.isfinite(planes[6][4:-4, 4:-4][ok]).all()):
             raise SystemExit("bench sanity check failed: statistics planes of the realisations")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"planes": planes})
         print(json.dumps({
             "metric": f"noise realisations/s ({N}x{N}x{len(rp)}grp: generate + calibrate + stack + exchange + reduce)",
             "value": n / elapsed, "unit": "realisations/s", "n_gpus": world, "steps": n, "warmup": max(world, 2),
@@ -485,8 +515,14 @@ def main():
     ap.add_argument("--tiled", action="store_true", help="the round-1 input: a 128-row strip repeated down the frame (numpy)")
     ap.add_argument("--set", action="append", default=[], metavar="OPTION=VALUE",
                     help="rip_set_option before the run (A/B timing: overlap=0, prepass_form=0, ...)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip pre-pass exclusive timing, variants and the 18-slot batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: CPU baseline, pre-pass exclusive timing, host-array path, variants and the 18-slot batch "
+                         "(N = 1; runs of their own)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without pre-pass exclusive timing, host-array path, variants and the 18-slot batch")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (f32 / f64; planes above DUMP_MAX_PIXELS sampled)")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="collective backend of the N > 1 run (nccl = RCCL over xGMI; gloo: rehearsals on a box with fewer GPUs than ranks)")
     ap.add_argument("--share-gpu", action="store_true",
@@ -495,6 +531,8 @@ def main():
                     help="rehearsal of the N-rank plumbing without a GPU: item scatter, barriers, MAX all-reduce and the JSON line run "
                          "as they are, a step is a 1 ms sleep; the line carries dry_run: true and is not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and not args.share_gpu and not args.dry_run:
         # one GPU per rank: checked before any rendezvous (counting devices does not initialise the GPU on this image), by the
@@ -639,6 +677,9 @@ def main():
     elapsed, ms, ncalls = run_steps(cb, calls, args.warmup, args.steps, fence, ramp_s=args.clock_ramp_s)
     elapsed, per_rank = gather_elapsed(torch, dist, elapsed, world, cdev)
     frac_good = sane(res)
+    if rank == 0 and args.dump_outputs:
+        o = res.outs   # batch72 too: every item writes into the same result planes
+        dump_outputs(args.dump_outputs, {"slope": o.slope, "err_read": o.er, "err_poisson": o.ep, "pixeldq": o.pdq, "groupdq": o.gdq})
 
     if rank == 0:
         total, per_kernel, avg_ms, dom, ach = kernel_report(G, args.p_order, args.ipc_dtype, ms, ncalls)
@@ -694,7 +735,7 @@ def main():
                                                            "kernel holds the CUs: not a duration of exclusive use; see refpix_prepass_exclusive")
         out.update(extras)
 
-        if world == 1 and not args.no_extras and args.workload == "single":
+        if args.full and world == 1 and not args.no_extras and args.workload == "single":
             # ---- pre-pass alone (overlap off: every kernel of a call runs on one stream, so event gaps are exclusive times)
             cb.ctx.set_option("overlap", 0)
             el0, ms0, nc0 = run_steps(cb, calls, 2, 30, fence, ramp_s=0.3)
@@ -770,7 +811,7 @@ def main():
                 cb.ctx.drop_caldir(s_)
             del sets, calls_b, keep
 
-        if world == 1 and not args.no_cpu_baseline and cal is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and cal is not None:
             out["cpu_baseline"] = cpu_baseline(cal, ramp)
             if N == 4096:
                 out["cpu_baseline"]["replicas"] = cpu_replicas(248, G, args.p_order, args.ipc_dtype == "f64")
