@@ -8,6 +8,13 @@
 // its own: with two extra streams the copies did not overlap at all.
 #include "rip_common.h"
 
+// api.hip: the staging of a host ramp that rip_calibrate's host branch uses as well
+size_t rip_host_ramp_bytes(const rip_ramp_desc &in, int ny, int nx);
+int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev);
+size_t rip_result_bytes(int G, size_t npix, bool groupdq);
+rip_outputs rip_result_planes(char *w, const rip_outputs &host, size_t npix);
+int rip_download_results(rip_ctx *ctx, const rip_outputs &dev, const rip_outputs &host, int G, size_t npix, hipStream_t st);
+
 namespace {
 
 struct BatchSet {
@@ -15,8 +22,6 @@ struct BatchSet {
     hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_out = nullptr;
     bool used = false;
 };
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 }   // namespace
 
@@ -41,11 +46,7 @@ extern "C" int rip_calibrate_batch(rip_ctx *ctx, int slot, int plan_id, unsigned
         if (out[i].cube) return rip_fail(ctx, RIP_EINVAL, "calibrate_batch: the corrected cube is not returned by this entry");
     }
     if (G < 1 || G > RIP_MAX_GROUPS) return rip_fail(ctx, RIP_EINVAL, "calibrate_batch: %d groups unsupported", G);
-    const size_t esz = in[0].data_dtype == RIP_U16 ? 2 : 4;
-    const int nch = nx / RIP_CW;
-    const size_t b_data = al256((size_t)G * npix * esz), b_a33 = al256((size_t)G * ny * RIP_CW * 2), b_gdq = al256((size_t)G * npix),
-                 b_pdq = al256(npix * 4), b_area = al256(npix * 8), b_lines = al256((size_t)G * nch * 16), b_pl = al256(npix * 4);
-    const size_t in_bytes = b_data + b_a33 + b_gdq + b_pdq + b_area + b_lines, out_bytes = 4 * b_pl + b_gdq;
+    const size_t in_bytes = rip_host_ramp_bytes(in[0], ny, nx), out_bytes = rip_result_bytes(G, npix, true);
 
     // Streams map onto a few hardware queues (four by default), so no stream is made here: the uploads ride on the context's
     // second stream, in front of the reference-pixel pre-pass of the same ramp; the downloads have the context's third one.
@@ -96,25 +97,8 @@ extern "C" int rip_calibrate_batch(rip_ctx *ctx, int slot, int plan_id, unsigned
         const rip_outputs &ro = out[i];
         // upload: the input buffers of this set are free once the chain of ramp i-2 has run
         if (b.used) BATCH_HIP(hipStreamWaitEvent(s_in, b.ev_done, 0));
-        rip_ramp_desc rd = ri;
-        rd.location = RIP_DEVICE;
-        size_t o = 0;
-        auto put = [&](const void *src, size_t bytes, size_t slot_bytes) -> void * {
-            void *dst = b.in + o;
-            o += slot_bytes;
-            if (!src) return nullptr;
-            if (hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s_in) != hipSuccess) rc = RIP_EHIP;
-            return dst;
-        };
-        rd.data = put(ri.data, (size_t)G * npix * esz, b_data);
-        rd.amp33 = (const uint16_t *)put(ri.amp33, (size_t)G * ny * RIP_CW * 2, b_a33);
-        rd.groupdq = (const uint8_t *)put(ri.groupdq, (size_t)G * npix, b_gdq);
-        rd.pixeldq = (const uint32_t *)put(ri.pixeldq, npix * 4, b_pdq);
-        rd.area_factor = (const double *)put(ri.area_factor, npix * 8, b_area);
-        rd.channel_lines = (const double *)put(ri.channel_lines, (size_t)G * nch * 16, b_lines);
-        if (rc == RIP_OK && ri.or_first_group && rd.groupdq) rc = rip_launch_or_bytes(ctx, (uint8_t *)rd.groupdq, npix, (uint8_t)DQ_DO_NOT_USE, s_in);
-        rd.or_first_group = 0;
-        if (rc != RIP_OK) {
+        rip_ramp_desc rd;
+        if (rip_upload_host_ramp(ctx, ri, ny, nx, b.in, s_in, &rd) != RIP_OK) {
             rc = rip_fail(ctx, RIP_EHIP, "calibrate_batch: upload of ramp %d failed", i);
             cleanup();
             return rc;
@@ -123,14 +107,7 @@ extern "C" int rip_calibrate_batch(rip_ctx *ctx, int slot, int plan_id, unsigned
         // chain: after its inputs have landed and the previous results of this set have left
         rd.ready_event = b.ev_in;   // the pre-pass stream and the main stream wait for the upload inside rip_calibrate
         if (b.used) BATCH_HIP(hipStreamWaitEvent(ctx->stream, b.ev_out, 0));
-        rip_outputs od;
-        od.location = RIP_DEVICE;
-        od.slope = (float *)b.out;
-        od.err_read = (float *)(b.out + b_pl);
-        od.err_poisson = (float *)(b.out + 2 * b_pl);
-        od.pixeldq = (uint32_t *)(b.out + 3 * b_pl);
-        od.groupdq = ro.groupdq ? (uint8_t *)(b.out + 4 * b_pl) : nullptr;
-        od.cube = nullptr;
+        const rip_outputs od = rip_result_planes(b.out, ro, npix);
         if ((rc = rip_calibrate(ctx, slot, plan_id, stages, &rd, &od)) != RIP_OK) {
             cleanup();
             return rc;
@@ -138,11 +115,10 @@ extern "C" int rip_calibrate_batch(rip_ctx *ctx, int slot, int plan_id, unsigned
         BATCH_HIP(hipEventRecord(b.ev_done, ctx->stream));
         // download
         BATCH_HIP(hipStreamWaitEvent(s_out, b.ev_done, 0));
-        BATCH_HIP(hipMemcpyAsync(ro.slope, od.slope, npix * 4, hipMemcpyDeviceToHost, s_out));
-        BATCH_HIP(hipMemcpyAsync(ro.err_read, od.err_read, npix * 4, hipMemcpyDeviceToHost, s_out));
-        BATCH_HIP(hipMemcpyAsync(ro.err_poisson, od.err_poisson, npix * 4, hipMemcpyDeviceToHost, s_out));
-        BATCH_HIP(hipMemcpyAsync(ro.pixeldq, od.pixeldq, npix * 4, hipMemcpyDeviceToHost, s_out));
-        if (ro.groupdq) BATCH_HIP(hipMemcpyAsync(ro.groupdq, od.groupdq, (size_t)G * npix, hipMemcpyDeviceToHost, s_out));
+        if ((rc = rip_download_results(ctx, od, ro, G, npix, s_out)) != RIP_OK) {
+            cleanup();
+            return rc;
+        }
         BATCH_HIP(hipEventRecord(b.ev_out, s_out));
         b.used = true;
         ctx->batch_completed = i + 1;

@@ -115,24 +115,43 @@ class Calibrator:
         """
         ny, nx = self.shapes[slot]
         pid, meta = self.plan_for(ramp["read_pattern"], ramp["frame_time"], exclude_first, ramp_opt_pars, jump_pars)
+        dil = read_pattern_dilution(ramp["read_pattern"]) if (flag_saturation and saturation_read_pattern) else None
+        rd, od = _native.RampDesc(), _native.Outputs()
+        res, keep = self._host_ramp(rd, od, ramp, (ny, nx), exclude_first, flag_saturation, saturation_backup,
+                                    saturation_skip_firstn, dil, out, want_groupdq, want_cube, area_factor, channel_lines)
+        self.ctx.calibrate_raw(slot, pid, stages, rd, od)
+        del keep
+        if not (stages & STAGE_RAMPFIT):
+            for k in ("slope", "err_read", "err_poisson"):
+                res.pop(k)
+            res.pop("groupdq", None)
+        res["K"], res["meta"] = meta["K"], meta
+        return res
+
+    def _host_ramp(self, rd, od, ramp, frame, exclude_first, flag_saturation, saturation_backup, saturation_skip_firstn, dil,
+                   given, want_groupdq, want_cube=False, area_factor=None, channel_lines=None, i=None):
+        """Fills ``rd`` / ``od`` (``RampDesc`` / ``Outputs``) for one ramp of numpy arrays (see ``calibrate``) and returns (the
+        result dict, the input arrays the call reads: they must outlive it).  ``dil``: the saturation step's dilution factors or
+        None; ``given``: a dict of preallocated result arrays or None; ``i``: the ramp's index in a batch, for error texts."""
+        ny, nx = frame
         data = np.ascontiguousarray(ramp["data"])
         if data.dtype not in (np.uint16, np.float32):
             data = data.astype(np.float32)
         G = data.shape[0]
         if data.shape != (G, ny, nx):
-            raise ValueError(f"ramp shape {data.shape} does not match the CALDIR frame {(ny, nx)}")
+            raise ValueError(f"{'ramp' if i is None else f'ramp {i}:'} shape {data.shape} does not match the CALDIR frame {frame}")
         gdq = None
         if ramp.get("groupdq") is not None:
             gdq = np.ascontiguousarray(ramp["groupdq"], dtype=np.uint8)   # (DO_NOT_USE on an excluded first group: set on the
             #                                                              library's device copy, rd.or_first_group below)
         elif not flag_saturation:
-            raise ValueError("ramp['groupdq'] is required unless flag_saturation is set")
+            what = "ramp['groupdq']" if i is None else f"ramp {i}: groupdq"
+            raise ValueError(f"{what} is required unless flag_saturation is set")
         pdq = np.ascontiguousarray(ramp["pixeldq"], dtype=np.uint32)
         amp33 = None if ramp.get("amp33") is None else np.ascontiguousarray(ramp["amp33"], dtype=np.uint16)
         area = None if area_factor is None else np.ascontiguousarray(area_factor, dtype=np.float64)
         lines = None if channel_lines is None else np.ascontiguousarray(channel_lines, dtype=np.float64)
 
-        rd = _native.RampDesc()
         rd.location, rd.ngrp = _native.RIP_HOST, G
         rd.data, rd.data_dtype = data.ctypes.data, _native.dtype_code(data)
         rd.amp33 = None if amp33 is None else amp33.ctypes.data
@@ -140,42 +159,31 @@ class Calibrator:
         rd.flag_saturation = 1 if flag_saturation else 0
         rd.or_first_group = 1 if (exclude_first and gdq is not None) else 0   # gen_cal_image.py:142-143, the caller's array untouched
         rd.sat_backup, rd.sat_skip_firstn = int(saturation_backup), int(saturation_skip_firstn)
-        dil = read_pattern_dilution(ramp["read_pattern"]) if (flag_saturation and saturation_read_pattern) else None
         rd.sat_dilution = None if dil is None else dil.ctypes.data
         rd.area_factor = None if area is None else area.ctypes.data
         rd.channel_lines = None if lines is None else lines.ctypes.data
-
-        given = out
 
         def result(name, shape, dtype):
             a = None if given is None else given.get(name)
             if a is None:
                 return self._results.empty(shape, dtype)
             if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError(f"out[{name!r}] must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+                where = "out" if i is None else f"out[{i}]"
+                raise ValueError(f"{where}[{name!r}] must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
             return a
 
-        res = {
-            "slope": result("slope", (ny, nx), np.float32), "err_read": result("err_read", (ny, nx), np.float32),
-            "err_poisson": result("err_poisson", (ny, nx), np.float32), "pixeldq": result("pixeldq", (ny, nx), np.uint32),
-        }
-        out = _native.Outputs()
-        out.location = _native.RIP_HOST
-        out.slope, out.err_read = res["slope"].ctypes.data, res["err_read"].ctypes.data
-        out.err_poisson, out.pixeldq = res["err_poisson"].ctypes.data, res["pixeldq"].ctypes.data
+        res = {"slope": result("slope", frame, np.float32), "err_read": result("err_read", frame, np.float32),
+               "err_poisson": result("err_poisson", frame, np.float32), "pixeldq": result("pixeldq", frame, np.uint32)}
+        od.location = _native.RIP_HOST
+        od.slope, od.err_read = res["slope"].ctypes.data, res["err_read"].ctypes.data
+        od.err_poisson, od.pixeldq = res["err_poisson"].ctypes.data, res["pixeldq"].ctypes.data
         if want_groupdq:
             res["groupdq"] = result("groupdq", (G, ny, nx), np.uint8)
-            out.groupdq = res["groupdq"].ctypes.data
+            od.groupdq = res["groupdq"].ctypes.data
         if want_cube:
             res["cube"] = result("cube", (G, ny, nx), np.float32)
-            out.cube = res["cube"].ctypes.data
-        self.ctx.calibrate_raw(slot, pid, stages, rd, out)
-        if not (stages & STAGE_RAMPFIT):
-            for k in ("slope", "err_read", "err_poisson"):
-                res.pop(k)
-            res.pop("groupdq", None)
-        res["K"], res["meta"] = meta["K"], meta
-        return res
+            od.cube = res["cube"].ctypes.data
+        return res, (data, gdq, pdq, amp33, area, lines)
 
     # ---- a batch of ramps in host memory, pipelined over PCIe --------------------------------
     def calibrate_many(self, slot, ramps, exclude_first=True, ramp_opt_pars=None, jump_pars=None, want_groupdq=False,
@@ -197,49 +205,9 @@ class Calibrator:
         for i, ramp in enumerate(ramps):
             if list(map(list, ramp["read_pattern"])) != list(map(list, ramps[0]["read_pattern"])):
                 raise ValueError(f"ramp {i}: read pattern differs from ramp 0")
-            data = np.ascontiguousarray(ramp["data"])
-            if data.dtype not in (np.uint16, np.float32):
-                data = data.astype(np.float32)
-            G = data.shape[0]
-            if data.shape != (G, ny, nx):
-                raise ValueError(f"ramp {i}: shape {data.shape} does not match the CALDIR frame {(ny, nx)}")
-            gdq = None
-            if ramp.get("groupdq") is not None:
-                gdq = np.ascontiguousarray(ramp["groupdq"], dtype=np.uint8)   # (DO_NOT_USE on an excluded first group: rd.or_first_group)
-            elif not flag_saturation:
-                raise ValueError(f"ramp {i}: groupdq is required unless flag_saturation is set")
-            pdq = np.ascontiguousarray(ramp["pixeldq"], dtype=np.uint32)
-            amp33 = None if ramp.get("amp33") is None else np.ascontiguousarray(ramp["amp33"], dtype=np.uint16)
-            keep.append((data, gdq, pdq, amp33))
-            rd = descs[i]
-            rd.location, rd.ngrp = _native.RIP_HOST, G
-            rd.data, rd.data_dtype = data.ctypes.data, _native.dtype_code(data)
-            rd.amp33 = None if amp33 is None else amp33.ctypes.data
-            rd.groupdq, rd.pixeldq = (None if gdq is None else gdq.ctypes.data), pdq.ctypes.data
-            rd.flag_saturation = 1 if flag_saturation else 0
-            rd.or_first_group = 1 if (exclude_first and gdq is not None) else 0   # gen_cal_image.py:142-143 on the device copy
-            rd.sat_backup, rd.sat_skip_firstn = int(saturation_backup), int(saturation_skip_firstn)
-            if dil is not None:
-                rd.sat_dilution = dil.ctypes.data
-            given = None if out is None else out[i]
-
-            def result(name, shape, dtype, given=given):
-                a = None if given is None else given.get(name)
-                if a is None:
-                    return self._results.empty(shape, dtype)
-                if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
-                    raise ValueError(f"out[{i}][{name!r}] must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
-                return a
-
-            res = {"slope": result("slope", (ny, nx), np.float32), "err_read": result("err_read", (ny, nx), np.float32),
-                   "err_poisson": result("err_poisson", (ny, nx), np.float32), "pixeldq": result("pixeldq", (ny, nx), np.uint32)}
-            od = outs[i]
-            od.location = _native.RIP_HOST
-            od.slope, od.err_read = res["slope"].ctypes.data, res["err_read"].ctypes.data
-            od.err_poisson, od.pixeldq = res["err_poisson"].ctypes.data, res["pixeldq"].ctypes.data
-            if want_groupdq:
-                res["groupdq"] = result("groupdq", (G, ny, nx), np.uint8)
-                od.groupdq = res["groupdq"].ctypes.data
+            res, arrays = self._host_ramp(descs[i], outs[i], ramp, (ny, nx), exclude_first, flag_saturation, saturation_backup,
+                                          saturation_skip_firstn, dil, None if out is None else out[i], want_groupdq, i=i)
+            keep.append(arrays)
             res["K"], res["meta"] = meta["K"], meta
             results.append(res)
         self.ctx.check(self.ctx.lib.rip_calibrate_batch(self.ctx.h, int(slot), int(pid), int(STAGE_ALL), n, descs, outs))
