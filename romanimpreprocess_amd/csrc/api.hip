@@ -832,10 +832,10 @@ struct Calibration {
                   ? (char *)rip_ws(ctx, 3, 2 * tab_bytes + npix * 4 + 512)
                   : nullptr;
         par = ctx->parity;
-        // (by situation: the f64-ipc4d form of up to 8 groups fills the 160 KB of every CU with its partial K ring -- the pre-pass of the
-        // next ramp finds no room beside it, runs when it drains, and the single-launch form in front of the own ramp is the shorter way:
-        // 1.121 against 1.140 ms per ramp, profiles/r04_summary.md)
-        const bool lds_full = c.ipc_dtype == RIP_F64 && G <= 8 && ctx->use_fused && in->data_dtype == RIP_U16;
+        // (by situation: where the fused kernel fills the LDS the pre-pass of the next ramp finds no room beside it, runs when it
+        // drains, and the single-launch form in front of the own ramp is the shorter way: 1.121 against 1.140 ms per ramp at f64
+        // ipc4d x 8 groups, profiles/r04_summary.md)
+        const bool lds_full = rip_chain_fills_lds(G, c.ipc_dtype) && ctx->use_fused && in->data_dtype == RIP_U16;
         overlap = do_ref && !host && ctx->use_overlap && (ctx->overlap_mode == 1 || !lds_full);
         pre = overlap ? ctx->stream2 : ctx->stream;
         int rc;

@@ -14,11 +14,11 @@
 //                                T: flag propagation, finish (dark rate, error split, flat), stores of pixel (r, c)
 // so each role needs <= 128 VGPRs and a CU holds 2 workgroups = 16 waves = 4 waves/SIMD.  That is the 256-column form (f32 ipc4d
 // with 6 / 8 groups, the bench path); 16 groups and f64 ipc4d, whose rings would leave one such workgroup per CU or none, run the
-// NARROW forms (one wide workgroup per CU that drops rings; see the template below).  Per step:
-//     S1: ingest A(r+3)   | fit O2(r), F(r) up to the half-step barrier (C2_BAR)       -- barrier --
+// NARROW forms (one wide workgroup per CU that drops rings; C2Form below).  Per step:
+//     S1: ingest A(r+3)   | fit O2(r) and the first half of F(r)                         -- barrier --
 //     S2: ingest C(r+2)   | fit: the rest of F(r) and T(r), the ring words of row r+1  -- barrier --
-// Everything after O2 is register-only in a fit thread, so the half-step barrier can fall anywhere in it (C2_BAR, chosen per
-// instantiation by same-box A/B).  Rings (3 rows each): x = gain*phi; the first iterate O1 (C writes row r+2 into the slot of
+// Everything after O2 is register-only in a fit thread, so the half-step barrier could fall anywhere in it (C2Form: where it
+// sits and why).  Rings (3 rows each): x = gain*phi; the first iterate O1 (C writes row r+2 into the slot of
 // row r-1, which O2(r) finished reading before the barrier; doubles with f64 ipc4d); the per-pixel words that travel from the
 // ingest thread of a column to its fit thread (merged flag word, packed groupdq bytes, gain); and the K ring (2 rows): the nine
 // IPC coefficients of a pixel are loaded ONCE, by its ingest thread, and handed to its fit thread.  Saturated pixels are
@@ -26,12 +26,6 @@
 #pragma once
 #include "chain_common.h"
 
-#ifndef C2_COLS_DEF
-#define C2_COLS_DEF 256   // (128-column workgroups WITH every ring: 4 % slower, profiles/r03_summary.md; the narrow forms drop rings)
-#endif
-// columns of a workgroup's window: a constant `COLS` of the enclosing template (c2_cols: 256; 384 / 256 in the ring-dropping forms)
-#define C2_COLS COLS
-#define C2_THREADS (2 * C2_COLS)
 // Diagnostic builds only (RIP_TIMING_BUILD: rip_version() then reports a timing build and the Python binding refuses the library
 // unless told otherwise): -DC2_DBG switches phases off by ChainArgs::dbg (results invalid by construction), -DCH_STAMP records
 // per-phase clock stamps.  Nothing else in this header changes what the kernel computes.
@@ -47,36 +41,6 @@
 #define C2_DRAIN()
 #endif
 #define C2_SYNC() __syncthreads()
-// Strip geometry: the window of strip s starts at column s * C2_OUTW; its lanes 2 .. C2_COLS-3 emit, lanes 0, 1 and C2_COLS-2,
-// C2_COLS-1 are the halo of the two 3 x 3 passes -- except at the frame's edge, where columns 0, 1 and nx-2, nx-1 are emitted
-// by those lanes themselves (border pixels: no IPC, no neighbours needed; nb >= 2).  So n strips cover n * C2_OUTW + 4 columns:
-// 33 strips of 128 columns cover 4096 exactly (34 with a uniform 2-column offset), 17 of 256.
-#define C2_OUTW (C2_COLS - 4)
-#define C2_NSTRIPS(nx) (((nx) - 4 + C2_OUTW - 1) / C2_OUTW < 1 ? 1 : ((nx) - 4 + C2_OUTW - 1) / C2_OUTW)
-// Where the half-step barrier falls in the fit role: 0 after the first half of the fit, 1 after its second half (and the saturated
-// refits), 2 after the flag propagation and the group-flag stores, 3 after the finish and the plane stores.  Same-box A/B on the
-// bench frame (profiles/r03_summary.md): f32 ipc4d x 8 groups 0.884 / 0.887 / 0.895 ms for 0 / 1 / 2; 16 groups 2.048 / 2.003 /
-// 2.024; f64 ipc4d 1.354 / 1.328 / 1.280 -- the forms whose IPC stages are longer want the barrier later.  -1: per instantiation.
-#ifndef C2_BAR
-#define C2_BAR -1
-#endif
-// Pairs per block of the linearity phase for the forms with a 256-register budget (16 groups: 2.048 -> 2.008 ms with 4; f64 ipc4d:
-// 1.345 -> 1.360, stays 2)
-#ifndef C2_PBW
-#define C2_PBW -1
-#endif
-#ifndef C2_PBC   // f64 ipc4d: pairs the first iterate evaluates in lockstep (-1: per instantiation)
-#define C2_PBC -1
-#endif
-// narrow forms: the fit role requests its coefficients at the top of the step (0), at the end of the step before (1), or two steps
-// ahead -- half a step after the ingest role's read of the same lines (2: fabric traffic 1.44 -> 1.19 x (f64), 1.50 -> 1.39 x (16
-// groups), 1.38 -> 1.27 x (both), and the kernels 3 % / 0 % / 10 % SLOWER: nine to eighteen more live registers; not bound by bytes)
-#ifndef C2_KFIT_EARLY
-#define C2_KFIT_EARLY 1
-#endif
-#ifndef C2_NBO   // f64 ipc4d: groups the second iterate evaluates in lockstep (2 or 4)
-#define C2_NBO 2
-#endif
 
 // Returns x, opaque to the optimiser: used on loop-invariant per-lane offsets right before a global access so that
 // the zero-extension stays next to the address add and instruction selection can use the
@@ -93,19 +57,6 @@ __device__ __forceinline__ unsigned c2_opaque(unsigned x) {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t c2_rsrc(const void *p) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, -1, 0x00020000);
 }
-// Cache policy of the ONCE-read arrays in the narrow forms (aux bits of the buffer loads; 2 = nt: stream through the caches).  The
-// narrow forms' fit role reads the IPC coefficients (NARROW = 2: gain and groupdq bytes too) a second time one row step after the
-// ingest role; a step of an XCD's 96 workgroups moves about 4 MB -- the size of its L2 -- so those lines have left L2 by then and
-// come back over the fabric (1.4-1.5 x the algorithmic bytes at ~5 TB/s of fabric traffic).  With the hint on everything read once,
-// same-box A/B (profiles/r04_summary.md): 16 groups 1.752 -> 1.730 / 1.780 -> 1.738 ms, f64 x 16 groups 2.414 -> 2.383 / 2.411 ->
-// 2.399 ms, f64 x 8 groups (NARROW = 1) 1.179 -> 1.237 ms SLOWER -- so it is on for NARROW = 2 only.  Results are identical either
-// way.  (256-column form, round 1: hints on the once-read arrays cost 11 %: no second read there.)
-#ifndef C2_STREAM_AUX
-#define C2_STREAM_AUX 2
-#endif
-#ifndef C2_STREAM_N1   // the same for NARROW = 1 (A/B)
-#define C2_STREAM_N1 0
-#endif
 template <int AUX = 0>
 __device__ __forceinline__ float c2_ld_f32(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, AUX));
@@ -207,89 +158,116 @@ __device__ __forceinline__ void c2_div64_shared(const double (&a)[NG], float bf,
     }
 }
 
-// Columns of a workgroup's window.  The ring-dropping (NARROW) forms were 128-column workgroups, three (two) per CU; what they
-// pay is windows at a 124-column pitch: a window row of a byte plane is one 128-byte line, misaligned it touches two (u16: two ->
-// three, f32: four -> five), and the lines shared with the neighbouring strip have left L2 by the time that strip wants them --
-// a third of the algorithmic bytes fetched twice.  ONE workgroup of 384 (256) columns with the same rings dropped has the same
-// waves per SIMD and LDS per CU and a third (half) of the seams.  C2_N*_COLS: A/B switches, results identical.
-#ifndef C2_N1_COLS    // NARROW = 1 (f64 ipc4d x 6 / 8 groups): 43 KB per 128 columns
-#define C2_N1_COLS 384
-#endif
-#ifndef C2_N2_COLS    // NARROW = 2, f32 ipc4d (16 groups): 51 KB per 128 columns
-#define C2_N2_COLS 384
-#endif
-#ifndef C2_N2K_COLS   // NARROW = 2, f64 ipc4d (16 groups): 76 KB per 128 columns
-#define C2_N2K_COLS 256
-#endif
-constexpr int c2_cols(bool k64, int narrow) {
-    return narrow == 0 ? C2_COLS_DEF : (narrow == 1 ? C2_N1_COLS : (k64 ? C2_N2K_COLS : C2_N2_COLS));
-}
-// coefficients of the partial K ring of the NARROW = 1 forms: what fits beside the other rings in 160 KB (C2_N1_KRN: A/B switch)
-#ifndef C2_N1_KRN
-#define C2_N1_KRN 9
-#endif
-constexpr int c2_krn(int G) {
-    // x ring + f64 O1 ring + word rings of C2_N1_COLS columns, lines: what is left over / (2 rows x C2_N1_COLS x 8 bytes)
-    const long used = (long)(G / 2) * C2_N1_COLS * 8 * 3 + (long)G * C2_N1_COLS * 8 * 3 + (long)C2_N1_COLS * 4 * 3 * (2 + (G + 3) / 4) +
-                      (long)(C2_N1_COLS / RIP_CW + 1) * G * 2 * 8;
-    const long fit = (160 * 1024 - used) / (2L * C2_N1_COLS * 8);
-    return fit < 0 ? 0 : (fit > C2_N1_KRN ? C2_N1_KRN : (int)fit);
-}
-// waves per SIMD an instantiation is compiled for (register budget 512 / waves) and launched with
-constexpr int c2_wps(int G, bool k64, int narrow) {
-    return !narrow ? ((G > 8 || k64) ? 2 : 4) : ((k64 && G > 8) ? 2 : ((k64 || G > 8) ? 3 : 4));
-}
+// The forms of the kernel, one per (group count, ipc4d dtype), and every choice that differs between them.  What does not fit the
+// 256-column form's LDS twice per CU runs a NARROW form: one wide workgroup per CU that drops rings, and what a dropped ring
+// carried the fit role loads itself, one step ahead (a second read of lines the ingest role fetched 1.5 steps earlier):
+//   ipc4d  groups  narrow  columns  waves/SIMD  rings
+//   f32    6, 8    0       256      4           every ring, two workgroups per CU (the bench path)
+//   f64    6, 8    1       384      3           a PARTIAL K ring (krn; every ring at 256 columns: 120 KB, one workgroup per CU)
+//   f32    16      2       384      3           no K ring, no gain / groupdq rings
+//   f64    16      2       256      2           no K ring, no gain / groupdq rings
+// Round 3 ran the narrow forms as 128-column workgroups, three (two) per CU: 3 (2) waves per SIMD at <= 168 (256) VGPRs.  What they
+// paid is windows at a 124-column pitch: a window row of a byte plane is one 128-byte line, misaligned it touches two (u16: two ->
+// three, f32: four -> five), and the lines shared with the neighbouring strip have left L2 by the time that strip wants them -- a
+// third of the algorithmic bytes fetched twice.  Round 4: ONE workgroup per CU of 384 columns (f64 x 16 groups: 256) -- the same
+// waves per SIMD and LDS per CU, a third (half) of the seams: 6-8 % faster, same bits.  Same arithmetic as the 256-column form,
+// which keeps 256 columns (128-column workgroups WITH every ring: 4 % slower, profiles/r03_summary.md; the narrow forms are slower
+// there too: same 16 waves per CU).
+// The half-step barrier falls after the first half of the fit in every form.  Same-box A/B of its place -- there / after the second
+// half of the fit and the saturated refits / after the flag propagation and the group-flag stores: f32 ipc4d x 8 groups 0.884 /
+// 0.887 / 0.895 ms (profiles/r03_summary.md); the wide narrow forms (round 4) 16 groups 1.704 / 1.770 / 1.751 ms per ramp, f64 x 16
+// groups 2.251 / 2.278 / 2.302, f64 x 8 groups 1.138 / 1.145 / 1.153.
+template <int G, bool K64>
+struct C2Form {
+    static constexpr int narrow = G > 8 ? 2 : (K64 ? 1 : 0);
+    // columns of a workgroup's window, and its threads (two roles of one thread per column)
+    static constexpr int cols = (narrow == 0 || (narrow == 2 && K64)) ? 256 : 384;
+    static constexpr int threads = 2 * cols;
+    // Strip geometry: the window of strip s starts at column s * outw; its lanes 2 .. cols-3 emit, lanes 0, 1 and cols-2, cols-1
+    // are the halo of the two 3 x 3 passes -- except at the frame's edge, where columns 0, 1 and nx-2, nx-1 are emitted by those
+    // lanes themselves (border pixels: no IPC, no neighbours needed; nb >= 2).  So n strips cover n * outw + 4 columns: 33 strips
+    // of 128 columns cover 4096 exactly (34 with a uniform 2-column offset), 17 of 256.
+    static constexpr int outw = cols - 4;
+    static constexpr int nstrips(int nx) { return (nx - 4 + outw - 1) / outw < 1 ? 1 : (nx - 4 + outw - 1) / outw; }
+    // waves per SIMD it is compiled for (register budget 512 / waves: 128, 168, 256 VGPRs) and launched with
+    static constexpr int wps = narrow == 0 ? 4 : ((narrow == 2 && K64) ? 2 : 3);
 
-// NARROW forms (the ring-dropping forms): what does not fit the 256-column form's LDS budget twice per CU drops rings, and what a
-// dropped ring carried the fit role loads itself, one step ahead (a second read of lines the ingest role fetched 1.5 steps earlier):
-//   NARROW = 1  a PARTIAL K ring (what the LDS left   f64 ipc4d x 6 / 8 groups: 43 KB per 128 columns (with every ring: 120 KB per 256);
-//               over holds: c2_krn, KRN below)         at 384 columns 5 (8 groups) / 9 (6 groups) of the nine f64 coefficients travel
-//                                                      through LDS, the fit role reads the others again: traffic 1.33 -> 1.17 x
-//   NARROW = 2  no K ring, no gain / groupdq rings     16 groups: 51 KB per 128 columns; f64 ipc4d x 16 groups: 76 KB
-// Round 3 ran them as 128-column workgroups, three (two) per CU: 3 (2) waves per SIMD at <= 168 (256) VGPRs.  Round 4: ONE
-// workgroup per CU of 384 columns (f64 x 16 groups: 256) -- the same waves per SIMD and LDS per CU, a third (half) of the seams
-// between strips, whose misaligned, twice-fetched lines were a third of these forms' excess traffic (c2_cols above): 6-8 % faster,
-// same bits.  Same arithmetic as the 256-column form.  For f32 ipc4d x 8 groups these forms are slower (same 16 waves per CU).
-template <int NP, int G, int START, typename KT = float, int NARROW = 0>
-__global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, sizeof(KT) == 8, NARROW)) void chain2_kernel(ChainArgs a, const RipPlanHeader *__restrict__ h,
-                                                               const RipVariant *__restrict__ vars,
-                                                               const float *__restrict__ kvals,
-                                                               const RipDiff *__restrict__ diffs, double guard) {
+    // The LDS layout, byte offsets; the ring slots of a row are `cols` columns wide:
+    static constexpr int ks = K64 ? 8 : 4;                               // bytes of a coefficient and of an O1 value
+    static constexpr int x_ofs = 0;                                      // [G/2][3] f2: x = gain*phi, pair-interleaved
+    static constexpr int o1_ofs = x_ofs + G / 2 * 3 * cols * 8;          // [G/2][3] f2 (f64 ipc4d: [G][3] double): first iterate
+    static constexpr int dq_ofs = o1_ofs + G * 3 * cols * ks;            // [3] u32: the flag word of the pixel
+    // the packed groupdq bytes and the gain of the pixel travel from the ingest thread of a column to its fit thread too --
+    // except in the 16-group forms, whose fit role loads them itself, like the coefficients
+    static constexpr bool wring = narrow < 2;
+    static constexpr int qs_ofs = dq_ofs + 3 * cols * 4;                          // [3][(G+3)/4] u32: groupdq bytes, packed
+    static constexpr int gn_ofs = qs_ofs + (wring ? 3 * ((G + 3) / 4) * cols * 4 : 0);  // [3] f32: gain
+    static constexpr int nlc = cols / RIP_CW + 1;                                 // channels a window can touch (not channel-aligned)
+    static constexpr int ln_ofs = gn_ofs + (wring ? 3 * cols * 4 : 0);            // [nlc][G][2] double: channel lines of this strip
+    static constexpr int kr_ofs = ln_ofs + nlc * G * 2 * 8;                       // [2][krn] KT: the K ring
+    // Coefficients the K ring holds: all nine, or what the rest of the layout leaves of the 160 KB of a CU.  That cap matters at
+    // f64 ipc4d x 8 groups (129.5 KB at 384 columns): the first five of the nine f64 coefficients travel from the ingest thread to
+    // the fit thread through LDS, the fit role reads only the other four planes a second time -- 32 instead of 72 bytes per pixel of
+    // re-read (traffic 1.33 -> 1.18 x), five loads fewer per step in flight in the fit role.  The 16-group forms have no K ring.
+    static constexpr int krn_room = (160 * 1024 - kr_ofs) / (2 * cols * ks);
+    static constexpr int krn = narrow == 2 ? 0 : (krn_room < 9 ? krn_room : 9);
+    static constexpr int lds_bytes = kr_ofs + 2 * krn * cols * ks;
+    static_assert(lds_bytes <= (narrow == 0 ? 80 : 160) * 1024, "the 256-column form runs two workgroups per CU, the others one");
+
+    // Cache policy of the ONCE-read arrays (aux bits of the buffer loads; 2 = nt: stream through the caches).  The narrow forms' fit
+    // role reads the IPC coefficients (16 groups: gain and groupdq bytes too) a second time one row step after the ingest role; a
+    // step of an XCD's 96 workgroups moves about 4 MB -- the size of its L2 -- so those lines have left L2 by then and come back
+    // over the fabric (1.4-1.5 x the algorithmic bytes at ~5 TB/s of fabric traffic).  With the hint on everything read once,
+    // same-box A/B (profiles/r04_summary.md): 16 groups 1.752 -> 1.730 / 1.780 -> 1.738 ms, f64 x 16 groups 2.414 -> 2.383 / 2.411 ->
+    // 2.399 ms, f64 x 8 groups 1.179 -> 1.237 ms SLOWER -- so it is on for the 16-group forms only.  Results are identical either
+    // way.  (256-column form, round 1: hints on the once-read arrays cost 11 %: no second read there.)
+    static constexpr int stream_aux = narrow == 2 ? 2 : 0;
+    // pairs per block of the linearity phase (their recurrences interleave): 2 at 128 and 168 registers; by same-box A/B at the
+    // 16-group forms (profiles/r04_ab_runs.txt): at 168 registers 1 (1.697 against 1.710 ms; 4 spills: 3.46), f64 ipc4d at 256
+    // registers 4 (2.24 against 2.27)
+    static constexpr int pb = narrow == 2 ? (K64 ? 4 : 1) : ((G / 2) % 2 == 0 ? 2 : 1);
+    // f64 ipc4d: pairs the first iterate evaluates in lockstep -- two at 256 registers (f64 x 16 groups: 2.23 / 2.25 ms for 2 / 1),
+    // one at 168
+    static constexpr int pbc = wps == 2 ? 2 : 1;
+    // f64 ipc4d: groups the second iterate evaluates in lockstep (16 groups: 256 registers, four)
+    static constexpr int nbo = G > 8 ? 4 : 2;
+};
+
+template <int NP, int G, int START, typename KT>
+__global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, sizeof(KT) == 8>::wps)) void chain2_kernel(
+    ChainArgs a, const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars, const float *__restrict__ kvals,
+    const RipDiff *__restrict__ diffs, double guard) {
     static_assert(G % 2 == 0 && G > 4 && G <= 16, "pairs of groups; the groupdq bytes travel packed four to a word");
-    constexpr int COLS = c2_cols(sizeof(KT) == 8, NARROW);
-    constexpr bool KRING = !NARROW;
-    // NARROW = 1 (f64 ipc4d x 6 / 8 groups; 129.5 KB of the 160 at 384 columns): the LDS left over holds a PARTIAL K ring -- the
-    // first KRN of the nine f64 coefficients travel from the ingest thread to the fit thread through LDS (two rows, like the full ring
-    // of the 256-column form), the fit role reads only the other 9 - KRN planes a second time: 32 instead of 72 bytes per pixel of
-    // re-read (traffic 1.33 -> 1.18 x), five loads fewer per step in flight in the fit role
-    constexpr int KRN = KRING ? 9 : ((NARROW == 1 && sizeof(KT) == 8) ? c2_krn(G) : 0);
-    constexpr bool WRING = NARROW < 2;   // NARROW = 2 (16 groups): gain and packed groupdq bytes do not travel through LDS either --
-                                         // the fit role loads them itself, like the coefficients (51 KB: three workgroups per CU)
+    using F = C2Form<G, sizeof(KT) == 8>;
+    constexpr int COLS = F::cols;
+    constexpr int KRN = F::krn;
+    // narrow forms: the fit role requests the coefficients the K ring does not carry itself (k >= KRN: none at f64 ipc4d x 6
+    // groups, where the partial ring has room for all nine)
+    constexpr bool KFIT = F::narrow > 0;
     constexpr int QW = (G + 3) / 4;  // words of packed group flags per pixel
     constexpr int GP = G / 2;
     // f64 ipc4d (KT = double; the reference's production writer stores f64): x = gain*phi stays f32, the Neumann iterates and
     // the division by the gain are f64 (numpy promotion, ipc_linearity.py:95-142), so the O1 ring holds doubles, one plane per
-    // group: 94 KB of LDS for 8 groups, one workgroup per CU (2 waves/SIMD, up to 256 VGPRs)
+    // group
     constexpr bool K64 = sizeof(KT) == 8;
-    constexpr int SA = NARROW == 2 ? C2_STREAM_AUX : (NARROW == 1 ? C2_STREAM_N1 : 0);   // cache policy of the once-read arrays
+    constexpr int SA = F::stream_aux;   // cache policy of the once-read arrays
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr int XR = 3;  // rows of the x ring
-    f2 *X2 = reinterpret_cast<f2 *>(lds_raw);                       // [GP][XR][C2_COLS]  x = gain*phi, pair-interleaved
-    f2 *O12 = X2 + GP * XR * C2_COLS;                               // [GP][3][C2_COLS]  first Neumann iterate
-    double *O1d = reinterpret_cast<double *>(O12);                  // f64 ipc4d: [G][3][C2_COLS] instead
-    uint32_t *DQ = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(O12) +
-                                                (size_t)G * 3 * C2_COLS * sizeof(KT));  // [4][C2_COLS] linearity dq of the row
-    // per-pixel words that travel from the ingest thread of a column to its fit thread (3-row rings, slots as the x ring: the fit
-    // thread takes row r+1's at the end of step r): the flag word, the packed groupdq bytes, the gain
-    uint32_t *QS = DQ + 3 * C2_COLS;                                // [3][QW][C2_COLS] groupdq bytes of the pixel, packed
-    float *GN = reinterpret_cast<float *>(QS + (WRING ? 3 * QW * C2_COLS : 0));   // [3][C2_COLS] gain of the pixel (f32)
-    double *LN = reinterpret_cast<double *>(GN + (WRING ? 3 * C2_COLS : 0));       // [NLC][G][2] channel lines of this strip
+    f2 *X2 = reinterpret_cast<f2 *>(lds_raw + F::x_ofs);         // [GP][XR][COLS]
+    f2 *O12 = reinterpret_cast<f2 *>(lds_raw + F::o1_ofs);       // [GP][3][COLS]
+    double *O1d = reinterpret_cast<double *>(lds_raw + F::o1_ofs);   // f64 ipc4d: [G][3][COLS] instead
+    // per-pixel words from the ingest thread of a column to its fit thread (slots as the x ring: the fit thread takes row r+1's at
+    // the end of step r)
+    uint32_t *DQ = reinterpret_cast<uint32_t *>(lds_raw + F::dq_ofs);   // [3][COLS] flag word
+    uint32_t *QS = reinterpret_cast<uint32_t *>(lds_raw + F::qs_ofs);   // [3][QW][COLS] groupdq bytes, packed
+    float *GN = reinterpret_cast<float *>(lds_raw + F::gn_ofs);         // [3][COLS] gain
+    double *LN = reinterpret_cast<double *>(lds_raw + F::ln_ofs);       // [NLC][G][2]
     // K ring: the nine IPC coefficients of destination (row, col), loaded ONCE by the ingest thread of the column and handed to
     // its fit thread (two rows live: C of row y runs two steps before O2 of row y)
-    constexpr int NLC = C2_COLS / RIP_CW + 1;                       // channels a window can touch (a window is not channel-aligned)
-    f2 *KR2 = reinterpret_cast<f2 *>(LN + NLC * G * 2);               // f32 ipc4d: [2][4][C2_COLS] pairs (k0,k1)..(k6,k7)
-    float *KR1 = reinterpret_cast<float *>(KR2 + 2 * 4 * C2_COLS);  //            [2][C2_COLS] k8
-    double *KRd = reinterpret_cast<double *>(LN + NLC * G * 2);       // f64 ipc4d: [2][KRN][C2_COLS]
+    constexpr int NLC = F::nlc;
+    f2 *KR2 = reinterpret_cast<f2 *>(lds_raw + F::kr_ofs);              // f32 ipc4d: [2][4][COLS] pairs (k0,k1)..(k6,k7)
+    float *KR1 = reinterpret_cast<float *>(KR2 + 2 * 4 * COLS);        //            [2][COLS] k8
+    double *KRd = reinterpret_cast<double *>(lds_raw + F::kr_ofs);      // f64 ipc4d: [2][KRN][COLS]
 
     // ChainArgs is the first kernel argument: it sits at offset 0 of the kernarg segment
     const RIP_K C2KernArgs *kargs = (const RIP_K C2KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -299,8 +277,8 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #else
     constexpr int dbg = 0;
 #endif
-    const bool fit_role = tid >= C2_COLS;
-    const int col = fit_role ? tid - C2_COLS : tid;
+    const bool fit_role = tid >= COLS;
+    const int col = fit_role ? tid - COLS : tid;
     const int ny = a.ny, nx = a.nx, nb = a.nb;
     const int ay0 = nb, ay1 = ny - nb, ax0 = nb, ax1 = nx - nb;
     const unsigned npix = (unsigned)ny * (unsigned)nx;
@@ -316,28 +294,29 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
         chf[L] = (float)((double)(L * (L + 1)) / 2.0);
     }
 
-    const int nstrips = C2_NSTRIPS(nx);
+    const int nstrips = F::nstrips(nx);
     const int bid = c2_xcd_block((int)blockIdx.x, (int)gridDim.x);
-    // (strip, row range) of this workgroup -- in QUAD mode (the last strip, when it has at most 64 live columns) of each of its four
-    // (narrow forms: two) wave columns: 64-column windows (2 + 2 halo lanes each) of the same strip that march down four different row ranges, so that
-    // a strip a quarter as wide takes a quarter of the workgroups (launcher: chain2_geometry)
+    // (strip, row range) of this workgroup -- in QUAD mode (the last strip, when it has at most 64 live columns) of each of its
+    // COLS / 64 wave columns (four at 256 columns, six at 384): 64-column windows (2 + 2 halo lanes each) of the same strip that
+    // march down as many different row ranges, so that a strip 64 columns wide takes 64 / COLS of the workgroups of a full one
+    // (launcher: chain2_geometry)
     const int nfull = a.geo_rows_q ? nstrips - 1 : nstrips;
     const bool quad = bid >= nfull * a.geo_nr;
     const int rows_wg = quad ? a.geo_rows_q : a.geo_rows;   // steps of every wave of the workgroup (barriers inside)
     const int strip = quad ? nfull : bid % nfull;
     const int wcol = quad ? (col & 63) : col;               // column inside the wave column's window
-    const int wl = quad ? 64 : C2_COLS;                     // ... and its width
-    const int R0 = min(ny, quad ? ((bid - nfull * a.geo_nr) * (C2_COLS / 64) + __builtin_amdgcn_readfirstlane(col >> 6)) * rows_wg
+    const int wl = quad ? 64 : COLS;                     // ... and its width
+    const int R0 = min(ny, quad ? ((bid - nfull * a.geo_nr) * (COLS / 64) + __builtin_amdgcn_readfirstlane(col >> 6)) * rows_wg
                                 : (bid / nfull) * rows_wg);
     const int R1 = min(ny, R0 + rows_wg);
     if (bid >= nfull * a.geo_nr + a.geo_nq) return;
-    const int c = strip * C2_OUTW + wcol;
+    const int c = strip * F::outw + wcol;
     const bool col_ok = (c >= 0 && c < nx);
     const bool col_act = (c >= ax0 && c < ax1);
     const int cc = col_ok ? c : 0;
-    const int ch0 = (strip * C2_OUTW) / RIP_CW;
+    const int ch0 = (strip * F::outw) / RIP_CW;
     const int chr = cc / RIP_CW - ch0;
-    for (int i = tid; i < NLC * G * 2; i += C2_THREADS) {
+    for (int i = tid; i < NLC * G * 2; i += F::threads) {
         const int ch = i / (G * 2), g = (i / 2) % G, w = i & 1;
         LN[i] = (ch0 + ch < nch) ? a.lines[(g * nch + ch0 + ch) * 2 + w] : 0.0;
     }
@@ -460,7 +439,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #pragma unroll
             for (int g = g0; g < g1; ++g) {
                 rr.S[g] = c2_ld_u16<SA>(rs, cc2, o2);
-                rr.q[g] = c2_ld_u8<WRING ? SA : 0>(rq, cc1, o1);   // (NARROW = 2: the fit role reads these bytes again)
+                rr.q[g] = c2_ld_u8<F::wring ? SA : 0>(rq, cc1, o1);   // (16 groups: the fit role reads these bytes again)
                 rr.dk[g] = c2_ld_f32<SA>(rd, cc4, o4);
                 rr.bs[g] = c2_ld_f32<SA>(rb, cc4, o4);
                 o4 += pl4;
@@ -489,7 +468,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                 else if (i == NP + 3)   // the flag word: linearity dq merged with what the finish step ORs into pixeldq (RipCal)
                     rr.dq = c2_ld_u32<SA>(rp, cc4, yl * row4 + (unsigned)(NP + ka->merged_dq) * pl4);
                 else
-                    rr.gain = c2_ld_f32<WRING ? SA : 0>(rp, cc4, o4);
+                    rr.gain = c2_ld_f32<F::wring ? SA : 0>(rp, cc4, o4);
                 o4 += pl4;
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -532,7 +511,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
             // load that exists on one side of a branch only forces vmcnt(0) at later uses).  All lanes compute (lanes
             // beyond the frame edge work on the clamped column and store zeros).
             const int xslot = (so_c == 2) ? 0 : so_c + 1;    // 3-row rings (x and the per-pixel words): row yi = r + 3 takes the slot of row r
-            f2 *xs = X2 + xslot * C2_COLS + col;
+            f2 *xs = X2 + xslot * COLS + col;
             const bool act = col_act && yi >= ay0 && yi < ay1;
             uint32_t dq = rr.dq;
             uint32_t w[QW];  // the pixel's groupdq bytes, packed
@@ -543,11 +522,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
             const bool fastdiv = __all(rcp_safe(span));
             const float rspan = rip_rcp_mid(span);  // used only when every lane passes rcp_safe (2^-59.8 .. 2^59.8)
             const double yd = (double)yi;
-            // pairs per block (their recurrences interleave): 2 at 128 registers; per instantiation by same-box A/B at the wide forms
-            // (profiles/r04_ab_runs.txt): 16 groups at 168 registers 1 (1.697 against 1.710 ms; 4 spills: 3.46), f64 ipc4d x 16 groups at
-            // 256 registers 4 (2.24 against 2.27)
-            constexpr int PBW = (C2_PBW > 0) ? C2_PBW : (NARROW == 2 ? (K64 ? 4 : 1) : 2);
-            constexpr int PB = ((K64 || G > 8) && GP % PBW == 0) ? PBW : (GP % 2 == 0) ? 2 : 1;
+            constexpr int PB = F::pb;   // pairs per block: their recurrences interleave
 #pragma unroll
             for (int pb = 0; pb < GP; pb += PB) {
                 f2 zz[PB], SS[PB];
@@ -599,7 +574,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                 fetch_groups(ka, r + 4, 2 * pb, 2 * (pb + PB), rr);
                 if (a_full && (dbg & 16)) {
 #pragma unroll
-                    for (int b = 0; b < PB; ++b) xs[(pb + b) * XR * C2_COLS] = zz[b] + f2{1000.0f, 1100.0f};
+                    for (int b = 0; b < PB; ++b) xs[(pb + b) * XR * COLS] = zz[b] + f2{1000.0f, 1100.0f};
                 } else if (a_full) {
                     const bool slow = __any(any_ex);
                     f2 phi[PB];
@@ -670,20 +645,20 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                         }
                         f2 xv = {vout[0], vout[1]};
                         if (act) xv = xv * rr.gain;
-                        xs[p * XR * C2_COLS] = col_ok ? xv : f2{0.0f, 0.0f};
+                        xs[p * XR * COLS] = col_ok ? xv : f2{0.0f, 0.0f};
                     }
                 } else if (do_a) {
 #pragma unroll
-                    for (int b = 0; b < PB; ++b) xs[(pb + b) * XR * C2_COLS] = f2{0.0f, 0.0f};
+                    for (int b = 0; b < PB; ++b) xs[(pb + b) * XR * COLS] = f2{0.0f, 0.0f};
                 }
             }
             if (do_a) {
                 const bool keep = a_full && col_ok;
-                DQ[xslot * C2_COLS + col] = keep ? dq : 0u;
-                if constexpr (WRING) {
+                DQ[xslot * COLS + col] = keep ? dq : 0u;
+                if constexpr (F::wring) {
 #pragma unroll
-                    for (int i = 0; i < QW; ++i) QS[(xslot * QW + i) * C2_COLS + col] = keep ? w[i] : 0u;
-                    GN[xslot * C2_COLS + col] = rr.gain;
+                    for (int i = 0; i < QW; ++i) QS[(xslot * QW + i) * COLS + col] = keep ? w[i] : 0u;
+                    GN[xslot * COLS + col] = rr.gain;
                 }
             }
             // IPC coefficients of row yc, consumed by C after the barrier; issued here so that their registers are not live
@@ -713,17 +688,16 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                     const int ks = yc & 1;
                     if constexpr (K64) {
 #pragma unroll
-                        for (int k = 0; k < KRN; ++k) KRd[(ks * KRN + k) * C2_COLS + col] = kCd[k];
+                        for (int k = 0; k < KRN; ++k) KRd[(ks * KRN + k) * COLS + col] = kCd[k];
                     } else {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) KR2[(ks * 4 + i) * C2_COLS + col] = kC[i];
-                        KR1[ks * C2_COLS + col] = kC[4].x;
+                        for (int i = 0; i < 4; ++i) KR2[(ks * 4 + i) * COLS + col] = kC[i];
+                        KR1[ks * COLS + col] = kC[4].x;
                     }
                 }
                 if constexpr (K64) {
-                    // two pairs (four groups) in lockstep: their 18 ring reads first, then four interleaved f64 chains
-                    constexpr bool BIG = !NARROW || (K64 && G > 8);   // 256-register budget (narrow f64 x 8 groups: 168 -- one pair at a time)
-                    constexpr int PBC = (C2_PBC > 0) ? C2_PBC : ((GP % 2 == 0 && BIG) ? 2 : 1);   // (f64 x 16 groups with C2_PBW 4: 2.23 / 2.25 ms for 2 / 1)
+                    // PBC pairs in lockstep: their ring reads first, then interleaved f64 chains
+                    constexpr int PBC = F::pbc;
 #pragma unroll
                     for (int p0 = 0; p0 < GP; p0 += PBC) {
 #pragma unroll
@@ -733,8 +707,8 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                             float v[2 * PBC][9];
 #pragma unroll
                             for (int q = 0; q < PBC; ++q) {
-                                const f2 *xb = X2 + (p0 + q) * XR * C2_COLS + col;
-                                const f2 *xm_ = xb + sm * C2_COLS, *x0_ = xb + s0 * C2_COLS, *xp_ = xb + sp * C2_COLS;
+                                const f2 *xb = X2 + (p0 + q) * XR * COLS + col;
+                                const f2 *xm_ = xb + sm * COLS, *x0_ = xb + s0 * COLS, *xp_ = xb + sp * COLS;
                                 const f2 tt[9] = {x0_[0], xm_[0], xp_[0], x0_[-1], x0_[1], xm_[-1], xm_[1], xp_[-1], xp_[1]};
 #pragma unroll
                                 for (int k = 0; k < 9; ++k) v[2 * q][k] = tt[k].x, v[2 * q + 1][k] = tt[k].y;
@@ -747,7 +721,7 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #pragma unroll
                             for (int b = 0; b < 2 * PBC; ++b) {
                                 const float xc = v[b][0];
-                                O1d[((2 * p0 + b) * 3 + so) * C2_COLS + col] = (double)(xc + xc) - f[b];
+                                O1d[((2 * p0 + b) * 3 + so) * COLS + col] = (double)(xc + xc) - f[b];
                             }
                         }
                     }
@@ -758,22 +732,22 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #pragma unroll
                     for (int p0 = 0; p0 < GP; ++p0) {
                         fetch_coefs(kb2, r + 4, p0 * CO_STEP, (p0 * CO_STEP + CO_STEP < NCO) ? p0 * CO_STEP + CO_STEP : NCO, rr);
-                        const f2 *xb = X2 + p0 * XR * C2_COLS;
-                        const f2 *xm[1] = {xb + sm * C2_COLS}, *x0[1] = {xb + s0 * C2_COLS}, *xp[1] = {xb + sp * C2_COLS};
+                        const f2 *xb = X2 + p0 * XR * COLS;
+                        const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
                         f2 f[1], xc[1];
                         fwd_rows_batch<1, true>(xm, x0, xp, col, kC, vC, f, xc);
-                        O12[(p0 * 3 + so) * C2_COLS + col] = (xc[0] + xc[0]) - f[0];
+                        O12[(p0 * 3 + so) * COLS + col] = (xc[0] + xc[0]) - f[0];
                     }
                 } else {
 #pragma unroll
                     for (int p0 = 0; p0 < GP; ++p0) {
                         fetch_coefs(kb2, r + 4, p0 * CO_STEP, (p0 * CO_STEP + CO_STEP < NCO) ? p0 * CO_STEP + CO_STEP : NCO, rr);
                         if (do_c && !(dbg & 1)) {
-                            const f2 *xb = X2 + p0 * XR * C2_COLS;
-                            const f2 *xm[1] = {xb + sm * C2_COLS}, *x0[1] = {xb + s0 * C2_COLS}, *xp[1] = {xb + sp * C2_COLS};
+                            const f2 *xb = X2 + p0 * XR * COLS;
+                            const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
                             f2 f[1], xc[1];
                             fwd_rows_batch<1, false>(xm, x0, xp, col, kC, vC, f, xc);
-                            O12[(p0 * 3 + so) * C2_COLS + col] = (xc[0] + xc[0]) - f[0];
+                            O12[(p0 * 3 + so) * COLS + col] = (xc[0] + xc[0]) - f[0];
                         }
                     }
                 }
@@ -797,16 +771,10 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #pragma unroll
         for (int i = 0; i < QW; ++i) qw_next[i] = 0;
         int o0_r = (R0 - 5 + 3000) % 3;  // O1 ring slot of row r
-        uint32_t qb_next[WRING ? 1 : G];   // NARROW = 2: the raw groupdq bytes of the next step's pixel
+        uint32_t qb_next[F::wring ? 1 : G];   // 16 groups: the raw groupdq bytes of the next step's pixel
 #pragma unroll
-        for (int g = 0; g < (WRING ? 1 : G); ++g) qb_next[g] = 0;
-        f2 kn2[5];      // (C2_KFIT_EARLY == 2: those of the row after)
-        double kn2_d[9];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) kn2[i] = f2{0.0f, 0.0f};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) kn2_d[k] = 0.0;
-        f2 kn[5];       // narrow form: the coefficients of the next step's row (C2_KFIT_EARLY)
+        for (int g = 0; g < (F::wring ? 1 : G); ++g) qb_next[g] = 0;
+        f2 kn[5];       // narrow forms: the coefficients of the next step's row
         double kn_d[9];
 #pragma unroll
         for (int i = 0; i < 5; ++i) kn[i] = f2{0.0f, 0.0f};
@@ -843,118 +811,16 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
             CH_T(0)
             C2_DRAIN()
             CH_T(1)
-            // (round 4, the wide ring-dropping forms, same box: 0 / 1 / 2 = 16 groups 1.704 / 1.770 / 1.751 ms per ramp, f64 x 16
-            // groups 2.251 / 2.278 / 2.302, f64 x 8 groups 1.138 / 1.145 / 1.153)
-            constexpr int BAR = (C2_BAR >= 0) ? C2_BAR : (NARROW ? 0 : (K64 ? 2 : (G > 8 ? 1 : 0)));
-            // The tail of pixel (r, c) in three parts; the half-step barrier falls between two of them (C2_BAR: everything after O2 is
-            // register-only in a fit thread, so the barrier sits where both roles take about the same time in both halves).
-            float s = 0.0f, er = 0.0f, ep = 0.0f;
-            uint32_t jmask = 0, pdq = 0;
-            // second half of the fit: exact pass where needed, jump mask; then the saturated refits
-            auto part_fb = [&](const RIP_K C2KernArgs *kx) {
-                if (kx->a.cube_out) {
-#pragma unroll
-                    for (int g = 0; g < G; ++g) kx->a.cube_out[(unsigned)g * npix + pe] = d[g];
-                }
-                uint32_t qor = 0;
-#pragma unroll
-                for (int i = 0; i < QW; ++i) qor |= qw[i];
-                const bool anysat = (qor & 0x02020202u) != 0u;
-                const bool unsat = ((qw[(G - 1) / 4] >> (8 * ((G - 1) & 3))) & DQ_SATURATED) == 0;
-                if (dbg & 4) {
-                    s = d[0], er = e_read, ep = e_gain;
-                } else {
-                    fit_full_pk_b<G>(dpair, kx->h, fc0, kx->a.dense, kx->kvals + v0.k_ofs, kx->diffs + v0.diff_ofs, unsat && act,
-                                     fs, jmask);
-                    s = fs.s, er = fs.er, ep = fs.ep;
-                    if (__any(anysat)) {
-                        uint32_t qe[G];
-#pragma unroll
-                        for (int g = 0; g < G; ++g) qe[g] = (qw[g / 4] >> (8 * (g & 3))) & 0xffu;
-                        trunc_layers<G, G - 1>(d, qe, kx->h, kx->vars, kx->kvals, kx->diffs, e_gain, e_read, act, kx->guard, s, er, ep,
-                                               jmask);
-                    }
-                }
-            };
-            // T, first part: flag propagation (fitting.py:339-353) and the stores of the group flags
-            auto part_flags = [&](const RIP_K C2KernArgs *kx) {
-                if (dbg & 8) return;
-                uint8_t *gq = (kx->a.gdq_out && !(dbg & 512)) ? kx->a.gdq_out + pe_row : nullptr;
-                pdq = propagate_flags_packed<G>(qw, jmask, start, e_pdq | lin_dq, gq, npix, c2_opaque(cc1));
-            };
-            // T, second part: finish and the stores of the four planes
-            auto part_finish = [&](const RIP_K C2KernArgs *kx) {
-                if (dbg & 8) return;
-                if (kx->a.finish) {
-                    // gen_cal_image.py:458-475, 213-229, 607-629.  One wave vote selects the straight-line form built
-                    // from the short exact operations (rip_rcp_mid, rip_sqrt_mid, sqrt(x*x) = x: tools/gpu_checks/
-                    // fpcheck.hip); every intermediate then lies in their validated range 2^-100 .. 2^100 or is +0.
-                    const float sd = (act && kx->a.dark_rate) ? s - e_dark : s;
-                    const bool lean = kx->a.flat && __all(act && rip_mid36(sd) && (er == 0.0f || rip_mid36(er)) &&
-                                                          (ep == 0.0f || rip_mid36(ep)) && e_flat > 0.0f && rip_mid36(e_flat));
-                    if (lean) {
-                        const float err = hypot_f32(er, ep);
-                        const float ep2 = ep;  // sqrt(ep * ep)
-                        const float e2 = err * err;
-                        const float p2 = ep2 * ep2;
-                        const float er2 = rip_sqrt_mid(clip_lo<float>(e2 - p2, 0.0f));
-                        const float rflat = rip_rcp_mid(e_flat);
-                        s = div_rcp(sd, e_flat, rflat);
-                        er = div_rcp(er2, e_flat, rflat);
-                        ep = div_rcp(ep2, e_flat, rflat);
-                    } else {
-                        float err = hypot_f32(er, ep);
-                        float vp = ep * ep;
-                        if (!act) {
-                            s = 0.0f;
-                            err = 0.0f;
-                            vp = 0.0f;
-                        }
-                        if (act && kx->a.dark_rate) s = s - e_dark;
-                        float ep2 = sqrtf(vp);
-                        const float e2 = err * err;
-                        const float p2 = ep2 * ep2;
-                        float er2 = sqrtf(clip_lo<float>(e2 - p2, 0.0f));
-                        if (kx->a.flat) {
-                            s = s / e_flat;
-                            er2 = er2 / e_flat;
-                            ep2 = ep2 / e_flat;
-                        }
-                        er = er2;
-                        ep = ep2;
-                    }
-                }
-                const unsigned w4 = c2_opaque(cc4);
-                // (dbg & 512: timing experiment without the plane stores; the test keeps the four values live)
-                if (!(dbg & 512) || (s + er + ep == 12345.678f && pdq == 0xdeadbeefu)) {
-                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kx->a.slope) + t_row4 + w4) = s;
-                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kx->a.err_read) + t_row4 + w4) = er;
-                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kx->a.err_poisson) + t_row4 + w4) = ep;
-                    *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(kx->a.pdq_out) + t_row4 + w4) = pdq;
-                }
-            };
-            // narrow form: the fit role loads the nine coefficients of destination (r, col) itself (all lanes: clamped addresses)
+            // narrow forms: the fit role loads the coefficients the K ring does not carry itself (all lanes: clamped addresses),
+            // requested at the end of the step before: they land across the barrier
             f2 kF[5];
             double kFd[9];
             kF[4].y = 0.0f;
-            if constexpr (!KRING) {
-#if C2_KFIT_EARLY   // requested at the end of the step before (they land across the barrier); 2: two steps before
+            if constexpr (KFIT) {
 #pragma unroll
                 for (int k = 0; k < 9; ++k) kFd[k] = kn_d[k];
 #pragma unroll
                 for (int i = 0; i < 5; ++i) kF[i] = kn[i];
-#if C2_KFIT_EARLY == 2
-#pragma unroll
-                for (int k = 0; k < 9; ++k) kn_d[k] = kn2_d[k];
-#pragma unroll
-                for (int i = 0; i < 5; ++i) kn[i] = kn2[i];
-#endif
-#else
-                if constexpr (K64)
-                    (void)load_kd(kf->a.kern, r, true, kFd, C2Int<KRN>{});
-                else
-                    (void)load_k(kf->a.kern, r, true, kF);
-#endif
             }
             if (emit) {
                 // the nine coefficients of destination (r, col) from the ingest thread of this column
@@ -962,17 +828,17 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                     const int ks = r & 1;
                     if constexpr (K64) {
 #pragma unroll
-                        for (int k = 0; k < KRN; ++k) kFd[k] = KRd[(ks * KRN + k) * C2_COLS + col];
+                        for (int k = 0; k < KRN; ++k) kFd[k] = KRd[(ks * KRN + k) * COLS + col];
                     } else {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) kF[i] = KR2[(ks * 4 + i) * C2_COLS + col];
-                        kF[4].x = KR1[ks * C2_COLS + col];
+                        for (int i = 0; i < 4; ++i) kF[i] = KR2[(ks * 4 + i) * COLS + col];
+                        kF[4].x = KR1[ks * COLS + col];
                     }
                 }
                 const unsigned vF = k_valid(r);
 #pragma unroll
                 for (int i = 0; i < QW; ++i) qw[i] = qw_next[i];
-                if constexpr (!WRING) {   // packed as the ingest role packs them
+                if constexpr (!F::wring) {   // packed as the ingest role packs them
 #pragma unroll
                     for (int i = 0; i < QW; ++i) qw[i] = 0;
 #pragma unroll
@@ -985,18 +851,18 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                 const int o0_ = o0_r, om_ = (o0_r == 0) ? 2 : o0_r - 1, op_ = (o0_r == 2) ? 0 : o0_r + 1;
                 constexpr int NB = (GP % 2 == 0) ? 2 : 1;
                 if constexpr (K64) {
-                    // f64 iterate: (O1 + x) - fwd(O1) and the division by the gain in f64, one rounding to f32 at the end; C2_NBO groups in
+                    // f64 iterate: (O1 + x) - fwd(O1) and the division by the gain in f64, one rounding to f32 at the end; NBO groups in
                     // lockstep (their ring reads, then interleaved chains), the divisions together at the end.  Lanes that are not
                     // active (border pixels) evaluate on whatever the rings hold there and keep x.
-                    constexpr int NBO = (G > 8 && C2_NBO == 2) ? 4 : ((G % C2_NBO == 0) ? C2_NBO : 2);   // (16 groups: 256 registers, four in lockstep)
+                    constexpr int NBO = F::nbo;
                     double o2v[G];
 #pragma unroll
                     for (int gb = 0; gb < G; gb += NBO) {
                         double v[NBO][9];
 #pragma unroll
                         for (int b = 0; b < NBO; ++b) {
-                            const double *ob = O1d + (size_t)(gb + b) * 3 * C2_COLS + col;
-                            const double *om = ob + om_ * C2_COLS, *o0 = ob + o0_ * C2_COLS, *op = ob + op_ * C2_COLS;
+                            const double *ob = O1d + (size_t)(gb + b) * 3 * COLS + col;
+                            const double *om = ob + om_ * COLS, *o0 = ob + o0_ * COLS, *op = ob + op_ * COLS;
                             v[b][0] = o0[0], v[b][1] = om[0], v[b][2] = op[0], v[b][3] = o0[-1], v[b][4] = o0[1], v[b][5] = om[-1],
                             v[b][6] = om[1], v[b][7] = op[-1], v[b][8] = op[1];
                         }
@@ -1032,8 +898,8 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             xc[b] = xnext[p0 + b];
-                            const f2 *ob = O12 + (p0 + b) * 3 * C2_COLS;
-                            om[b] = ob + om_ * C2_COLS, o0[b] = ob + o0_ * C2_COLS, op[b] = ob + op_ * C2_COLS;
+                            const f2 *ob = O12 + (p0 + b) * 3 * COLS;
+                            om[b] = ob + om_ * COLS, o0[b] = ob + o0_ * COLS, op[b] = ob + op_ * COLS;
                         }
                         f2 f[NB], oc[NB];
                         fwd_rows_batch<NB, true>(om, o0, op, col, kF, vF, f, oc);
@@ -1056,8 +922,8 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                             const f2 *om[NBG], *o0[NBG], *op[NBG];
 #pragma unroll
                             for (int b = 0; b < NBG; ++b) {
-                                const f2 *ob = O12 + (p0 + b) * 3 * C2_COLS;
-                                om[b] = ob + om_ * C2_COLS, o0[b] = ob + o0_ * C2_COLS, op[b] = ob + op_ * C2_COLS;
+                                const f2 *ob = O12 + (p0 + b) * 3 * COLS;
+                                om[b] = ob + om_ * COLS, o0[b] = ob + o0_ * COLS, op[b] = ob + op_ * COLS;
                             }
                             f2 f[NBG], oc[NBG];
                             if (all)
@@ -1087,33 +953,117 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                 const bool unsat = ((qw[(G - 1) / 4] >> (8 * ((G - 1) & 3))) & DQ_SATURATED) == 0;
                 if (!(dbg & 4))
                     fit_full_pk_a<G, rip_full_valid<G, START>()>(dpair, fc0, v0, kf->a.dense, e_gain, e_read, unsat && act, kf->guard, fs);
-                if (BAR >= 1) part_fb(kf);
-                if (BAR >= 2) part_flags(kf);
-                if (BAR >= 3) part_finish(kf);
             }
             CH_T(2)
             C2_SYNC();
             CH_T(3)
             const RIP_K C2KernArgs *kg = c2_args(kargs);  // S2 copy
-            // ---- S2: the rest of pixel (r, c) (C2_BAR); at its end the per-pixel words of row r + 1 from the rings
+            // ---- S2: the rest of pixel (r, c); at its end the per-pixel words of row r + 1 from the rings
             CH_T(4)
             C2_DRAIN()
             CH_T(5)
+            // The tail of pixel (r, c), three steps in order.  (They stay lambdas: written out in place, the same code is given
+            // another register assignment.)
+            float s = 0.0f, er = 0.0f, ep = 0.0f;
+            uint32_t jmask = 0, pdq = 0;
+            // second half of the fit: exact pass where needed, jump mask; then the saturated refits
+            auto part_fb = [&]() {
+                if (kg->a.cube_out) {
+#pragma unroll
+                    for (int g = 0; g < G; ++g) kg->a.cube_out[(unsigned)g * npix + pe] = d[g];
+                }
+                uint32_t qor = 0;
+#pragma unroll
+                for (int i = 0; i < QW; ++i) qor |= qw[i];
+                const bool anysat = (qor & 0x02020202u) != 0u;
+                const bool unsat = ((qw[(G - 1) / 4] >> (8 * ((G - 1) & 3))) & DQ_SATURATED) == 0;
+                if (dbg & 4) {
+                    s = d[0], er = e_read, ep = e_gain;
+                } else {
+                    fit_full_pk_b<G>(dpair, kg->h, fc0, kg->a.dense, kg->kvals + v0.k_ofs, kg->diffs + v0.diff_ofs, unsat && act,
+                                     fs, jmask);
+                    s = fs.s, er = fs.er, ep = fs.ep;
+                    if (__any(anysat)) {
+                        uint32_t qe[G];
+#pragma unroll
+                        for (int g = 0; g < G; ++g) qe[g] = (qw[g / 4] >> (8 * (g & 3))) & 0xffu;
+                        trunc_layers<G, G - 1>(d, qe, kg->h, kg->vars, kg->kvals, kg->diffs, e_gain, e_read, act, kg->guard, s, er, ep,
+                                               jmask);
+                    }
+                }
+            };
+            // T: flag propagation (fitting.py:339-353) and the stores of the group flags
+            auto part_flags = [&]() {
+                if (dbg & 8) return;
+                uint8_t *gq = (kg->a.gdq_out && !(dbg & 512)) ? kg->a.gdq_out + pe_row : nullptr;
+                pdq = propagate_flags_packed<G>(qw, jmask, start, e_pdq | lin_dq, gq, npix, c2_opaque(cc1));
+            };
+            // T: finish and the stores of the four planes
+            auto part_finish = [&]() {
+                if (dbg & 8) return;
+                if (kg->a.finish) {
+                    // gen_cal_image.py:458-475, 213-229, 607-629.  One wave vote selects the straight-line form built
+                    // from the short exact operations (rip_rcp_mid, rip_sqrt_mid, sqrt(x*x) = x: tools/gpu_checks/
+                    // fpcheck.hip); every intermediate then lies in their validated range 2^-100 .. 2^100 or is +0.
+                    const float sd = (act && kg->a.dark_rate) ? s - e_dark : s;
+                    const bool lean = kg->a.flat && __all(act && rip_mid36(sd) && (er == 0.0f || rip_mid36(er)) &&
+                                                          (ep == 0.0f || rip_mid36(ep)) && e_flat > 0.0f && rip_mid36(e_flat));
+                    if (lean) {
+                        const float err = hypot_f32(er, ep);
+                        const float ep2 = ep;  // sqrt(ep * ep)
+                        const float e2 = err * err;
+                        const float p2 = ep2 * ep2;
+                        const float er2 = rip_sqrt_mid(clip_lo<float>(e2 - p2, 0.0f));
+                        const float rflat = rip_rcp_mid(e_flat);
+                        s = div_rcp(sd, e_flat, rflat);
+                        er = div_rcp(er2, e_flat, rflat);
+                        ep = div_rcp(ep2, e_flat, rflat);
+                    } else {
+                        float err = hypot_f32(er, ep);
+                        float vp = ep * ep;
+                        if (!act) {
+                            s = 0.0f;
+                            err = 0.0f;
+                            vp = 0.0f;
+                        }
+                        if (act && kg->a.dark_rate) s = s - e_dark;
+                        float ep2 = sqrtf(vp);
+                        const float e2 = err * err;
+                        const float p2 = ep2 * ep2;
+                        float er2 = sqrtf(clip_lo<float>(e2 - p2, 0.0f));
+                        if (kg->a.flat) {
+                            s = s / e_flat;
+                            er2 = er2 / e_flat;
+                            ep2 = ep2 / e_flat;
+                        }
+                        er = er2;
+                        ep = ep2;
+                    }
+                }
+                const unsigned w4 = c2_opaque(cc4);
+                // (dbg & 512: timing experiment without the plane stores; the test keeps the four values live)
+                if (!(dbg & 512) || (s + er + ep == 12345.678f && pdq == 0xdeadbeefu)) {
+                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kg->a.slope) + t_row4 + w4) = s;
+                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kg->a.err_read) + t_row4 + w4) = er;
+                    *reinterpret_cast<float *>(reinterpret_cast<char *>(kg->a.err_poisson) + t_row4 + w4) = ep;
+                    *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(kg->a.pdq_out) + t_row4 + w4) = pdq;
+                }
+            };
             if (emit) {
-                if (BAR < 1) part_fb(kg);
-                if (BAR < 2) part_flags(kg);
-                if (BAR < 3) part_finish(kg);
+                part_fb();
+                part_flags();
+                part_finish();
             }
             // x of (r + 1, own column) for the next step's O2: its ring slot is overwritten in S1 of that step (row r + 4)
             {
                 const int sn = (o0_r == 2) ? 0 : o0_r + 1;
 #pragma unroll
-                for (int p0 = 0; p0 < GP; ++p0) xnext[p0] = X2[(p0 * XR + sn) * C2_COLS + col];
-                dq_next = DQ[sn * C2_COLS + col];
-                if constexpr (WRING) {
+                for (int p0 = 0; p0 < GP; ++p0) xnext[p0] = X2[(p0 * XR + sn) * COLS + col];
+                dq_next = DQ[sn * COLS + col];
+                if constexpr (F::wring) {
 #pragma unroll
-                    for (int i = 0; i < QW; ++i) qw_next[i] = QS[(sn * QW + i) * C2_COLS + col];
-                    gain_next = GN[sn * C2_COLS + col];
+                    for (int i = 0; i < QW; ++i) qw_next[i] = QS[(sn * QW + i) * COLS + col];
+                    gain_next = GN[sn * COLS + col];
                 } else {
                     // the fit role's own loads of row r + 1 (second read of lines its ingest role fetched three steps earlier):
                     // packed as the ingest role packs them; rows / columns outside the frame are never emitted
@@ -1128,21 +1078,15 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
                     gain_next = c2_ld_f32(c2_rsrc(kg->a.planes), cc4, (unsigned)(NP + 4) * pl4 + yl * row4);
                 }
             }
-#if C2_KFIT_EARLY == 2   // (row r + 2: the lines the ingest role fetched half a step ago)
-            if constexpr (!KRING) {
-                if constexpr (K64)
-                    (void)load_kd(kg->a.kern, r + 2, true, kn2_d, C2Int<KRN>{});
-                else
-                    (void)load_k(kg->a.kern, r + 2, true, kn2);
-            }
-#elif C2_KFIT_EARLY
-            if constexpr (!KRING) {
+            // (two steps ahead instead -- half a step after the ingest role's read of the same lines: fabric traffic 1.44 -> 1.19 x
+            // (f64), 1.50 -> 1.39 x (16 groups), 1.38 -> 1.27 x (both), and the kernels 3 % / 0 % / 10 % SLOWER: nine to eighteen more
+            // live registers; not bound by bytes)
+            if constexpr (KFIT) {
                 if constexpr (K64)
                     (void)load_kd(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn_d, C2Int<KRN>{});
                 else
                     (void)load_k(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn);
             }
-#endif
             CH_T(6)
             C2_SYNC();
             CH_T(7)
@@ -1150,21 +1094,15 @@ __global__ __launch_bounds__(2 * c2_cols(sizeof(KT) == 8, NARROW), c2_wps(G, siz
     }
 #ifdef CH_STAMP
     if ((tid & 63) == 0 && a.dbg_buf) {
-        unsigned long long *o = a.dbg_buf + ((size_t)blockIdx.x * (C2_THREADS / 64) + (tid >> 6)) * 9;
+        unsigned long long *o = a.dbg_buf + ((size_t)blockIdx.x * (F::threads / 64) + (tid >> 6)) * 9;
         for (int i = 0; i < 9; ++i) o[i] += st_[i];
     }
 #endif
 }
 
-static inline size_t chain2_lds_bytes(int G, size_t ksize = 4, int cols = C2_COLS_DEF, int krn = 9, bool wring = true) {
-    // x ring (3 rows) + O1 ring (3 rows) + flag word (+ packed groupdq / gain) rings (3 rows) + channel lines + K ring (2 rows)
-    return (size_t)(G / 2) * cols * 8 * 3 + (size_t)G * cols * ksize * 3 + (size_t)cols * 4 * 3 * (wring ? 2 + (G + 3) / 4 : 1) +
-           (size_t)(cols / RIP_CW + 1) * G * 2 * 8 + (size_t)2 * krn * cols * ksize;
-}
-
 // Launch geometry on `slots` co-resident workgroups, `reserve` of them left free where that costs nothing (the pre-pass of the NEXT
 // ramp runs in them beside this kernel): every strip gets the same number of row ranges -- except a last strip of at most 64 live
-// columns (nx = 4096 in the 256-column form: 16 strips of 252 + 64), which is covered in QUAD mode: nq workgroups whose four wave
+// columns (nx = 4096 in the 256-column form: 16 strips of 252 + 64), which is covered in QUAD mode: nq workgroups whose wc wave
 // columns take a row range each.  4096 x 4096: 16 x 31 ranges of 133 rows + 8 quad workgroups (32 ranges of 128 rows) = 504 workgroups
 // of 139 steps; before (17 x 30 ranges of 137 rows): 510 of 143.  Returns the grid size.
 static inline long chain2_geometry(ChainArgs &a, int nstrips, int live_last, int slots, int reserve, int wc = 4, bool quad_ok = true) {
@@ -1196,28 +1134,27 @@ static inline long chain2_geometry(ChainArgs &a, int nstrips, int live_last, int
     return (long)nr_u * nstrips;
 }
 
-template <int NP, int G, int START, typename KT = float, int NARROW = 0>
+template <int NP, int G, int START, typename KT>
 static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
-    constexpr int COLS = c2_cols(sizeof(KT) == 8, NARROW);
-    constexpr int KRN = !NARROW ? 9 : ((NARROW == 1 && sizeof(KT) == 8) ? c2_krn(G) : 0);
-    const size_t lds = chain2_lds_bytes(G, sizeof(KT), COLS, KRN, NARROW < 2);
+    using F = C2Form<G, sizeof(KT) == 8>;
+    const size_t lds = F::lds_bytes;
     const int ncu = ctx->ncu;
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu < 1) per_cu = 1;
-    // 4 waves/SIMD at <= 128 VGPRs (2 at 256 for G = 16 / f64; 3 at 168 in the narrow form)
-    const int max_wg = 4 * c2_wps(G, sizeof(KT) == 8, NARROW) / (C2_THREADS / 64);
+    // workgroups per CU: as many as the LDS holds, at most as many as the form's waves per SIMD allow
+    const int max_wg = 4 * F::wps / (F::threads / 64);
     if (per_cu > max_wg) per_cu = max_wg;
     if (a.nb < 2) return 1;   // (the frame-edge lanes of the first / last strip emit without neighbours: border pixels)
     ChainArgs ag = a;
-    const long grid = chain2_geometry(ag, C2_NSTRIPS(a.nx), a.nx - (C2_NSTRIPS(a.nx) - 1) * C2_OUTW, ncu * per_cu,
-                                      NARROW ? 0 : ctx->chain_reserve, COLS / 64, ctx->chain_quad);
+    const long grid = chain2_geometry(ag, F::nstrips(a.nx), a.nx - (F::nstrips(a.nx) - 1) * F::outw, ncu * per_cu,
+                                      F::narrow ? 0 : ctx->chain_reserve, F::cols / 64, ctx->chain_quad);
     static bool lds_set[64] = {};   // per device, once per instantiation (contexts are used from one thread each)
     if (lds > 48 * 1024 && !lds_set[ctx->device & 63]) {
-        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT, NARROW>),
+        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set[ctx->device & 63] = true;
     }
-    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT, NARROW>), dim3((unsigned)grid), dim3(C2_THREADS), lds, ctx->stream, ag,
+    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT>), dim3((unsigned)grid), dim3(F::threads), lds, ctx->stream, ag,
                        reinterpret_cast<const RipPlanHeader *>(plan->dev), plan->d_variants, plan->d_k, plan->d_diffs,
                        ctx->guard_band);
     RIP_HIP(ctx, hipGetLastError());
@@ -1225,9 +1162,25 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
 }
 
 // returns the launch status, or 1 when the plan is not one the specialised kernel was compiled for
-template <int NP, int G, typename KT = float, int NARROW = 0>
+template <int NP, int G, typename KT>
 static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
-    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return launch_chain2_s<NP, G, 0, KT, NARROW>(ctx, plan, a);
-    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>()) return launch_chain2_s<NP, G, 1, KT, NARROW>(ctx, plan, a);
+    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return launch_chain2_s<NP, G, 0, KT>(ctx, plan, a);
+    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>()) return launch_chain2_s<NP, G, 1, KT>(ctx, plan, a);
+    return 1;
+}
+
+// The fused kernel for NP Legendre planes and ipc4d coefficients of type KT, every group count it has a form for; chain.hip calls
+// it for the configurations it lists, chain_np*.hip instantiate it.  Returns the launch status, or 1 when no instantiation fits
+// (the caller then takes the stage kernels).
+template <int NP, typename KT>
+int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
+    switch (a.ngrp) {
+        case 6:
+            return launch_chain2<NP, 6, KT>(ctx, plan, a);
+        case 8:
+            return launch_chain2<NP, 8, KT>(ctx, plan, a);
+        case 16:
+            return launch_chain2<NP, 16, KT>(ctx, plan, a);
+    }
     return 1;
 }

@@ -278,6 +278,7 @@ struct ChainArgs {
     int geo_nr, geo_rows, geo_nq, geo_rows_q;
 };
 bool rip_chain_supported(const rip_ctx *ctx, int nplanes, int G, int k_dtype, int gain_dtype);
+bool rip_chain_fills_lds(int G, int k_dtype);   // the pre-pass of the next ramp cannot run beside the fused kernel
 int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype);
 
 // ipc.hip
