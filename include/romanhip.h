@@ -226,7 +226,8 @@ int rip_calibrate_batch_completed(rip_ctx *ctx);
 /* ---- stage-level entry points (host arrays; for function-level drop-in and parity tests) ----- */
 
 /* reference_subtraction.ref_subtraction_row(image, use_ref_channel=True, slope) followed by
-   ref_subtraction_channel(image, use_ref_channel=True) on one (ny, nx+128) f32 image, in place.
+   ref_subtraction_channel(image, use_ref_channel=True) on one (ny, nx+128) f32 image, in place: rip_stage_refpix_row
+   (nside = nx, RIP_ROW_SLOPE_F64) then rip_stage_refpix_channel (windows [0, 128) + 128 k, nx/128+1 of them).
    do_row / do_channel select the steps; medians out (optional): ref_med (ny) f32, ctr (1) f32,
    bottom_top (nx/128+1, 2) f32; lines in (optional, (nx/128+1,2) f64 (m,c)) override the fit. */
 int rip_stage_refpix_image(rip_ctx *ctx, float *image, int ny, int nx, double slope, int do_row, int do_channel,
@@ -258,7 +259,8 @@ int rip_stage_refpix_channel(rip_ctx *ctx, float *image, int ny, int width, int 
    f32, amp33 (ngrp,ny,128) u16, amp33_med (ny,128) f32 -> rowcorr (ngrp,ny) f64 = slope * f64(f32(row median - ctr)) and
    lines (ngrp,nx/128,2) f64 = (m, c) of the science channels.  form: 1 = the single-launch kernel (refpix_one.hip; frames up to
    4096 rows), 0 = the multi-launch kernels (refpix.hip), -1 = what rip_calibrate takes for a pre-pass in front of its own ramp
-   (option "prepass_form").  Both forms give identical bits.  status out (may be NULL): != 0 when a group barrier of the single-launch kernel timed out. */
+   (option "prepass_form").  Both forms give identical bits.  status out (may be NULL): != 0 when a group barrier of the single-launch kernel
+   timed out since the last status read; the read clears the word, so a timeout is reported once. */
 int rip_stage_refpix_tables(rip_ctx *ctx, const void *data, int data_dtype, const float *dark, const uint16_t *amp33,
                             const float *amp33_med, double slope, int ngrp, int ny, int nx, int form, double *rowcorr,
                             double *lines, int *status);

@@ -26,7 +26,7 @@ int rip_fail(rip_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
-void *rip_ws(rip_ctx *ctx, int slot, size_t bytes) {
+void *rip_ws(rip_ctx *ctx, RipWs slot, size_t bytes) {
     if (ctx->ws_bytes[slot] >= bytes && ctx->ws[slot]) return ctx->ws[slot];
     if (ctx->ws[slot]) {
         (void)hipStreamSynchronize(ctx->stream);
@@ -415,7 +415,7 @@ int rip_caldir_upload(rip_ctx *ctx, int slot, const rip_caldir_desc *d) {
     // ipc4d (3,3,nya,nxa) -> (9,ny,nx), biascorr (g,nya,nxa) -> (g,ny,nx): zero border, aligned rows
     if (d->ipc4d) {
         const size_t es = dsize(d->ipc_dtype);
-        void *tmp = rip_ws(ctx, 2, (size_t)9 * nya * nxa * es);
+        void *tmp = rip_ws(ctx, RIP_WS_STAGING, (size_t)9 * nya * nxa * es);
         hipError_t e = tmp ? hipMalloc(&c.ipc, 9 * npix * es) : hipErrorOutOfMemory;
         if (e != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "caldir upload: ipc4d allocation failed");
         RIP_HIP(ctx, hipMemcpyAsync(tmp, d->ipc4d, (size_t)9 * nya * nxa * es, hipMemcpyHostToDevice, ctx->stream));
@@ -425,7 +425,7 @@ int rip_caldir_upload(rip_ctx *ctx, int slot, const rip_caldir_desc *d) {
     if (d->biascorr) {
         c.ngrp_bias = d->ngrp_bias;
         const size_t nb_in = (size_t)d->ngrp_bias * nya * nxa * 4;
-        void *tmp = rip_ws(ctx, 2, nb_in);
+        void *tmp = rip_ws(ctx, RIP_WS_STAGING, nb_in);
         hipError_t e = tmp ? hipMalloc((void **)&c.bias, (size_t)d->ngrp_bias * npix * 4) : hipErrorOutOfMemory;
         if (e != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "caldir upload: biascorr allocation failed");
         RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // tmp may still feed the ipc embed
@@ -809,11 +809,11 @@ struct Calibration {
     // the chain writes it to)
     int stage_host() {
         if (!host) return RIP_OK;
-        char *w = (char *)rip_ws(ctx, 2, rip_host_ramp_bytes(*in, ny, nx));
+        char *w = (char *)rip_ws(ctx, RIP_WS_STAGING, rip_host_ramp_bytes(*in, ny, nx));
         if (!w) return RIP_ENOMEM;
         if (const int rc = rip_upload_host_ramp(ctx, *in, ny, nx, w, ctx->stream, &d)) return rc;
         RIP_HIP(ctx, hipGetLastError());
-        w = (char *)rip_ws(ctx, 7, rip_result_bytes(G, npix, out->groupdq != nullptr));
+        w = (char *)rip_ws(ctx, RIP_WS_RESULTS, rip_result_bytes(G, npix, out->groupdq != nullptr));
         if (!w) return RIP_ENOMEM;
         o = rip_result_planes(w, *out, npix);
         return RIP_OK;
@@ -829,7 +829,7 @@ struct Calibration {
         if (!host && in->ready_event) RIP_HIP(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)in->ready_event, 0));
         tab_bytes = ((size_t)2 * G * ny * 8 + (size_t)G * nch * 16 + 255) / 256 * 256;
         ws3 = (do_ref || (do_fit && (stages & RIP_STAGE_FLAT) && c.has_flat && d.area_factor))
-                  ? (char *)rip_ws(ctx, 3, 2 * tab_bytes + npix * 4 + 512)
+                  ? (char *)rip_ws(ctx, RIP_WS_TABLES, 2 * tab_bytes + npix * 4 + 512)
                   : nullptr;
         par = ctx->parity;
         // (by situation: where the fused kernel fills the LDS the pre-pass of the next ramp finds no room beside it, runs when it
@@ -874,7 +874,7 @@ struct Calibration {
         }
         mark(ctx, pre);
         int rc;
-        if ((rc = pre_order()) || (rc = rip_launch_refpix_prepass(ctx, ra))) return rc;
+        if ((rc = pre_order()) || (rc = rip_launch_refpix_prepass(ctx, ra, rip_refpix_form(ctx->prepass_form, ra)))) return rc;
         if (do_sat && (rc = sat_pass())) return rc;  // same stream as the pre-pass: overlaps the previous ramp's main kernel
         if ((rc = pre_done())) return rc;
         mark(ctx, pre);
@@ -889,7 +889,7 @@ struct Calibration {
     // buffered by call parity like the reference-pixel tables because the pass may run ahead on the second stream
     int sat_pass() {
         const size_t b_gdq = al256((size_t)G * npix), one = b_gdq + al256(npix * 4);
-        char *w = (char *)rip_ws(ctx, 8, 2 * one);
+        char *w = (char *)rip_ws(ctx, RIP_WS_SATFLAG, 2 * one);
         if (!w) return RIP_ENOMEM;
         uint8_t *g2 = (uint8_t *)(w + (size_t)par * one);
         uint32_t *p2 = (uint32_t *)(w + (size_t)par * one + b_gdq);
@@ -961,7 +961,7 @@ struct Calibration {
         ca.gdq_out = o.groupdq;
         float *cube = nullptr;
         if (out->cube) {
-            cube = host ? (float *)rip_ws(ctx, 1, (size_t)G * npix * 4) : out->cube;
+            cube = host ? (float *)rip_ws(ctx, RIP_WS_CUBE_B, (size_t)G * npix * 4) : out->cube;
             if (!cube) return RIP_ENOMEM;
             ca.cube_out = cube;
         }
@@ -990,7 +990,7 @@ struct Calibration {
         pdq_mid = d.pixeldq;
         // ---- cube stage: refpix apply + bias + linearity (or a plain conversion to f32)
         if (do_ref || do_bias || do_lin || in->data_dtype != RIP_F32) {
-            float *cubeA = (float *)rip_ws(ctx, 0, (size_t)G * npix * 4 + npix * 4);
+            float *cubeA = (float *)rip_ws(ctx, RIP_WS_CUBE_A, (size_t)G * npix * 4 + npix * 4);
             if (!cubeA) return RIP_ENOMEM;
             uint32_t *pdq_ws = (uint32_t *)(cubeA + (size_t)G * npix);
             LinArgs la;
@@ -1030,7 +1030,7 @@ struct Calibration {
         mark(ctx, ctx->stream);
         // ---- IPC
         if (do_ipc) {
-            float *cubeB = (float *)rip_ws(ctx, 1, (size_t)G * npix * 4);
+            float *cubeB = (float *)rip_ws(ctx, RIP_WS_CUBE_B, (size_t)G * npix * 4);
             if (!cubeB) return RIP_ENOMEM;
             IpcArgs ia{cur, cubeB, c.ipc, c.gain, c.ipc_dtype, c.gain_dtype, ny, nx, c.nb, G};
             if ((rc = rip_launch_ipc_cube(ctx, ia))) return rc;
@@ -1123,6 +1123,7 @@ int rip_calibrate(rip_ctx *ctx, int slot, int plan_id, unsigned stages, const ri
 int rip_stage_refpix_image(rip_ctx *ctx, float *image, int ny, int nx, double slope, int do_row, int do_channel,
                            const double *lines, float *ref_med, float *ctr, float *bottom_top) {
     RIP_HIP(ctx, hipSetDevice(ctx->device));
+    if (nx % RIP_CW) return rip_fail(ctx, RIP_EINVAL, "refpix: nx=%d is not a multiple of 128", nx);
     const int w = nx + RIP_CW, nch = w / RIP_CW;
     const size_t n = (size_t)ny * w;
     DevBuf img, ln, rm, ct, bt;
@@ -1130,8 +1131,12 @@ int rip_stage_refpix_image(rip_ctx *ctx, float *image, int ny, int nx, double sl
     if ((rc = img.upload(ctx, image, n * 4))) return rc;
     if (lines && (rc = ln.upload(ctx, lines, (size_t)nch * 16))) return rc;
     if ((rc = rm.alloc(ctx, (size_t)ny * 4)) || (rc = ct.alloc(ctx, 4)) || (rc = bt.alloc(ctx, (size_t)nch * 8))) return rc;
-    if ((rc = rip_refpix_image(ctx, img.as<float>(), ny, nx, slope, do_row, do_channel, lines ? ln.as<double>() : nullptr,
-                               rm.as<float>(), ct.as<float>(), bt.as<float>())))
+    // the row step on the reference output (nside = nx, f64 slope), then the channel step on the nch 128-column channels
+    if (do_row && (rc = rip_refpix_row_general(ctx, img.as<float>(), ny, w, nx, 1, RIP_ROW_SLOPE_F64, slope, rm.as<float>(), nullptr,
+                                               ct.as<float>())))
+        return rc;
+    if (do_channel && (rc = rip_refpix_channel_general(ctx, img.as<float>(), ny, w, 0, RIP_CW, nch, lines ? ln.as<double>() : nullptr,
+                                                       bt.as<float>())))
         return rc;
     RIP_HIP(ctx, hipMemcpyAsync(image, img.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (ref_med && do_row) RIP_HIP(ctx, hipMemcpyAsync(ref_med, rm.p, (size_t)ny * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1199,15 +1204,9 @@ int rip_stage_refpix_tables(rip_ctx *ctx, const void *data, int data_dtype, cons
     RefpixArgs ra{d_data.p, data_dtype, d_dark.as<float>(), d_a33.as<uint16_t>(), d_med.as<float>(), slope, nullptr,
                   d_rc.as<double>(), d_rt.as<double>(), d_ln.as<double>(), ny, nx, ngrp};
     if (form < -1 || form > 1) return rip_fail(ctx, RIP_EINVAL, "refpix tables: form %d", form);
-    const int keep = ctx->prepass_form;
-    if (form >= 0) ctx->prepass_form = form;
-    if (form >= 1 && !rip_refpix_one_supported(ra)) {
-        ctx->prepass_form = keep;
+    if (form == 1 && !rip_refpix_one_supported(ra))
         return rip_fail(ctx, RIP_EINVAL, "refpix tables: the single-launch kernel does not cover a %d x %d frame of %d groups", ny, nx, ngrp);
-    }
-    rc = rip_launch_refpix_prepass(ctx, ra);
-    ctx->prepass_form = keep;
-    if (rc) return rc;
+    if ((rc = rip_launch_refpix_prepass(ctx, ra, rip_refpix_form(form < 0 ? ctx->prepass_form : form, ra)))) return rc;
     RIP_HIP(ctx, hipMemcpyAsync(rowcorr, d_rc.p, (size_t)ngrp * ny * 8, hipMemcpyDeviceToHost, ctx->stream));
     RIP_HIP(ctx, hipMemcpyAsync(lines, d_ln.p, (size_t)ngrp * nch * 16, hipMemcpyDeviceToHost, ctx->stream));
     RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -251,8 +251,8 @@ static int ipc_image_typed(rip_ctx *ctx, int reverse, int order, const void *img
                            const void *gain, void *out) {
     // XT = dtype of gain*image (image alone without gain); T = promote(XT, kernel) = output dtype
     const size_t n = (size_t)ny * nx;
-    XT *xbuf = (XT *)rip_ws(ctx, 5, n * sizeof(XT));
-    T *abuf = (T *)rip_ws(ctx, 6, n * sizeof(T));
+    XT *xbuf = (XT *)rip_ws(ctx, RIP_WS_IPC_X, n * sizeof(XT));
+    T *abuf = (T *)rip_ws(ctx, RIP_WS_IPC_A, n * sizeof(T));
     T *bbuf = (T *)out;
     if (!xbuf || !abuf) return RIP_ENOMEM;
     const unsigned nb1 = (unsigned)((n + 255) / 256);

@@ -216,7 +216,7 @@ int rip_launch_satflag(rip_ctx *ctx, const void *data, int data_dtype, const flo
         return rip_fail(ctx, RIP_EINVAL, "saturation flagging: bad group / backup / skip arguments");
     if (nx % 4) return rip_fail(ctx, RIP_EINVAL, "saturation flagging: nx=%d is not a multiple of 4", nx);
     const size_t npix = (size_t)ny * nx;
-    uint64_t *ex = (uint64_t *)rip_ws(ctx, 9, npix * 8);
+    uint64_t *ex = (uint64_t *)rip_ws(ctx, RIP_WS_EXCEED, npix * 8);
     if (!ex) return RIP_ENOMEM;
     const dim3 g1((unsigned)((npix / 4 + 255) / 256)), block(256);
     SatDilution dil;

@@ -352,7 +352,7 @@ extern "C" int rip_synth_frames_ahead(rip_ctx *ctx, int rows, int width, int nfr
     if (!ctx->stream2) return RIP_OK;   // no second stream: rip_synth_fill makes the frames itself, in stream order
     if (rows < 1 || width < 1 || nframes < 1) return rip_fail(ctx, RIP_EINVAL, "synth_frames_ahead: bad geometry");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    float *made = (float *)rip_ws(ctx, 12, (size_t)nframes * rows * width * sizeof(float));
+    float *made = (float *)rip_ws(ctx, RIP_WS_FRAMES, (size_t)nframes * rows * width * sizeof(float));
     if (!made) return RIP_ENOMEM;
     if (!ctx->ev_frames) RIP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_frames, hipEventDisableTiming));
     // behind what the main stream holds at the time of the call: the previous exposure's fill kernels (they read the frames this

@@ -16,34 +16,14 @@
 // All medians are exact selections (np.median: mean of the two middle elements in f32).
 // Arithmetic recipe: oracle/refpix.py.
 //
-// The line through (1.5, b), (ny-2.5, t) is m = (t-b)/(ny-4), c = b - 1.5 m in f64; the reference gets
-// it from LAPACK gelsd, which agrees to ~1e-13 relative but not bit for bit -- the caller may pass
-// LAPACK's (m, c) instead (`lines_override`).  See DESIGN.md "channel line fit".
+// Keys, the selection levels' scan step, the median of a selected pair, the row correction and the channel line come from
+// refpix_shared.h (shared with refpix_one.hip).
 #include "rip_common.h"
-#include "refpix_keys.h"
-
-// np.median of vals[0..n) held in LDS, by rank counting; result broadcast through slot[0..1].
-// All threads of the block must call it.  Ties are ordered by index, so ranks are a permutation.
-__device__ float block_median(const float *vals, int n, float *slot) {
-    const int k_hi = n / 2, k_lo = (n & 1) ? n / 2 : n / 2 - 1;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const float v = vals[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const float w = vals[j];
-            rank += (w < v || (w == v && j < i)) ? 1 : 0;
-        }
-        if (rank == k_lo) slot[0] = v;
-        if (rank == k_hi) slot[1] = v;
-    }
-    __syncthreads();
-    const float m = (slot[0] + slot[1]) * 0.5f;
-    __syncthreads();
-    return m;
-}
+#include "refpix_shared.h"
 
 // np.median of vals[0..n) in LDS by an in-place bitonic sort; the buffer must hold npow2 >= n floats
-// (entries n.. are overwritten with +inf).  All threads of the block must call it.
+// (entries n.. are overwritten with +inf).  All threads of the block must call it.  The median of the image drop-ins; the
+// pre-pass's rowcorr_kernel takes block_median_select, whose key order can pick the other of two tied -0 / +0.
 __device__ float block_median_sorted(float *vals, int n, int npow2) {
     for (int i = n + threadIdx.x; i < npow2; i += blockDim.x) vals[i] = INFINITY;
     __syncthreads();
@@ -108,7 +88,6 @@ struct SelState {
     uint32_t rank[2];
 };
 
-
 __global__ __launch_bounds__(256) void sel_hist_kernel(const uint16_t *__restrict__ amp33, const float *__restrict__ med,
                                                        const SelState *__restrict__ st, uint32_t *__restrict__ ghist,
                                                        int ny, int level, int chunk) {
@@ -139,33 +118,19 @@ __global__ __launch_bounds__(256) void sel_hist_kernel(const uint16_t *__restric
 }
 
 __global__ __launch_bounds__(256) void sel_scan_kernel(SelState *__restrict__ st, uint32_t *__restrict__ ghist, int level, uint32_t n) {
-    // bin holding the wanted rank: 8 bins per thread, wave prefix sums over the 256 partial sums, the owner walks its 8 bins
+    // bin holding the wanted rank: 8 bins per thread
     __shared__ uint32_t part[4];
     const int g = blockIdx.x, t = blockIdx.y;
     uint32_t *h = ghist + ((size_t)g * 2 + t) * SEL_BINS;
     const int per = SEL_BINS / 256;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     // level 0 starts the selection: the two middle elements of n values, empty prefix (no separate initialisation launch)
     const uint32_t rank = level ? st[g].rank[t] : (t ? n / 2 : n / 2 - 1);
     const uint32_t before = level ? st[g].prefix[t] : 0u;
-    uint32_t own = 0;
-    for (int k = 0; k < per; ++k) own += h[tid * per + k];
-    uint32_t incl = own;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) part[w] = incl;
-    __syncthreads();
-    for (int k = 0; k < w; ++k) incl += part[k];
-    const uint32_t excl = incl - own;
-    if ((excl <= rank && rank < incl) || (tid == 255 && rank >= incl)) {
-        uint32_t cum = excl;
-        int b = tid * per;
-        while (b < tid * per + per - 1 && cum + h[b] <= rank) cum += h[b++];
-        st[g].prefix[t] = before | ((uint32_t)b << sel_shift(level));
-        st[g].rank[t] = rank - cum;
+    uint32_t bin, left;
+    if (sel_find_bin<256, per>([&](int k) { return h[tid * per + k]; }, rank, tid, true, part, bin, left)) {
+        st[g].prefix[t] = before | (bin << sel_shift(level));
+        st[g].rank[t] = left;
     }
     __syncthreads();
     for (int k = 0; k < per; ++k) h[tid * per + k] = 0;  // ready for the next level
@@ -178,7 +143,7 @@ __global__ __launch_bounds__(256) void sel_scan_kernel(SelState *__restrict__ st
 __device__ float block_median_select(const float *vals, int n, uint32_t (*h)[SEL_BINS], uint32_t *tmp) {
     uint32_t prefix[2] = {0u, 0u};
     uint32_t rank[2] = {(uint32_t)((n & 1) ? n / 2 : n / 2 - 1), (uint32_t)(n / 2)};
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     for (int lv = 0; lv < 3; ++lv) {
         for (int i = t; i < 2 * SEL_BINS; i += blockDim.x) (&h[0][0])[i] = 0;
         __syncthreads();
@@ -192,48 +157,26 @@ __device__ float block_median_select(const float *vals, int n, uint32_t (*h)[SEL
         }
         __syncthreads();
         for (int q = 0; q < 2; ++q) {
-            // parallel scan of the 2048 bins: 8 per thread for the first 256 threads, wave prefix sums, then the owner walks its 8
+            // the 2048 bins: 8 per thread for the first 256 threads; the owner writes {bin, rank inside it} to tmp[4..5]
             const int per = SEL_BINS / 256;
-            uint32_t own = 0, incl = 0;
-            if (t < 256) {
-                for (int k = 0; k < per; ++k) own += h[q][t * per + k];
-                incl = own;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t y = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += y;
-                }
-                if (lane == 63) tmp[w] = incl;
-            }
-            __syncthreads();
-            if (t < 256) {
-                for (int k = 0; k < w; ++k) incl += tmp[k];
-                const uint32_t excl = incl - own;
-                if ((excl <= rank[q] && rank[q] < incl) || (t == 255 && rank[q] >= incl)) {
-                    uint32_t cum = excl;
-                    int b = t * per;
-                    while (b < t * per + per - 1 && cum + h[q][b] <= rank[q]) cum += h[q][b++];
-                    tmp[4] = (uint32_t)b;
-                    tmp[5] = rank[q] - cum;
-                }
-            }
+            const uint32_t *own = h[q] + t * per;
+            sel_find_bin<256, per>([=](int k) { return own[k]; }, rank[q], t, t < 256, tmp, tmp[4], tmp[5]);
             __syncthreads();
             prefix[q] |= tmp[4] << shift;
             rank[q] = tmp[5];
             __syncthreads();
         }
     }
-    return (key2f(prefix[0]) + key2f(prefix[1])) * 0.5f;
+    return key_median(prefix[0], prefix[1]);
 }
 
 // ---- 3. per group: global median M, row medians, ctr, rowcorr ------------------------------------
 __global__ __launch_bounds__(1024) void rowcorr_kernel(const SelState *__restrict__ st, const float *__restrict__ lohi,
                                                        double slope, double *__restrict__ rowcorr,
-                                                       double *__restrict__ rowcorr_t, float *__restrict__ dbg_refmed,
-                                                       float *__restrict__ dbg_scal, int ny, int npow2) {
-    extern __shared__ float rm[];  // [npow2] sort buffer
+                                                       double *__restrict__ rowcorr_t, int ny) {
+    extern __shared__ float rm[];  // [ny] row medians
     const int g = blockIdx.x;
-    const float M = (key2f(st[g].prefix[0]) + key2f(st[g].prefix[1])) * 0.5f;  // np.median of the block
+    const float M = key_median(st[g].prefix[0], st[g].prefix[1]);  // np.median of the block
     auto refmed = [&](int r) {
         const float a = lohi[((size_t)g * ny + r) * 2] - M;
         const float b = lohi[((size_t)g * ny + r) * 2 + 1] - M;
@@ -245,14 +188,9 @@ __global__ __launch_bounds__(1024) void rowcorr_kernel(const SelState *__restric
     __syncthreads();
     const float ctr = block_median_select(rm, ny, hsel, tmp);
     for (int r = threadIdx.x; r < ny; r += blockDim.x) {
-        const float v = refmed(r);
-        rowcorr[(size_t)g * ny + r] = slope * (double)(v - ctr);
-        if (rowcorr_t) rowcorr_t[(size_t)r * gridDim.x + g] = slope * (double)(v - ctr);  // [row][group]: one scalar load per row
-        if (dbg_refmed) dbg_refmed[(size_t)g * ny + r] = v;
-    }
-    if (dbg_scal && threadIdx.x == 0) {
-        dbg_scal[g * 2] = M;
-        dbg_scal[g * 2 + 1] = ctr;
+        const double v = row_corr(slope, refmed(r), ctr);
+        rowcorr[(size_t)g * ny + r] = v;
+        if (rowcorr_t) rowcorr_t[(size_t)r * gridDim.x + g] = v;  // [row][group]: one scalar load per row
     }
 }
 
@@ -261,8 +199,7 @@ template <typename DT>
 __global__ __launch_bounds__(1024) void chan_kernel(const DT *__restrict__ data, const float *__restrict__ dark,
                                                     const double *__restrict__ rowcorr,
                                                     const double *__restrict__ lines_override,
-                                                    double *__restrict__ lines, float *__restrict__ dbg_bt, int ny,
-                                                    int nx) {
+                                                    double *__restrict__ lines, int ny, int nx) {
     __shared__ float v[1024];
     const int ch = blockIdx.x, g = blockIdx.y, nch = gridDim.x;
     const int e = threadIdx.x & 511, half = threadIdx.x >> 9;
@@ -289,45 +226,48 @@ __global__ __launch_bounds__(1024) void chan_kernel(const DT *__restrict__ data,
             __syncthreads();
         }
     if (threadIdx.x == 0) {
-        const float b = (v[255] + v[256]) * 0.5f;
-        const float t = (v[512 + 255] + v[512 + 256]) * 0.5f;
+        const size_t o = ((size_t)g * nch + ch) * 2;
         double m, c;
-        if (lines_override) {
-            m = lines_override[((size_t)g * nch + ch) * 2];
-            c = lines_override[((size_t)g * nch + ch) * 2 + 1];
-        } else {
-            m = ((double)t - (double)b) / (double)(ny - 4);
-            c = (double)b - 1.5 * m;
-        }
-        lines[((size_t)g * nch + ch) * 2] = m;
-        lines[((size_t)g * nch + ch) * 2 + 1] = c;
-        if (dbg_bt) {
-            dbg_bt[((size_t)g * nch + ch) * 2] = b;
-            dbg_bt[((size_t)g * nch + ch) * 2 + 1] = t;
-        }
+        chan_line((v[255] + v[256]) * 0.5f, (v[512 + 255] + v[512 + 256]) * 0.5f, ny, lines_override ? lines_override + o : nullptr,
+                  m, c);
+        lines[o] = m;
+        lines[o + 1] = c;
     }
 }
 
-int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a) {
+template <typename K>
+static int with_lds(rip_ctx *ctx, K kernel, size_t lds) {
+    if (lds > 48 * 1024)
+        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return RIP_OK;
+}
+
+// which pre-pass makes the tables: 1 the single launch of refpix_one.hip, 0 the launches below.  option (rip_ctx::prepass_form,
+// or the form a stage call asks for): -1 by situation -- the single launch in front of its own ramp, the small launches beside
+// the previous ramp's fused kernel (a.background) --, 1 the single launch wherever it covers the frame, 0 never
+int rip_refpix_form(int option, const RefpixArgs &a) {
+    return (option == 1 || (option < 0 && !a.background)) && rip_refpix_one_supported(a) ? 1 : 0;
+}
+
+int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a, int form) {
     if (a.nx % RIP_CW) return rip_fail(ctx, RIP_EINVAL, "refpix: nx=%d is not a multiple of 128", a.nx);
     if (a.ny < 8) return rip_fail(ctx, RIP_EINVAL, "refpix: ny=%d too small", a.ny);
     const int G = a.ngrp, ny = a.ny, nch = a.nx / RIP_CW;
     hipStream_t strm = a.stream ? a.stream : ctx->stream;   // (the overlapped pre-pass: the context's second stream)
-    if ((ctx->prepass_form == 1 || (ctx->prepass_form < 0 && !a.background)) && rip_refpix_one_supported(a))
-        return rip_launch_refpix_one(ctx, a);
+    if (form == 1) return rip_launch_refpix_one(ctx, a);
     if (a.amp33) {
         // scratch: lohi (G,ny,2) f32 | SelState[G]
         const size_t lohi_b = (size_t)G * ny * 2 * sizeof(float);
         const size_t st_b = ((size_t)G * sizeof(SelState) + 255) / 256 * 256;
-        char *ws = (char *)rip_ws(ctx, 4, lohi_b + st_b);
+        char *ws = (char *)rip_ws(ctx, RIP_WS_REFPIX, lohi_b + st_b);
         if (!ws) return RIP_ENOMEM;
         float *lohi = (float *)ws;
         SelState *st = (SelState *)(ws + lohi_b);
         // the selection histograms have a workspace slot of their own, of a fixed size: every level's scan leaves them zero, so
         // they are cleared only when the slot is first allocated (no initialisation launch per call)
         const size_t gh_b = (size_t)RIP_MAX_GROUPS * 2 * SEL_BINS * sizeof(uint32_t);
-        const void *had = ctx->ws[13];
-        uint32_t *ghist = (uint32_t *)rip_ws(ctx, 13, gh_b);
+        const void *had = ctx->ws[RIP_WS_SEL_HIST];
+        uint32_t *ghist = (uint32_t *)rip_ws(ctx, RIP_WS_SEL_HIST, gh_b);
         if (!ghist) return RIP_ENOMEM;
         if ((const void *)ghist != had) RIP_HIP(ctx, hipMemsetAsync(ghist, 0, gh_b, strm));
         const uint32_t n = (uint32_t)ny * RIP_CW;
@@ -340,14 +280,10 @@ int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a) {
                                ghist, ny, level, chunk);
             hipLaunchKernelGGL(sel_scan_kernel, dim3(G, 2), dim3(256), 0, strm, st, ghist, level, n);
         }
-        int npow2 = 1;
-        while (npow2 < ny) npow2 <<= 1;
-        const size_t lds = (size_t)npow2 * sizeof(float);
-        if (lds > 48 * 1024)
-            RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rowcorr_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(rowcorr_kernel, dim3(G), dim3(1024), lds, strm, st, lohi, a.slope, a.rowcorr,
-                           a.rowcorr_t, (float *)nullptr, (float *)nullptr, ny, npow2);
+        const size_t lds = (size_t)ny * sizeof(float);
+        int rc;
+        if ((rc = with_lds(ctx, rowcorr_kernel, lds))) return rc;
+        hipLaunchKernelGGL(rowcorr_kernel, dim3(G), dim3(1024), lds, strm, st, lohi, a.slope, a.rowcorr, a.rowcorr_t, ny);
     } else {
         // no reference output in the read file: the row step is the identity
         RIP_HIP(ctx, hipMemsetAsync(a.rowcorr, 0, (size_t)G * ny * sizeof(double), strm));
@@ -355,36 +291,51 @@ int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a) {
     }
     if (a.data_dtype == RIP_U16)
         hipLaunchKernelGGL(chan_kernel<uint16_t>, dim3(nch, G), dim3(1024), 0, strm, (const uint16_t *)a.data,
-                           a.dark_data, a.rowcorr, a.lines_override, a.lines, (float *)nullptr, ny, a.nx);
+                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx);
     else
         hipLaunchKernelGGL(chan_kernel<float>, dim3(nch, G), dim3(1024), 0, strm, (const float *)a.data,
-                           a.dark_data, a.rowcorr, a.lines_override, a.lines, (float *)nullptr, ny, a.nx);
+                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx);
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;
 }
 
 // ------------------------------------------------------------------ image-level drop-ins
-// ref_subtraction_row(image, use_ref_channel=True, slope) / ref_subtraction_channel(image,
-// use_ref_channel=True) on one (ny, nx+128) f32 image resident on the device.
+// reference_subtraction.py with ANY of its arguments, on one f32 image resident on the device (rip_stage_refpix_image, the
+// configuration of calibrateimage, is the two of them in a row):
+//   ref_subtraction_row(image, use_ref_channel=False, slope=None)      :77-125  row medians of the 4+4 border pixels or of
+//       the reference output, of the science pixels (for the np.polyfit of slope=None, done by the host mirror), update
+//       in the dtype numpy's promotion gives: f64 for a numpy f64 slope, f32 for a Python float / numpy f32 slope
+//   ref_subtraction_channel(image, channel_start, channel_end, use_ref_channel) :16-74  windows [start+128k, end+128k),
+//       one after the other as the reference's loop runs them (windows wider than 128 columns overlap)
 
-__global__ __launch_bounds__(RIP_CW) void img_rowmed_kernel(const float *__restrict__ image, float *__restrict__ ref_med,
-                                                            int nx) {
-    __shared__ float v[RIP_CW];
-    __shared__ float slot[2];
-    const int r = blockIdx.x;
-    v[threadIdx.x] = image[(size_t)r * (nx + RIP_CW) + nx + threadIdx.x];
+// median of the values of `nr` rows x (cols [c0, c0+n0) u [c1, c1+n1)) per block: block (b, k) starts at row row0 + b * rstep,
+// its columns are shifted by 128 k (window k); out[k * gridDim.x + b].  Dynamic LDS: npow2 floats.
+__global__ __launch_bounds__(1024) void img_window_median_kernel(const float *__restrict__ image, int w, int row0, int rstep,
+                                                                 int nr, int c0, int n0, int c1, int n1,
+                                                                 float *__restrict__ out, int npow2) {
+    extern __shared__ float mv[];
+    const int per = n0 + n1, n = nr * per;
+    const int rbase = row0 + (int)blockIdx.x * rstep, cs = (int)blockIdx.y * RIP_CW;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int rr = i / per, cc = i % per;
+        const int col = cs + (cc < n0 ? c0 + cc : c1 + (cc - n0));
+        mv[i] = image[(size_t)(rbase + rr) * w + col];
+    }
     __syncthreads();
-    const float m = block_median(v, RIP_CW, slot);
-    if (threadIdx.x == 0) ref_med[r] = m;
+    const float m = block_median_sorted(mv, n, npow2);
+    if (threadIdx.x == 0) out[blockIdx.y * gridDim.x + blockIdx.x] = m;
 }
 
-__global__ __launch_bounds__(1024) void img_ctr_kernel(const float *__restrict__ ref_med, double slope,
-                                                       double *__restrict__ rowcorr, float *__restrict__ ctr_out, int ny,
-                                                       int npow2) {
+// ctr = median of the row medians; rowcorr[r] = the row correction of ref_med[r], f64 or f32 form
+__global__ __launch_bounds__(1024) void img_ctr2_kernel(const float *__restrict__ ref_med, double slope, int f32_form,
+                                                        double *__restrict__ rowcorr, float *__restrict__ ctr_out, int ny,
+                                                        int npow2) {
     extern __shared__ float rm[];
     for (int r = threadIdx.x; r < ny; r += blockDim.x) rm[r] = ref_med[r];
     const float ctr = block_median_sorted(rm, ny, npow2);
-    for (int r = threadIdx.x; r < ny; r += blockDim.x) rowcorr[r] = slope * (double)(ref_med[r] - ctr);
+    const float s32 = (float)slope;
+    for (int r = threadIdx.x; r < ny; r += blockDim.x)
+        rowcorr[r] = f32_form ? row_corr_f32(s32, ref_med[r], ctr) : row_corr(slope, ref_med[r], ctr);
     if (threadIdx.x == 0 && ctr_out) *ctr_out = ctr;
 }
 
@@ -394,165 +345,33 @@ __global__ void img_rowapply_kernel(float *__restrict__ image, const double *__r
     image[i] = (float)((double)image[i] - rowcorr[i / w]);
 }
 
-__global__ __launch_bounds__(1024) void img_chan_kernel(const float *__restrict__ image,
-                                                        const double *__restrict__ lines_override,
-                                                        double *__restrict__ lines, float *__restrict__ bt_out, int ny,
-                                                        int w) {
-    __shared__ float v[1024];
-    __shared__ float lh[2][2];
-    const int ch = blockIdx.x;
-    const int e = threadIdx.x & 511, half = threadIdx.x >> 9;
-    const int row = (half ? ny - 4 : 0) + e / RIP_CW;
-    const float val = image[(size_t)row * w + (size_t)ch * RIP_CW + e % RIP_CW];
-    v[threadIdx.x] = val;
-    __syncthreads();
-    const float *mine = v + half * 512;
-    int rank = 0;
-    for (int j = 0; j < 512; ++j) {
-        const float q = mine[j];
-        rank += (q < val || (q == val && j < e)) ? 1 : 0;
-    }
-    if (rank == 255) lh[half][0] = val;
-    if (rank == 256) lh[half][1] = val;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float b = (lh[0][0] + lh[0][1]) * 0.5f;
-        const float t = (lh[1][0] + lh[1][1]) * 0.5f;
-        double m, c;
-        if (lines_override) {
-            m = lines_override[ch * 2];
-            c = lines_override[ch * 2 + 1];
-        } else {
-            m = ((double)t - (double)b) / (double)(ny - 4);
-            c = (double)b - 1.5 * m;
-        }
-        lines[ch * 2] = m;
-        lines[ch * 2 + 1] = c;
-        if (bt_out) {
-            bt_out[ch * 2] = b;
-            bt_out[ch * 2 + 1] = t;
-        }
-    }
-}
-
-__global__ void img_chanapply_kernel(float *__restrict__ image, const double *__restrict__ lines, int ny, int w) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)ny * w) return;
-    const int r = (int)(i / w), c = (int)(i % w);
-    const double *ln = lines + (size_t)(c / RIP_CW) * 2;
-    const double iel = ln[0] * (double)r + ln[1];
-    image[i] = (float)((double)image[i] - iel);
-}
-
-int rip_refpix_image(rip_ctx *ctx, float *d_image, int ny, int nx, double slope, int do_row, int do_channel,
-                     const double *d_lines, float *d_ref_med, float *d_ctr, float *d_bottom_top) {
-    if (nx % RIP_CW) return rip_fail(ctx, RIP_EINVAL, "refpix: nx=%d is not a multiple of 128", nx);
-    const int w = nx + RIP_CW, nch = w / RIP_CW;
-    const size_t n = (size_t)ny * w;
-    char *ws = (char *)rip_ws(ctx, 4, (size_t)ny * (sizeof(double) + sizeof(float)) + (size_t)nch * 2 * sizeof(double) + 256);
-    if (!ws) return RIP_ENOMEM;
-    double *rowcorr = (double *)ws;
-    double *lines = rowcorr + ny;
-    float *refmed = (float *)(lines + nch * 2);
-    if (do_row) {
-        hipLaunchKernelGGL(img_rowmed_kernel, dim3(ny), dim3(RIP_CW), 0, ctx->stream, d_image, refmed, nx);
-        int npow2 = 1;
-        while (npow2 < ny) npow2 <<= 1;
-        const size_t lds = (size_t)npow2 * sizeof(float);
-        if (lds > 48 * 1024)
-            RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(img_ctr_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(img_ctr_kernel, dim3(1), dim3(1024), lds, ctx->stream, refmed, slope, rowcorr, d_ctr, ny,
-                           npow2);
-        hipLaunchKernelGGL(img_rowapply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_image,
-                           rowcorr, ny, w);
-        if (d_ref_med)
-            RIP_HIP(ctx, hipMemcpyAsync(d_ref_med, refmed, (size_t)ny * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (do_channel) {
-        hipLaunchKernelGGL(img_chan_kernel, dim3(nch), dim3(1024), 0, ctx->stream, d_image, d_lines, lines, d_bottom_top,
-                           ny, w);
-        hipLaunchKernelGGL(img_chanapply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_image,
-                           lines, ny, w);
-    }
-    RIP_HIP(ctx, hipGetLastError());
-    return RIP_OK;
-}
-
-// ------------------------------------------------------------------ general forms of the image-level drop-ins
-// reference_subtraction.py with ANY of its arguments (the forms above are the configuration of calibrateimage):
-//   ref_subtraction_row(image, use_ref_channel=False, slope=None)      :77-125  row medians of the 4+4 border pixels or of
-//       the reference output, of the science pixels (for the np.polyfit of slope=None, done by the host mirror), update
-//       in the dtype numpy's promotion gives: f64 for a numpy f64 slope, f32 for a Python float / numpy f32 slope
-//   ref_subtraction_channel(image, channel_start, channel_end, use_ref_channel) :16-74  windows [start+128k, end+128k),
-//       one after the other as the reference's loop runs them (windows wider than 128 columns overlap)
-
-// median of the values of `nr` rows x (cols [c0, c0+n0) u [c1, c1+n1)) per block: block b starts at row row0 + b * rstep.
-// Dynamic LDS: npow2 floats.
-__global__ __launch_bounds__(1024) void img_window_median_kernel(const float *__restrict__ image, int w, int row0, int rstep,
-                                                                 int nr, int c0, int n0, int c1, int n1,
-                                                                 float *__restrict__ out, int npow2) {
-    extern __shared__ float mv[];
-    const int per = n0 + n1, n = nr * per;
-    const int rbase = row0 + (int)blockIdx.x * rstep;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int rr = i / per, cc = i % per;
-        const int col = cc < n0 ? c0 + cc : c1 + (cc - n0);
-        mv[i] = image[(size_t)(rbase + rr) * w + col];
-    }
-    __syncthreads();
-    const float m = block_median_sorted(mv, n, npow2);
-    if (threadIdx.x == 0) out[blockIdx.x] = m;
-}
-
-// ctr = median of the row medians; corr[r] = slope * f64(f32(ref_med[r] - ctr)) (f64 form) or f32(slope) * (ref_med[r] - ctr)
-// rounded to f32 (f32 form)
-__global__ __launch_bounds__(1024) void img_ctr2_kernel(const float *__restrict__ ref_med, double slope, int f32_form,
-                                                        double *__restrict__ rowcorr, float *__restrict__ ctr_out, int ny,
-                                                        int npow2) {
-    extern __shared__ float rm[];
-    for (int r = threadIdx.x; r < ny; r += blockDim.x) rm[r] = ref_med[r];
-    const float ctr = block_median_sorted(rm, ny, npow2);
-    const float s32 = (float)slope;
-    for (int r = threadIdx.x; r < ny; r += blockDim.x) {
-        const float d = ref_med[r] - ctr;
-        rowcorr[r] = f32_form ? (double)(s32 * d) : slope * (double)d;
-    }
-    if (threadIdx.x == 0 && ctr_out) *ctr_out = ctr;
-}
-
 __global__ void img_rowapply_f32_kernel(float *__restrict__ image, const double *__restrict__ rowcorr, int ny, int w) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)ny * w) return;
     image[i] = image[i] - (float)rowcorr[i / w];
 }
 
-// line through (1.5, b), (ny - 2.5, t) of one window (or the caller's), then the update of its columns
-__global__ void img_line1_kernel(const float *__restrict__ bt, const double *__restrict__ line_override,
-                                 double *__restrict__ line, float *__restrict__ bt_out, int ny) {
-    const float b = bt[0], t = bt[1];
-    double m, c;
-    if (line_override) {
-        m = line_override[0];
-        c = line_override[1];
-    } else {
-        m = ((double)t - (double)b) / (double)(ny - 4);
-        c = (double)b - 1.5 * m;
-    }
-    line[0] = m;
-    line[1] = c;
+// the lines of nwin windows from their bottom / top medians bt[k] (or the caller's, line_override[k])
+__global__ void img_lines_kernel(const float *__restrict__ bt, const double *__restrict__ line_override, double *__restrict__ line,
+                                 float *__restrict__ bt_out, int ny, int nwin) {
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= nwin) return;
+    const float b = bt[2 * k], t = bt[2 * k + 1];
+    chan_line(b, t, ny, line_override ? line_override + 2 * k : nullptr, line[2 * k], line[2 * k + 1]);
     if (bt_out) {
-        bt_out[0] = b;
-        bt_out[1] = t;
+        bt_out[2 * k] = b;
+        bt_out[2 * k + 1] = t;
     }
 }
 
+// the update of the ncols columns of window k = blockIdx.y, from column c0 + 128 k, by its line
 __global__ void img_winapply_kernel(float *__restrict__ image, const double *__restrict__ line, int ny, int w, int c0,
                                     int ncols) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)ny * ncols) return;
-    const int r = (int)(i / ncols), c = c0 + (int)(i % ncols);
-    const double iel = line[0] * (double)r + line[1];
+    const int k = (int)blockIdx.y;
+    const int r = (int)(i / ncols), c = c0 + k * RIP_CW + (int)(i % ncols);
+    const double iel = line[2 * k] * (double)r + line[2 * k + 1];
     float *p = image + (size_t)r * w + c;
     *p = (float)((double)*p - iel);
 }
@@ -563,19 +382,12 @@ static int pow2_at_least(int n) {
     return p;
 }
 
-template <typename K>
-static int with_lds(rip_ctx *ctx, K kernel, size_t lds) {
-    if (lds > 48 * 1024)
-        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return RIP_OK;
-}
-
 int rip_refpix_row_general(rip_ctx *ctx, float *d_image, int ny, int width, int nside, int use_ref_channel, int mode,
                            double slope, float *d_ref_med, float *d_sci_med, float *d_ctr) {
     if (nside < 16 || nside > width || (use_ref_channel && nside + RIP_CW > width))
         return rip_fail(ctx, RIP_EINVAL, "refpix row: nside=%d does not fit an image %d wide", nside, width);
     if (nside - 8 > 32768 || ny > 32768) return rip_fail(ctx, RIP_EINVAL, "refpix row: frame too large (%d x %d)", ny, nside);
-    char *ws = (char *)rip_ws(ctx, 4, (size_t)ny * (sizeof(double) + 2 * sizeof(float)) + 256);
+    char *ws = (char *)rip_ws(ctx, RIP_WS_REFPIX, (size_t)ny * (sizeof(double) + 2 * sizeof(float)) + 256);
     if (!ws) return RIP_ENOMEM;
     double *rowcorr = (double *)ws;
     float *refmed = (float *)(rowcorr + ny), *scimed = refmed + ny;
@@ -622,23 +434,27 @@ int rip_refpix_channel_general(rip_ctx *ctx, float *d_image, int ny, int width, 
         return rip_fail(ctx, RIP_EINVAL, "refpix channel: windows [%d,%d) + 128 k, k < %d do not fit an image %d wide", channel_start,
                         channel_end, nchan, width);
     if (4 * cw > 32768) return rip_fail(ctx, RIP_EINVAL, "refpix channel: window of %d columns is too wide", cw);
-    char *ws = (char *)rip_ws(ctx, 4, 64);
+    // The reference's loop takes the windows one after the other, and a window sees the updates of the windows before it.
+    // Windows no wider than a channel are disjoint column ranges: then all of them at once (medians, lines, update) give the
+    // same result; wider ones, which overlap, go one at a time.
+    const int batch = cw <= RIP_CW ? nchan : 1;
+    char *ws = (char *)rip_ws(ctx, RIP_WS_REFPIX, (size_t)batch * 2 * (sizeof(double) + sizeof(float)));
     if (!ws) return RIP_ENOMEM;
     double *line = (double *)ws;
-    float *bt = (float *)(line + 2);
+    float *bt = (float *)(line + 2 * batch);
     const int np2 = pow2_at_least(4 * cw);
     int rc;
     if ((rc = with_lds(ctx, img_window_median_kernel, (size_t)np2 * 4))) return rc;
     const size_t n = (size_t)ny * cw;
-    for (int k = 0; k < nchan; ++k) {   // in the reference's order: a window sees the updates of the windows before it
+    for (int k = 0; k < nchan; k += batch) {
         const int c0 = channel_start + k * RIP_CW;
-        // two blocks: rows 0:4 and ny-4:ny
-        hipLaunchKernelGGL(img_window_median_kernel, dim3(2), dim3(1024), (size_t)np2 * 4, ctx->stream, d_image, width, 0, ny - 4, 4,
-                           c0, cw, 0, 0, bt, np2);
-        hipLaunchKernelGGL(img_line1_kernel, dim3(1), dim3(1), 0, ctx->stream, bt, d_lines ? d_lines + 2 * k : nullptr, line,
-                           d_bottom_top ? d_bottom_top + 2 * k : nullptr, ny);
-        hipLaunchKernelGGL(img_winapply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_image, line, ny,
-                           width, c0, cw);
+        // per window two blocks: rows 0:4 and ny-4:ny
+        hipLaunchKernelGGL(img_window_median_kernel, dim3(2, batch), dim3(1024), (size_t)np2 * 4, ctx->stream, d_image, width, 0,
+                           ny - 4, 4, c0, cw, 0, 0, bt, np2);
+        hipLaunchKernelGGL(img_lines_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream, bt,
+                           d_lines ? d_lines + 2 * k : nullptr, line, d_bottom_top ? d_bottom_top + 2 * k : nullptr, ny, batch);
+        hipLaunchKernelGGL(img_winapply_kernel, dim3((unsigned)((n + 255) / 256), batch), dim3(256), 0, ctx->stream, d_image, line,
+                           ny, width, c0, cw);
     }
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;

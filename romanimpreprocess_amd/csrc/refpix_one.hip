@@ -34,8 +34,11 @@
 // are agent-scope atomics, everything else that crosses workgroups is written with sc1 (write-through) stores of whole 128-byte
 // lines by one wave instruction, each storing wave waits vmcnt(0) before its workgroup's lane 0 arrives on the counter, consumers
 // poll with sc1 loads, pass a workgroup barrier and read with sc1 loads.
+//
+// Keys, the selection levels' digit layout and scan step, the median of a selected pair, the row correction and the channel line
+// come from refpix_shared.h (shared with refpix.hip).
 #include "rip_common.h"
-#include "refpix_keys.h"
+#include "refpix_shared.h"
 #include <string.h>
 
 namespace {
@@ -52,6 +55,11 @@ struct R1Ctrl {
     uint32_t arrive[3];
     uint32_t exitc;
 };
+// the scratch that is zero between launches (workspace RIP_WS_R1_ZERO, cleared when the slot is (re)allocated): control words
+// R1Ctrl[RIP_MAX_GROUPS] | histograms [RIP_MAX_GROUPS][3][2][SEL_BINS] | status word
+constexpr size_t R1_GHIST_OFF = ((size_t)RIP_MAX_GROUPS * sizeof(R1Ctrl) + 255) / 256 * 256;
+constexpr size_t R1_STATUS_OFF = R1_GHIST_OFF + (size_t)RIP_MAX_GROUPS * 3 * 2 * SEL_BINS * sizeof(uint32_t);
+constexpr size_t R1_ZERO_BYTES = R1_STATUS_OFF + 256;
 
 struct R1Args {
     const void *data;
@@ -169,16 +177,6 @@ __device__ __forceinline__ void mergeN(uint32_t (&v)[NS], int lane, bool desc = 
     stageN<2, NS>(v, lane, 64, desc);
     stageN<1, NS>(v, lane, 64, desc);
 }
-__device__ __forceinline__ uint32_t sort64(uint32_t v, int lane, bool desc = false) {
-    uint32_t a[1] = {v};
-    sortN<1>(a, lane, desc);
-    return a[0];
-}
-__device__ __forceinline__ uint32_t merge64(uint32_t v, int lane, bool desc = false) {
-    uint32_t a[1] = {v};
-    mergeN<1>(a, lane, desc);
-    return a[0];
-}
 __device__ __forceinline__ uint32_t rev64(uint32_t v, int lane) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((63 - lane) << 2, (int)v);
 }
@@ -232,25 +230,8 @@ __device__ __forceinline__ void hist_slot(uint32_t key, bool live, int lv, uint3
 // Among SEL_BINS counts (four per thread: c[0..3] = bins 4t .. 4t+3 for t = tid & 511; the halves of the workgroup scan one
 // histogram each, q = tid >> 9) the bin holding rank[q]; result in sel[q] = {bin, rank inside the bin}.  All threads call.
 __device__ __forceinline__ void scan_find(const uint32_t (&c)[4], uint32_t rank, uint32_t (*wtot)[8], uint32_t (*sel)[2], int tid) {
-    const int lane = tid & 63, q = tid >> 9, t = tid & 511, wq = (tid >> 6) & 7;
-    const uint32_t own = c[0] + c[1] + c[2] + c[3];
-    uint32_t incl = own;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = (uint32_t)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) wtot[q][wq] = incl;
-    __syncthreads();
-    for (int k = 0; k < wq; ++k) incl += wtot[q][k];
-    const uint32_t excl = incl - own;
-    if ((excl <= rank && rank < incl) || (t == 511 && rank >= incl)) {
-        uint32_t cum = excl;
-        int b = 0;
-        while (b < 3 && cum + c[b] <= rank) cum += c[b++];
-        sel[q][0] = (uint32_t)(4 * t + b);
-        sel[q][1] = rank - cum;
-    }
+    const int q = tid >> 9;
+    sel_find_bin<512, 4>([&](int k) { return c[k]; }, rank, tid & 511, true, wtot[q], sel[q][0], sel[q][1]);
     __syncthreads();
 }
 
@@ -310,14 +291,7 @@ __device__ __forceinline__ float chan_median(const uint32_t (&x)[4][2], int lane
     }
     lo = wave_umax(lo, lane);
     hi = wave_umin(hi, lane);
-    return (key2f(lo) + key2f(hi)) * 0.5f;
-}
-// the line through (1.5, b), (ny - 2.5, t) (reference_subtraction.py:57-60; DESIGN.md "channel line fit")
-__device__ __forceinline__ void store_line(const R1Args &a, int g, int nch, int ch, float b, float t) {
-    const double m = ((double)t - (double)b) / (double)(a.ny - 4);
-    const double c = (double)b - 1.5 * m;
-    a.lines[((size_t)g * nch + ch) * 2] = m;
-    a.lines[((size_t)g * nch + ch) * 2 + 1] = c;
+    return key_median(lo, hi);
 }
 
 // Row tables of one group from its row medians (refmed[k]: row tid + 1024 k, already minus the block's median): ctr = their
@@ -365,12 +339,12 @@ __device__ __forceinline__ void row_tables(const float (&refmed)[R1_NV], const R
         for (int i = tid; i < 2 * SEL_BINS; i += R1_THREADS) (&hist[0][0])[i] = 0;
         __syncthreads();
     }
-    const float ctr = (key2f(pre2[0]) + key2f(pre2[1])) * 0.5f;
+    const float ctr = key_median(pre2[0], pre2[1]);
 #pragma unroll
     for (int k = 0; k < R1_NV; ++k) {
         const int r = tid + R1_THREADS * k;
         if (r < ny) {
-            const double v = a.slope * (double)(refmed[k] - ctr);
+            const double v = row_corr(a.slope, refmed[k], ctr);
             a.rowcorr[(size_t)g * ny + r] = v;
             if (a.rowcorr_t) a.rowcorr_t[(size_t)r * a.G + g] = v;   // [row][group]: one scalar load per row in the fused kernel
             if (r < 4) rc8[r] = v;
@@ -379,7 +353,6 @@ __device__ __forceinline__ void row_tables(const float (&refmed)[R1_NV], const R
     }
     __syncthreads();
 }
-
 
 #define R1_STAMP(k)                                                                                    \
     if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime();
@@ -509,7 +482,7 @@ __global__ __launch_bounds__(R1_THREADS) void refpix_one_kernel(R1Args a) {
         __syncthreads();   // sel is rewritten by the next level
         R1_STAMP(4 + 3 * lv)
     }
-    const float M = (key2f(prefix[0]) + key2f(prefix[1])) * 0.5f;   // np.median of the block
+    const float M = key_median(prefix[0], prefix[1]);   // np.median of the block
 
     // this workgroup is done with the group's histograms and counters: the last one to say so restores their zero state
     if (tid == 0) flag_s = __hip_atomic_fetch_add(&ctrl->exitc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -557,11 +530,13 @@ __global__ __launch_bounds__(R1_THREADS) void refpix_one_kernel(R1Args a) {
             }
             bt[half] = chan_median(x, lane);
         }
-        if (lane == 0) store_line(a, g, nch, ch, bt[0], bt[1]);
+        if (lane == 0) {
+            const size_t o = ((size_t)g * nch + ch) * 2;
+            chan_line(bt[0], bt[1], ny, nullptr, a.lines[o], a.lines[o + 1]);
+        }
     }
     R1_STAMP(14)
 }
-
 
 }  // namespace
 
@@ -577,17 +552,14 @@ int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a) {
     if (!rip_refpix_one_supported(a)) return rip_fail(ctx, RIP_EINVAL, "refpix: frame not covered by the single-launch pre-pass");
     const int G = a.ngrp, ny = a.ny, nch = a.nx / RIP_CW;
     const int B = (ny + R1_ROWS - 1) / R1_ROWS;
-    // scratch: control words + histograms (zero between launches; cleared when the slot is (re)allocated) | status | lo, hi | chsort
-    const size_t ctrl_b = ((size_t)RIP_MAX_GROUPS * sizeof(R1Ctrl) + 255) / 256 * 256;
-    const size_t gh_b = (size_t)RIP_MAX_GROUPS * 3 * 2 * SEL_BINS * sizeof(uint32_t);
-    const size_t zero_b = ctrl_b + gh_b + 256;
-    const void *had = ctx->ws[14];
-    char *z = (char *)rip_ws(ctx, 14, zero_b);
+    const void *had = ctx->ws[RIP_WS_R1_ZERO];
+    char *z = (char *)rip_ws(ctx, RIP_WS_R1_ZERO, R1_ZERO_BYTES);
     if (!z) return RIP_ENOMEM;
-    if ((const void *)z != had) RIP_HIP(ctx, hipMemsetAsync(z, 0, zero_b, st));
+    if ((const void *)z != had) RIP_HIP(ctx, hipMemsetAsync(z, 0, R1_ZERO_BYTES, st));
+    // scratch: lo, hi | chsort
     const size_t lohi_b = ((size_t)G * ny * 4 + 255) / 256 * 256;
     const size_t chs_b = (size_t)G * nch * 8 * RIP_CW * 4;
-    char *s = (char *)rip_ws(ctx, 15, 2 * lohi_b + chs_b);
+    char *s = (char *)rip_ws(ctx, RIP_WS_R1_SCRATCH, 2 * lohi_b + chs_b);
     if (!s) return RIP_ENOMEM;
     R1Args r;
     r.data = a.data;
@@ -599,8 +571,8 @@ int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a) {
     r.rowcorr_t = a.rowcorr_t;
     r.lines = a.lines;
     r.ctrl = (R1Ctrl *)z;
-    r.ghist = (uint32_t *)(z + ctrl_b);
-    r.status = (uint32_t *)(z + ctrl_b + gh_b);
+    r.ghist = (uint32_t *)(z + R1_GHIST_OFF);
+    r.status = (uint32_t *)(z + R1_STATUS_OFF);
     r.lo = (uint32_t *)s;
     r.hi = (uint32_t *)(s + lohi_b);
     r.chsort = (uint32_t *)(s + 2 * lohi_b);
@@ -618,16 +590,20 @@ int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a) {
     return RIP_OK;
 }
 
-// != 0 after a pre-pass whose group barrier timed out (diagnostic; synchronises the stream)
+// != 0 when a group barrier of a single-launch pre-pass timed out since the last call; the word is cleared, so a timeout is
+// reported once (diagnostic; synchronises the streams)
 int rip_refpix_one_status(rip_ctx *ctx, int *status) {
     *status = 0;
-    if (!ctx->ws[14]) return RIP_OK;
-    const size_t ctrl_b = ((size_t)RIP_MAX_GROUPS * sizeof(R1Ctrl) + 255) / 256 * 256;
-    const size_t gh_b = (size_t)RIP_MAX_GROUPS * 3 * 2 * SEL_BINS * sizeof(uint32_t);
+    if (!ctx->ws[RIP_WS_R1_ZERO]) return RIP_OK;
+    uint32_t *word = (uint32_t *)((char *)ctx->ws[RIP_WS_R1_ZERO] + R1_STATUS_OFF);
     uint32_t v = 0;
     RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->stream2) RIP_HIP(ctx, hipStreamSynchronize(ctx->stream2));
-    RIP_HIP(ctx, hipMemcpy(&v, (char *)ctx->ws[14] + ctrl_b + gh_b, 4, hipMemcpyDeviceToHost));
+    RIP_HIP(ctx, hipMemcpy(&v, word, 4, hipMemcpyDeviceToHost));
+    if (v) {
+        RIP_HIP(ctx, hipMemsetAsync(word, 0, 4, ctx->stream));
+        RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     *status = (int)v;
     return RIP_OK;
 }

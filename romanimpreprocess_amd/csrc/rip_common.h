@@ -117,6 +117,28 @@ struct RipCal {
     size_t bytes = 0;
 };
 
+// device workspaces of a context (rip_ws: grown on demand, kept between calls), one slot per use
+enum RipWs {
+    RIP_WS_CUBE_A = 0,      // stage kernels: the corrected cube (+ a pixel-dq plane)
+    RIP_WS_CUBE_B = 1,      // stage kernels: the cube after IPC; host calls: the cube the fused kernel writes
+    RIP_WS_STAGING = 2,     // host inputs of a call, CALDIR planes before they are embedded
+    RIP_WS_TABLES = 3,      // reference-pixel tables (two sets, by call parity) + the per-exposure flat plane
+    RIP_WS_REFPIX = 4,      // multi-launch pre-pass: row middle elements + selection state; image drop-ins: row / line tables
+    RIP_WS_IPC_X = 5,       // single-image IPC operator: gain * image
+    RIP_WS_IPC_A = 6,       // single-image IPC operator: first pass
+    RIP_WS_RESULTS = 7,     // host calls: the result planes before they are read back
+    RIP_WS_SATFLAG = 8,     // saturation pass: flag-array copies (two sets, by call parity)
+    RIP_WS_EXCEED = 9,      // saturation flagging: per-pixel exceed bits
+    RIP_WS_SHARE_TAB = 10,  // Level-1 synthesis: the read-share table
+    RIP_WS_SYNTH_START = 11,  // Level-1 synthesis: the start-of-exposure image
+    RIP_WS_FRAMES = 12,     // Level-1 synthesis: 1/f frames
+    RIP_WS_SEL_HIST = 13,   // multi-launch pre-pass: selection histograms (zero between calls)
+    RIP_WS_R1_ZERO = 14,    // single-launch pre-pass: control words + histograms + status word (zero between calls)
+    RIP_WS_R1_SCRATCH = 15,   // single-launch pre-pass: row / channel scratch
+    RIP_WS_DEFER = 16,      // Level-1 synthesis: the apportioning's lists of deferred pixels
+    RIP_WS_COUNT
+};
+
 struct rip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -139,10 +161,8 @@ struct rip_ctx {
     double guard_band = 1e-5;  // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
     bool prof = false;
     std::vector<hipEvent_t> prof_events;  // 6 per rip_calibrate call
-    void *ws[18] = {};          // 0-9: calibration path and stage entries; 10-12: Level-1 synthesis (synth.hip); 13: the multi-launch
-                                // pre-pass's selection histograms (zero between calls); 14: control words + histograms of the
-                                // single-launch pre-pass (zero between calls), 15: its row / channel scratch; 16: the apportioning's list of deferred pixels
-    size_t ws_bytes[18] = {};
+    void *ws[RIP_WS_COUNT] = {};   // RipWs
+    size_t ws_bytes[RIP_WS_COUNT] = {};
     void *prepass_stamps = nullptr;   // diagnostic: device buffer of 16 clock stamps per workgroup of the single-launch pre-pass
     bool chain_quad = true;     // a last strip of <= 64 live columns in quad mode (chain2_geometry); false: every strip alike (A/B timing)
     int chain_reserve = 8;      // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
@@ -188,7 +208,7 @@ struct rip_ctx {
 // ---------------------------------------------------------------- host helpers
 int rip_fail(rip_ctx *ctx, int code, const char *fmt, ...);
 void rip_pink_release(rip_ctx *ctx);   // pink.hip: drops the cached transform plan and buffers
-void *rip_ws(rip_ctx *ctx, int slot, size_t bytes);  // nullptr on failure (error recorded)
+void *rip_ws(rip_ctx *ctx, RipWs slot, size_t bytes);  // nullptr on failure (error recorded)
 
 #define RIP_HIP(ctx, call)                                                                      \
     do {                                                                                        \
@@ -312,18 +332,18 @@ struct RefpixArgs {
     int background = 0;   // 1: launched beside the previous ramp's fused kernel (second stream)
     hipStream_t stream = nullptr;   // where the launches go (null: the context's main stream)
 };
-int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a);
+// the form that makes a call's tables (1: refpix_one.hip, 0: refpix.hip) from option = rip_ctx::prepass_form or a stage call's
+int rip_refpix_form(int option, const RefpixArgs &a);
+int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a, int form);
 // refpix_one.hip: the same tables in one launch (frames up to 4096 rows with a reference output)
 bool rip_refpix_one_supported(const RefpixArgs &a);
 int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a);
-int rip_refpix_one_status(rip_ctx *ctx, int *status);
+int rip_refpix_one_status(rip_ctx *ctx, int *status);   // reads and clears the barrier-timeout word
 // the general forms (any argument of reference_subtraction.py's two functions); device pointers
 int rip_refpix_row_general(rip_ctx *ctx, float *d_image, int ny, int width, int nside, int use_ref_channel, int mode,
                            double slope, float *d_ref_med, float *d_sci_med, float *d_ctr);
 int rip_refpix_channel_general(rip_ctx *ctx, float *d_image, int ny, int width, int channel_start, int channel_end, int nchan,
                                const double *d_lines, float *d_bottom_top);
-int rip_refpix_image(rip_ctx *ctx, float *d_image, int ny, int nx, double slope, int do_row, int do_channel,
-                     const double *d_lines, float *d_ref_med, float *d_ctr, float *d_bottom_top);
 
 // misc.hip
 int rip_launch_embed(rip_ctx *ctx, const void *src, void *dst, int nplanes, int ny, int nx, int nb, int elem_size);

@@ -458,8 +458,8 @@ extern "C" int rip_synth_apportion(rip_ctx *ctx, const float *counts, int nya, i
         tab.lw[r] = w > 0.0 ? log(w) : 0.0;
         t_prev = t_reads[r];
     }
-    const void *had = ctx->ws[10];
-    double *d_tab = (double *)rip_ws(ctx, 10, sizeof(ShareTable));
+    const void *had = ctx->ws[RIP_WS_SHARE_TAB];
+    double *d_tab = (double *)rip_ws(ctx, RIP_WS_SHARE_TAB, sizeof(ShareTable));
     if (!d_tab) return RIP_ENOMEM;
     // the device copy of the table is kept between calls: an exposure after exposure of one read pattern (the many-realisations
     // harness) uploads it once and the call stays asynchronous; a new table waits for the kernels still reading the old one
@@ -476,7 +476,7 @@ extern "C" int rip_synth_apportion(rip_ctx *ctx, const float *counts, int nya, i
     uint32_t *defer = nullptr;
     double w_max = 0.0;
     if (poisson && npix < 0xFFFFFFFFull) {
-        defer = (uint32_t *)rip_ws(ctx, 16, (DEFER_HEAD + 2 * DEFER_LISTS * defer_cap(npix)) * sizeof(uint32_t));
+        defer = (uint32_t *)rip_ws(ctx, RIP_WS_DEFER, (DEFER_HEAD + 2 * DEFER_LISTS * defer_cap(npix)) * sizeof(uint32_t));
         if (!defer) return RIP_ENOMEM;
         RIP_HIP(ctx, hipMemsetAsync(defer, 0, DEFER_HEAD * sizeof(uint32_t), ctx->stream));
         for (int r = 0; r < nreads; ++r) w_max = tab.w[r] > w_max ? tab.w[r] : w_max;
@@ -514,7 +514,7 @@ extern "C" int rip_synth_resultants(rip_ctx *ctx, const rip_synth_cal *cal, int 
     const int nya = cal->ny - 2 * cal->nb, nxa = cal->nx - 2 * cal->nb;
     float *start = start_e;
     if (!start) {
-        start = (float *)rip_ws(ctx, 11, (size_t)nya * nxa * sizeof(float));
+        start = (float *)rip_ws(ctx, RIP_WS_SYNTH_START, (size_t)nya * nxa * sizeof(float));
         if (!start) return RIP_ENOMEM;
     }
     const dim3 ga((unsigned)((nxa + 255) / 256), (unsigned)nya), block(256);
@@ -571,7 +571,7 @@ extern "C" int rip_synth_fill(rip_ctx *ctx, const rip_synth_cal *cal, int ngrp, 
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t fsz = (size_t)cal->ny * cal->channelwidth;
     if (banding && !frames) {
-        float *made = (float *)rip_ws(ctx, 12, (size_t)ngrp * (nch + 2) * fsz * sizeof(float));
+        float *made = (float *)rip_ws(ctx, RIP_WS_FRAMES, (size_t)ngrp * (nch + 2) * fsz * sizeof(float));
         if (!made) return RIP_ENOMEM;
         if (ctx->frames_pending && ctx->frames_seed == seed && ctx->frames_geom[0] == cal->ny && ctx->frames_geom[1] == cal->channelwidth &&
             ctx->frames_geom[2] == ngrp * (nch + 2)) {

@@ -35,20 +35,6 @@ def _nside(image, nside, use_ref_channel):
     return int(nside)
 
 
-def _run(image, slope, do_row, do_channel, lines, ctx):
-    """the configuration of calibrateimage (33 channels, reference-output row medians, float64 slope): one call"""
-    ctx = ctx or _native.default_context()
-    _check(image)
-    ny, w = image.shape
-    nx = w - 128
-    if nx <= 0 or nx % 128:
-        raise ValueError("image must be (ny, 128*nchannel + 128): science channels plus the reference output")
-    ln = None if lines is None else np.ascontiguousarray(lines, dtype=np.float64)
-    ctx.check(ctx.lib.rip_stage_refpix_image(ctx.h, image.ctypes.data, ny, nx, float(slope), int(do_row), int(do_channel),
-                                             None if ln is None else ln.ctypes.data, None, None, None))
-    return image
-
-
 def _is_f64_scalar(x):
     return isinstance(x, (np.floating, np.ndarray)) and np.asarray(x).dtype == np.float64
 
@@ -78,8 +64,6 @@ def ref_subtraction_row(image, use_ref_channel=False, slope=None, ctx=None, nsid
     if slope is None:
         ref, sci, _ctr = row_medians(image, use_ref_channel, ns, True, ctx)
         slope, _ = np.polyfit(ref, sci, 1)          # reference_subtraction.py:114, on float32 medians
-    if use_ref_channel and _is_f64_scalar(slope) and ns + 128 == w and ns % 128 == 0:
-        return _run(image, slope, 1, 0, None, ctx)   # the driver's configuration: the single-purpose kernels
     mode = ROW_SLOPE_F64 if _is_f64_scalar(slope) else ROW_SLOPE_F32
     ctx.check(ctx.lib.rip_stage_refpix_row(ctx.h, image.ctypes.data, ny, w, ns, int(bool(use_ref_channel)), mode, float(slope),
                                            None, None, None))
@@ -96,8 +80,6 @@ def ref_subtraction_channel(image, channel_start=0, channel_end=128, use_ref_cha
     nchan = (32 if n_channels is None else int(n_channels)) + (1 if use_ref_channel else 0)   # :42-44
     if channel_end + (nchan - 1) * 128 > w:
         raise ValueError(f"{nchan} windows of columns [{channel_start}, {channel_end}) + 128 k do not fit an image {w} wide")
-    if use_ref_channel and channel_start == 0 and channel_end == 128 and nchan * 128 == w:
-        return _run(image, 0.0, 0, 1, lines, ctx)
     ln = None if lines is None else np.ascontiguousarray(lines, dtype=np.float64)
     if ln is not None and ln.shape != (nchan, 2):
         raise ValueError(f"lines must be ({nchan}, 2)")
