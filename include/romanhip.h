@@ -334,6 +334,32 @@ int rip_stage_gauss_hist(rip_ctx *ctx, const float *arr, int64_t n, const double
 int rip_stage_legendre2d(rip_ctx *ctx, float *arr, int ny, int nx, int order, const double *LPX, const double *LPY,
                          const double *coef, int subtract, float *model_out);
 
+/* A FITS celestial WCS of a zenithal projection (Calabretta & Greisen 2002, sect. 5.1), optionally with SIP distortion: what
+   the exposure's FITSWCS header (gen_cal_image.py:64-87) holds, parsed and validated by the host
+   (romanimpreprocess_amd/utils/coordutils.py:FitsWCS).  Pixel coordinates are 0-based and crpix is a 0-based pixel
+   coordinate (the header's CRPIX minus 1, the convention sim_to_isim.py:501-503 writes the header in).  Angles in degrees. */
+typedef enum { RIP_PROJ_TAN = 0, RIP_PROJ_STG = 1, RIP_PROJ_ZEA = 2, RIP_PROJ_ARC = 3, RIP_PROJ_SIN = 4 } rip_projection;
+#define RIP_SIP_MAX_ORDER 9
+typedef struct {
+    int32_t projection;  /* rip_projection                                                                              */
+    int32_t sip_order;   /* 0 = no SIP; else max(A_ORDER, B_ORDER) <= RIP_SIP_MAX_ORDER                                  */
+    double crpix[2];     /* 0-based reference pixel (x, y)                                                              */
+    double cd[2][2];     /* CDi_j, or CDELTi * PCi_j                                                                    */
+    double crval[2];     /* (alpha0, delta0) of the reference point                                                     */
+    double lonpole;      /* LONPOLE, 180 by default                                                                    */
+    double sip_a[RIP_SIP_MAX_ORDER + 1][RIP_SIP_MAX_ORDER + 1]; /* A_p_q at [p][q], zero where absent                     */
+    double sip_b[RIP_SIP_MAX_ORDER + 1][RIP_SIP_MAX_ORDER + 1]; /* B_p_q at [p][q], zero where absent                     */
+} rip_wcs_desc;
+
+/* coordutils.pixelarea (coordutils.py:17-82) on an (ny,nx) frame: the solid angle of every pixel from the WCS evaluated on the
+   pixel grid x = -1..nx, y = -1..ny, re-projected to Lambert equal-area coordinates about the pole of the hemisphere of grid
+   point (-1,-1), and central differences of those; out (ny,nx) f64 = area / scale (scale = 1: steradians; Omega_ideal: the
+   AreaFactor of gen_cal_image.py:618-621, which rip_ramp_desc::area_factor takes).  f64 throughout.
+   out_location RIP_HOST: out is a host array, the call returns when it is filled; RIP_DEVICE: out is device memory, written
+   in place, ordered on rip_stream().  RIP_EINVAL for an unknown projection, sip_order outside 0..9, ny or nx < 1, scale <= 0
+   or a non-finite descriptor. */
+int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, double scale, int out_location, double *out);
+
 /* ---- simulation side ------------------------------------------------- */
 /* ipc_linearity.invlinearity (ipc_linearity.py:347-394): 24 bisection steps on z in (-1, 1) of the Legendre series evaluated
    as ipc_linearity._lin does without the extrapolation branch, then S = Smin + (Smax - Smin)/2 * (1 + z).  slin (ny,nx) f32 or

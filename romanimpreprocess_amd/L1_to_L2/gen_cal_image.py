@@ -14,9 +14,12 @@ What runs where
     the L2 tree layout of ``romanisim.image.make_asdf`` (:653-662);
   * the post-path reductions (:632-651, 697-712: median gain, sky mode, SKYORDER model, SLICEOUT) -> ``utils/sky.py``,
     ``utils/maskhandling.py`` (HIP kernels);
-  * not done here (outside the hot path): WCS->gwcs and the pixel-area map (pass ``AREAFACTOR``: file with
-    an (N,N) f64 array, else 1), dark decay, WFI18 transient, romancal likelihood ramp fit, FITS output.  Asking for one
-    of those raises NotImplementedError.
+  * the pixel-area map of the flat division (:616-622): from the exposure's WCS, ``config["FITSWCS"]`` (a FITS header as text,
+    :64-87, read by ``wcs_from_config``), through ``utils/coordutils.py`` and one HIP kernel (``rip_stage_pixel_area``) over the
+    full frame, border included, as the reference's ``N=np.shape(slope)[-1]``.  The repository's own ``AREAFACTOR`` key (a
+    file with an (N,N) f64 array) takes precedence when both are given; with neither, AreaFactor = 1;
+  * not done here (outside the hot path): the gwcs object of the L2 tree (:660), dark decay, WFI18 transient,
+    romancal likelihood ramp fit, FITS output.  Asking for one of those raises NotImplementedError.
 """
 
 import sys
@@ -25,9 +28,17 @@ import numpy as np
 
 from .. import calio, pars, pipeline, plan as planmod
 from ..dqflags import group
-from ..utils import maskhandling, processlog, sky
+from ..utils import coordutils, flatutils, maskhandling, processlog, sky
 
 _cal_cache = {}  # (ctx id, tuple of CALDIR paths) -> slot
+
+
+def wcs_from_config(config):
+    """The exposure's WCS from the configuration (gen_cal_image.py:64-87): ``config["FITSWCS"]`` is the path of a FITS header
+    written as text (``sim_to_isim.py:986-987``), returned as a validated ``coordutils.FitsWCS``; None without the key."""
+    if "FITSWCS" in config:
+        return coordutils.FitsWCS.from_file(config["FITSWCS"])
+    return None
 
 
 def initializationstep(config, caldir, mylog):
@@ -137,6 +148,10 @@ def calibrateimage(config, verbose=True, calibrator=None):
     if "AREAFACTOR" in config:
         with calio.open_tree(config["AREAFACTOR"]) as f:
             area = np.asarray(f["roman"]["data"], dtype=np.float64)
+    elif "FITSWCS" in config:
+        # the ratio of the true pixel area to the reference area (0.11 arcsec)^2 over the full frame (:618-621)
+        area = cb.area_factor(wcs_from_config(config), *ramp["data"].shape[-2:])
+        mylog.append("pixel-area map from FITSWCS (GPU)\n")
     ramp["read_pattern"], ramp["frame_time"] = meta["read_pattern"], meta["frame_time"]
     if sat_on_device:
         ramp["groupdq"] = None  # zeros + DO_NOT_USE on the first group: made on the device
@@ -148,6 +163,13 @@ def calibrateimage(config, verbose=True, calibrator=None):
     mylog.append(f"\n\nRamp fit optimized for u = {planmod.ramp_opt_u(uopt):11.5E} s**-1\n")
     mylog.append(f"weights = {K}\n")
     mylog.append("Reference pixels, bias, linearity, IPC, ramp fit, dark current, flat: complete (GPU)\n")
+    if area is not None:   # the flat the slope was divided by, f32(flat / AreaFactor), as the reference logs it (:622-626)
+        flat = (flatutils.get_flat(caldir, meta, None, ipc_deconvolve="ipc4d" in caldir, ctx=cb.ctx) / area).astype(np.float32)
+        mylog.append("acquired flat field\n")
+        for p in [1, 2, 5, 10, 25, 50, 75, 90, 95, 98, 99]:
+            mylog.append(f" {p:2d}%ile = {np.percentile(flat, p):6.4f},")
+        mylog.append("\n")
+        del flat
 
     slope, pdq, rdq = res["slope"], res["pixeldq"], res["groupdq"]
     err_read, err_poisson = res["err_read"], res["err_poisson"]

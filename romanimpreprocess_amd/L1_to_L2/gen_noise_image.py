@@ -159,7 +159,7 @@ class _Files:
 
 def _device_path_applies(config, rng):
     """The HBM-resident layer loop runs when the exposures stay in memory, the deviates are the device's and nothing asks for a
-    host-side ingredient (pixel-area map)."""
+    host-side ingredient (an ``AREAFACTOR`` file; a ``FITSWCS`` pixel-area map is made on the device and stays there)."""
     if not bool(config["NOISE"].get("IN_MEMORY", True)) or not bool(config["NOISE"].get("DEVICE_RESIDENT", True)):
         return False
     if isinstance(rng, np.random.Generator) or "AREAFACTOR" in config or not config["NOISE"].get("CORRELATED", True):
@@ -180,7 +180,7 @@ def _make_noise_cube_device(config, seed, files, base_tree):
     from .. import pipeline
     from ..devarray import DevArray
     from ..from_sim.sim_to_isim import L1Synth
-    from .gen_cal_image import _caldir_slot
+    from .gen_cal_image import _caldir_slot, wcs_from_config
 
     layers = config["NOISE"]["LAYER"]
     nb = pars.nborder
@@ -213,6 +213,9 @@ def _make_noise_cube_device(config, seed, files, base_tree):
         t_mask = torch.zeros((ny, nx), dtype=torch.int32, device=dev)
     read = np.asarray(files.roman(caldir["read"])["data"], dtype=np.float32)
     t_read = up(read)
+    thewcs = wcs_from_config(config)   # AreaFactor in HBM, the same map calibrateimage divides by
+    t_area = None if thewcs is None else cb.area_factor(thewcs, ny, nx, device=True)
+    area_ptr = None if t_area is None else t_area.data_ptr()
     nreads = np.array([len(g) for g in read_pattern], dtype=np.int32)
     l2 = files.tree(config["OUT"])
     t_orig = up(np.asarray(l2["roman"]["data"], dtype=np.float32))
@@ -231,8 +234,8 @@ def _make_noise_cube_device(config, seed, files, base_tree):
         """roman.data of calibrateimage for a device-resident exposure: the chain, the active region, minus the sky model"""
         tsync()
         cb.calibrate_device(slot, pid, G, t_cube.data_ptr(), True, None if t_a33 is None else t_a33.data_ptr(), None, t_mask.data_ptr(),
-                            outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), flag_saturation=True,
-                            saturation_backup=backup, read_pattern=read_pattern)
+                            outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), area_ptr=area_ptr,
+                            flag_saturation=True, saturation_backup=backup, read_pattern=read_pattern)
         cb.synchronize()
         data = outs[0][nb:ny - nb, nb:nx - nb].contiguous()
         if skyorder is not None:

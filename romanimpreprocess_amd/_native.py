@@ -17,6 +17,8 @@ RIP_TIMING_BUILD_FLAG = 1000000   # include/romanhip.h
 RIP_F32, RIP_F64, RIP_U16 = 0, 1, 2
 RIP_HOST, RIP_DEVICE = 0, 1
 RIP_INPUTS_STREAM_ORDERED, RIP_INPUTS_COMPLETE = 0, 1
+RIP_PROJ_TAN, RIP_PROJ_STG, RIP_PROJ_ZEA, RIP_PROJ_ARC, RIP_PROJ_SIN = 0, 1, 2, 3, 4
+RIP_SIP_MAX_ORDER = 9
 
 STAGE_REFPIX, STAGE_BIAS, STAGE_LIN, STAGE_IPC, STAGE_RAMPFIT, STAGE_DARK, STAGE_FLAT = (1 << i for i in range(7))
 STAGE_ALL = 0x7F
@@ -83,6 +85,15 @@ class SynthCal(C.Structure):   # rip_synth_cal: DEVICE pointers
     ]
 
 
+class WcsDesc(C.Structure):   # rip_wcs_desc: a FITS zenithal (+SIP) WCS, crpix 0-based, angles in degrees
+    _fields_ = [
+        ("projection", C.c_int32), ("sip_order", C.c_int32), ("crpix", C.c_double * 2), ("cd", (C.c_double * 2) * 2),
+        ("crval", C.c_double * 2), ("lonpole", C.c_double),
+        ("sip_a", (C.c_double * (RIP_SIP_MAX_ORDER + 1)) * (RIP_SIP_MAX_ORDER + 1)),
+        ("sip_b", (C.c_double * (RIP_SIP_MAX_ORDER + 1)) * (RIP_SIP_MAX_ORDER + 1)),
+    ]
+
+
 # every symbol include/romanhip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _I = C.c_int
@@ -120,6 +131,7 @@ SYMBOLS = {
     "rip_stage_select_ranks": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
     "rip_stage_gauss_hist": (_I, [_VP, _VP, C.c_int64, _VP, _I, C.c_double, _VP]),
     "rip_stage_legendre2d": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _I, _VP]),
+    "rip_stage_pixel_area": (_I, [_VP, C.POINTER(WcsDesc), _I, _I, C.c_double, _I, _VP]),
     "rip_stage_invlinearity": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "rip_stage_noise_inject": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, C.c_uint64, C.c_uint32, _VP]),
     "rip_stage_noise_1f": (_I, [_VP, _I, _I, _I, _VP, C.c_uint64, C.c_uint32, _VP]),

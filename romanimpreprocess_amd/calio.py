@@ -9,7 +9,8 @@ same mapping for
     reader below (ASDF 1.x: YAML tree + binary blocks, uncompressed / zlib / bzip2 blocks, ndarray
     tags with ``source``/``datatype``/``byteorder``/``shape``[/``offset``/``strides``], inline arrays).
 ``write_asdf`` writes such files (uncompressed blocks) so that synthetic CALDIR sets and L2 products
-can be exchanged with the reference tooling.
+can be exchanged with the reference tooling.  ``parse_fits_header`` reads the FITS header text of an exposure's WCS
+(``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy.
 """
 
 import bz2
@@ -18,6 +19,7 @@ import hashlib
 import io
 import json
 import os
+import re
 import struct
 import zlib
 
@@ -252,3 +254,65 @@ def _materialise(node):
     if hasattr(node, "shape") and hasattr(node, "dtype"):
         return np.asarray(node)
     return node
+
+
+# ------------------------------------------------------------------------------- FITS header text
+_FITS_INT = re.compile(r"[+-]?\d+\Z")
+_FITS_FLOAT = re.compile(r"[+-]?(\d+\.?\d*|\.\d+)([EeDd][+-]?\d+)?\Z")
+
+
+def _fits_value(key, text):
+    """Value of a card's value field (the text after ``= ``): quoted string, logical, integer or float; None if empty."""
+    s = text.lstrip()
+    if s.startswith("'"):
+        out, i = [], 1
+        while True:
+            j = s.find("'", i)
+            if j < 0:
+                raise ValueError(f"FITS header: unterminated string in {key}")
+            out.append(s[i:j])
+            if s[j + 1:j + 2] == "'":   # '' is a quote inside the string
+                out.append("'")
+                i = j + 2
+                continue
+            rest = s[j + 1:].strip()
+            if rest and not rest.startswith("/"):
+                raise ValueError(f"FITS header: text after the string of {key}: {rest!r}")
+            return "".join(out).rstrip()
+    token = s.split("/", 1)[0].strip()
+    if token == "":
+        return None
+    if token in ("T", "F"):
+        return token == "T"
+    if _FITS_INT.match(token):
+        return int(token)
+    if _FITS_FLOAT.match(token):
+        return float(token.replace("D", "E").replace("d", "e"))
+    raise ValueError(f"FITS header: cannot read the value of {key}: {token!r}")
+
+
+def parse_fits_header(text):
+    """A FITS header given as text -> dict keyword -> value (str, bool, int, float or None), without astropy.
+
+    Accepts what ``astropy.io.fits.Header.tofile`` writes (80-character cards with no separator, ``END``, blank padding to 2880
+    bytes) and cards separated by newlines (what ``Header.fromstring(..., sep="\\n")`` reads).  Strings are unquoted (``''`` is a
+    quote) with trailing blanks removed; ``/ comments`` are dropped; COMMENT, HISTORY, blank and other cards without a value
+    indicator are skipped; a repeated keyword keeps its first value, as ``Header[key]`` does.  Reading stops at ``END``.  A value
+    that is none of the above raises ValueError naming the keyword."""
+    if isinstance(text, (bytes, bytearray)):
+        text = text.decode("ascii")
+    cards = []
+    for line in text.splitlines():
+        line = line.rstrip("\r")
+        cards.extend(line[i:i + 80] for i in range(0, max(len(line), 1), 80))
+    out = {}
+    for card in cards:
+        card = card.ljust(80)
+        key = card[:8].strip().upper()
+        if key == "END" and not card[8:].strip():
+            break
+        if key in ("", "COMMENT", "HISTORY") or card[8:10] != "= ":
+            continue
+        if key not in out:
+            out[key] = _fits_value(key, card[10:])
+    return out

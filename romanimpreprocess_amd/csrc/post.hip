@@ -6,7 +6,11 @@
 //                                                                                            rip_stage_gauss_hist   (f64 sums; order differs)
 //   sky.py:100-191           medfit: block nan-medians, Legendre model, subtraction       -> rip_stage_select_ranks, rip_stage_legendre2d (exact)
 //   gen_cal_image.py:697-712 SLICEOUT endslice                                            -> rip_stage_endslice     (exact)
-// Host arrays in and out (these are per-image calls on planes the caller already holds).
+//   coordutils.py:17-82      pixelarea of a FITS zenithal (+SIP) WCS -> AreaFactor plane  -> rip_stage_pixel_area   (f64)
+// Host arrays in and out (these are per-image calls on planes the caller already holds); the area map may also be written to
+// device memory.
+#include <cmath>
+
 #include "rip_common.h"
 
 namespace {
@@ -218,6 +222,84 @@ __global__ __launch_bounds__(256) void legendre2d_kernel(float *__restrict__ arr
     if (subtract) arr[p] = arr[p] - mf;
 }
 
+// ------------------------------------------------------------------------------------------ pixel area
+// (alpha, delta) in radians of the 0-based pixel coordinate (x, y): SIP, CD, the zenithal projection's native latitude, then
+// the spherical rotation of Calabretta & Greisen (2002) eq. 2 with (alpha_p, delta_p) = CRVAL, phi_p = LONPOLE.
+__device__ void pa_world(const rip_wcs_desc &w, double x, double y, double &alpha, double &delta) {
+    const double deg = M_PI / 180.0;
+    double u = x - w.crpix[0], v = y - w.crpix[1];
+    if (w.sip_order > 0) {
+        double fa = 0.0, fb = 0.0;   // sum over p + q <= order of A_p_q u^p v^q, B likewise (Horner in v, then in u)
+        for (int p = w.sip_order; p >= 0; --p) {
+            double ra = 0.0, rb = 0.0;
+            for (int q = w.sip_order - p; q >= 0; --q) {
+                ra = ra * v + w.sip_a[p][q];
+                rb = rb * v + w.sip_b[p][q];
+            }
+            fa = fa * u + ra;
+            fb = fb * u + rb;
+        }
+        u = u + fa;
+        v = v + fb;
+    }
+    const double X = w.cd[0][0] * u + w.cd[0][1] * v, Y = w.cd[1][0] * u + w.cd[1][1] * v;   // degrees
+    const double R = hypot(X, Y);
+    const double phi = atan2(X, -Y);
+    double theta;
+    switch (w.projection) {
+        case RIP_PROJ_TAN: theta = atan2(180.0 / M_PI, R); break;
+        case RIP_PROJ_STG: theta = M_PI / 2.0 - 2.0 * atan(M_PI * R / 360.0); break;
+        case RIP_PROJ_ZEA: theta = M_PI / 2.0 - 2.0 * asin(M_PI * R / 360.0); break;
+        case RIP_PROJ_ARC: theta = (90.0 - R) * deg; break;
+        default: theta = acos(M_PI * R / 180.0); break;   // RIP_PROJ_SIN
+    }
+    double st, ct, sd, cd, sp, cp;
+    sincos(theta, &st, &ct);
+    sincos(w.crval[1] * deg, &sd, &cd);
+    sincos(phi - w.lonpole * deg, &sp, &cp);
+    delta = asin(st * sd + ct * cd * cp);
+    alpha = w.crval[0] * deg + atan2(-ct * sp, st * cd - ct * sd * cp);
+}
+
+// One workgroup per 32 x 32 output pixels: its threads evaluate the WCS on the tile's grid points plus a one-point halo (34 x 34),
+// keep the equal-area coordinates (U, V) in LDS, then form the central-difference Jacobian of each pixel (coordutils.py:57-81).
+// Grid point (gx, gy) = pixel coordinate; the grid runs from -1 to nx (ny), so every halo point an output needs exists.
+#define PA_T 32
+#define PA_H (PA_T + 2)
+__global__ __launch_bounds__(256) void pixel_area_kernel(const rip_wcs_desc w, int ny, int nx, double scale, double *__restrict__ out) {
+    __shared__ double su[PA_H * PA_H], sv[PA_H * PA_H];
+    __shared__ int north;
+    const int x0 = blockIdx.x * PA_T, y0 = blockIdx.y * PA_T;
+    if (threadIdx.x == 0) {   // the hemisphere of the first grid point picks the pole (coordutils.py:60-62)
+        double a, d;
+        pa_world(w, -1.0, -1.0, a, d);
+        north = d > 0.0 ? 1 : 0;
+    }
+    __syncthreads();
+    const bool n = north != 0;
+    for (int i = threadIdx.x; i < PA_H * PA_H; i += blockDim.x) {
+        const int gx = x0 - 1 + i % PA_H, gy = y0 - 1 + i / PA_H;
+        if (gx > nx || gy > ny) continue;
+        double a, d;
+        pa_world(w, (double)gx, (double)gy, a, d);
+        const double th = n ? M_PI / 2.0 - d : M_PI / 2.0 + d;
+        const double rho = 2.0 * sin(th / 2.0);
+        double sa, ca;
+        sincos(a, &sa, &ca);
+        su[i] = rho * ca;
+        sv[i] = rho * sa;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < PA_T * PA_T; i += blockDim.x) {
+        const int tx = i % PA_T, ty = i / PA_T, x = x0 + tx, y = y0 + ty;
+        if (x >= nx || y >= ny) continue;
+        const int c = (ty + 1) * PA_H + tx + 1;
+        const double J11 = (su[c + 1] - su[c - 1]) / 2.0, J12 = (su[c + PA_H] - su[c - PA_H]) / 2.0;
+        const double J21 = (sv[c + 1] - sv[c - 1]) / 2.0, J22 = (sv[c + PA_H] - sv[c - PA_H]) / 2.0;
+        out[(size_t)y * nx + x] = fabs(J11 * J22 - J21 * J12) / scale;
+    }
+}
+
 }  // namespace
 
 // ============================================================================================ C-ABI
@@ -368,4 +450,36 @@ int rip_stage_legendre2d(rip_ctx *ctx, float *arr, int ny, int nx, int order, co
     if (subtract && (rc = d.download(arr, n))) return rc;
     if (model_out && (rc = mo.download(model_out, n))) return rc;
     return RIP_OK;
+}
+
+int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, double scale, int out_location, double *out) {
+    if (!wcs || !out || ny < 1 || nx < 1 || (out_location != RIP_HOST && out_location != RIP_DEVICE))
+        return rip_fail(ctx, RIP_EINVAL, "pixel_area: bad arguments (ny %d, nx %d, out_location %d)", ny, nx, out_location);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return rip_fail(ctx, RIP_EINVAL, "pixel_area: scale %g is not a positive number", scale);
+    if (wcs->projection < RIP_PROJ_TAN || wcs->projection > RIP_PROJ_SIN)
+        return rip_fail(ctx, RIP_EINVAL, "pixel_area: projection %d is not one of TAN, STG, ZEA, ARC, SIN", wcs->projection);
+    if (wcs->sip_order < 0 || wcs->sip_order > RIP_SIP_MAX_ORDER)
+        return rip_fail(ctx, RIP_EINVAL, "pixel_area: SIP order %d outside 0..%d", wcs->sip_order, RIP_SIP_MAX_ORDER);
+    const double *scalars = &wcs->crpix[0];   // crpix, cd, crval, lonpole: 9 doubles in a row
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(scalars[i])) return rip_fail(ctx, RIP_EINVAL, "pixel_area: non-finite CRPIX, CD, CRVAL or LONPOLE");
+    for (int p = 0; p <= RIP_SIP_MAX_ORDER; ++p)
+        for (int q = 0; q <= RIP_SIP_MAX_ORDER; ++q)
+            if (!std::isfinite(wcs->sip_a[p][q]) || !std::isfinite(wcs->sip_b[p][q]))
+                return rip_fail(ctx, RIP_EINVAL, "pixel_area: non-finite SIP coefficient [%d][%d]", p, q);
+    RIP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)ny * nx;
+    const dim3 grid((nx + PA_T - 1) / PA_T, (ny + PA_T - 1) / PA_T);
+    if (grid.y > 65535) return rip_fail(ctx, RIP_EINVAL, "pixel_area: %d rows is too many", ny);
+    if (out_location == RIP_DEVICE) {
+        hipLaunchKernelGGL(pixel_area_kernel, grid, dim3(256), 0, ctx->stream, *wcs, ny, nx, scale, out);
+        RIP_HIP(ctx, hipGetLastError());
+        return RIP_OK;
+    }
+    DevBuf<double> o(ctx);
+    int rc;
+    if ((rc = o.alloc(n))) return rc;
+    hipLaunchKernelGGL(pixel_area_kernel, grid, dim3(256), 0, ctx->stream, *wcs, ny, nx, scale, o.p);
+    RIP_HIP(ctx, hipGetLastError());
+    return o.download(out, n);
 }

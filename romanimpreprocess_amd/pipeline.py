@@ -244,6 +244,27 @@ class Calibrator:
         out.pixeldq, out.groupdq = pixeldq_out_ptr, groupdq_out_ptr
         self.ctx.calibrate_raw(slot, plan_id, stages, rd, out)
 
+    # ---- pixel-area map ------------------------------------------------------------------
+    def area_factor(self, wcs, ny, nx, device=False):
+        """AreaFactor = pixel solid angle / Omega_ideal (gen_cal_image.py:618-621) of an (ny, nx) frame from a ``FitsWCS``, made on
+        the device (``rip_stage_pixel_area``): a read-only numpy array, or with ``device=True`` a torch tensor in HBM (what
+        ``calibrate_device`` takes as ``area_ptr``).  Cached on the context by WCS digest, shape and place; at most two maps are
+        kept (a host map of a 4096 x 4096 frame is 134 MB)."""
+        from .utils import coordutils
+
+        key = (wcs.digest(), int(ny), int(nx), bool(device))
+        cache = self.ctx.__dict__.setdefault("_area_cache", {})
+        if key in cache:
+            cache[key] = cache.pop(key)   # most recently used last
+            return cache[key]
+        area = coordutils.pixelarea_map(wcs, ny, nx, scale=pars.Omega_ideal, device=device, ctx=self.ctx)
+        if not device:
+            area.flags.writeable = False
+        while len(cache) >= 2:
+            cache.pop(next(iter(cache)))
+        cache[key] = area
+        return area
+
     def pinned_empty(self, shape, dtype):
         """A page-locked numpy array: host buffers the library copies from / to at PCIe rate."""
         return self.ctx.pinned_empty(shape, dtype)
