@@ -432,11 +432,11 @@ int rip_profile_enable(rip_ctx *ctx, int on);
 int rip_profile_read(rip_ctx *ctx, double out_ms[4], int *ncalls);
 
 /* options: "fused" (default 1) -- run the chain as the single fused kernel when the configuration allows it (complete chain on a
-   u16 cube; f32 gain; 4, 9 or 11 Legendre planes; 6, 8 or 16 groups; flag words of the CALDIR set mergeable); 0 forces the
+   u16 cube; f32 gain; 4, 9 or 11 Legendre planes; 5 to 16 groups; flag words of the CALDIR set mergeable); 0 forces the
    stage-by-stage kernels.  Both give identical results. */
 int rip_set_option(rip_ctx *ctx, const char *name, int value);
 /* further options (results identical either way; they exist for A/B timing and tests):
-   "chain2"  -- (default 1) the fused kernel (chain2_kernel.h: f32 or f64 ipc4d with 6, 8 or 16 groups); 0 = the stage kernels
+   "chain2"  -- (default 1) the fused kernel (chain2_kernel.h: f32 or f64 ipc4d with 5 to 16 groups); 0 = the stage kernels
                 (rounds 1-2: a general fused kernel, dropped in round 3);
    "prepass_form" -- how the reference-pixel tables are made: -1 (default) by situation -- a pre-pass that overlaps the previous
                 ramp's fused kernel as the nine small launches of refpix.hip (they slip into that kernel's tail), a pre-pass in
@@ -450,11 +450,17 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
                 power-of-two frame lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise, 0 hipFFT for every length;
    "overlap" -- run the reference-pixel pre-pass of a ramp on a second stream so that it overlaps the previous ramp's
                 fused kernel: -1 (default) by situation -- wherever the fused kernel leaves room on the CUs (every form except the
-                f64-ipc4d one of up to 8 groups, whose partial coefficient ring fills the LDS), 0 never, 1 always. */
+                f64-ipc4d one of 5 to 8 groups, whose partial coefficient ring fills the LDS), 0 never, 1 always. */
 
 /* how the last rip_calibrate ran: 0 = stage kernels, 2 = the fused kernel (1 and 3 were the general and the wave-private fused
    kernels of rounds 1-2) */
 int rip_last_chain_form(rip_ctx *ctx);
+
+/* Is a fused-kernel form compiled for a complete chain with this many Legendre planes, groups and these ipc4d / gain dtypes
+   (RIP_F32 / RIP_F64)?  2 = yes (the value rip_last_chain_form reports), 0 = such a ramp takes the stage kernels.  Needs no
+   context and no GPU.  What it does not know: the plan (a difference mask other than the full one takes the stage kernels), the
+   CALDIR set (flag words that cannot be merged do too), the call (a sub-chain, an f32 cube, "fused" / "chain2" switched off). */
+int rip_chain_form_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype);
 
 /* pseudo-Poisson noise layers ("O" directives, gen_noise_image.py:173-240): per element of I (n doubles, host memory) the
    member of the Pearson family with the moments tilnu_21 I, tilnu_31 I, 3 tilnu_21^2 I^2 + tilnu_41 I, replacing

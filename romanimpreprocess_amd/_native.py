@@ -148,6 +148,7 @@ SYMBOLS = {
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_last_chain_form": (_I, [_VP]),
+    "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
     "rip_profile_enable": (_I, [_VP, _I]),
     "rip_profile_read": (_I, [_VP, C.POINTER(C.c_double), C.POINTER(_I)]),
 }
@@ -183,6 +184,14 @@ def load_library():
                            "invalid by construction); set ROMANHIP_ALLOW_TIMING_BUILD=1 to load it for timing experiments")
     _lib = lib
     return lib
+
+
+def chain_form_for(lin_nplanes, ngroups, ipc_dtype=RIP_F32, gain_dtype=RIP_F32):
+    """2 where the library has a fused-kernel form for a complete chain on a ramp of ``ngroups`` groups with ``lin_nplanes``
+    Legendre planes and these ipc4d / gain dtypes (RIP_F32, RIP_F64), 0 where the stage kernels run.  Needs no GPU.  It does not
+    know the plan or the CALDIR set: a ramp also takes the stage kernels when the plan's differences are not the full set or
+    the set's flag words cannot be merged (``Context.last_chain_form`` tells what a call really ran)."""
+    return int(load_library().rip_chain_form_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype)))
 
 
 def dtype_code(arr):
@@ -224,6 +233,7 @@ class Context:
         self.h = h
         self.device = int(device)
         self._keep = {}
+        self.caldir_dtypes = {}   # slot -> (Legendre planes, ipc4d dtype, gain dtype) of the set uploaded there
 
     def close(self):
         if getattr(self, "h", None):
@@ -345,10 +355,13 @@ class Context:
             if cal["saturation"].get("dq") is not None:
                 d.saturation_dq = P(cal["saturation"]["dq"], np.uint32, c_u32_p)
         self.check(self.lib.rip_caldir_upload(self.h, int(slot), C.byref(d)))
+        # what rip_chain_form_for asks about (Calibrator.chain_form_for)
+        self.caldir_dtypes[int(slot)] = (int(d.lin_nplanes), int(d.ipc_dtype), int(d.gain_dtype))
         return (ny, nx)
 
     def drop_caldir(self, slot):
         self.check(self.lib.rip_caldir_drop(self.h, int(slot)))
+        self.caldir_dtypes.pop(int(slot), None)
 
     # ---- plans -------------------------------------------------------------------------
     def create_plan(self, desc):

@@ -1,25 +1,53 @@
 // Dispatch of the fused chain kernel (chain2_kernel.h): the one list of the configurations it is compiled for.  Each (Legendre
-// order, ipc4d dtype) is one instantiation of rip_launch_chain2 in a translation unit of its own (chain_np*.hip), so that they
-// compile in parallel.
-#include "rip_common.h"
+// order, ipc4d dtype, part of the group-count list) is one instantiation of rip_launch_chain2 in a translation unit of its own
+// (chain_np*.hip, compiled once per part), so that they compile in parallel.
+#include "chain2_form.h"
 
-template <int NP, typename KT>
+template <int NP, typename KT, int PART>
 int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
 
 typedef int (*ChainLauncher)(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
 
-// 4 / 9 / 11 Legendre planes (P_ORDER 3 / 8 / 10), f32 or f64 ipc4d, 6, 8 or 16 groups (C2Form has a form for each); null for
-// everything else (the stage kernels)
+// part of the group-count list (rip_common.h: RIP_CHAIN_G_PART*) that holds G, -1 when the fused kernel has no form for G
+static int chain_part(int G) {
+#define RIP_IN_PART(g) \
+    if (G == g) return part;
+    int part = 0;
+    RIP_CHAIN_G_PART0(RIP_IN_PART)
+    part = 1;
+    RIP_CHAIN_G_PART1(RIP_IN_PART)
+    part = 2;
+    RIP_CHAIN_G_PART2(RIP_IN_PART)
+#undef RIP_IN_PART
+    return -1;
+}
+
+template <int NP, typename KT>
+static ChainLauncher chain_launcher_of(int part) {
+    switch (part) {
+        case 0:
+            return rip_launch_chain2<NP, KT, 0>;
+        case 1:
+            return rip_launch_chain2<NP, KT, 1>;
+        case 2:
+            return rip_launch_chain2<NP, KT, 2>;
+    }
+    return nullptr;
+}
+
+// 4 / 9 / 11 Legendre planes (P_ORDER 3 / 8 / 10), f32 or f64 ipc4d, 5 to 16 groups (C2Form has a form for each even count; an odd
+// count runs the form of the next even one); null for everything else (the stage kernels)
 static ChainLauncher chain_launcher(int nplanes, int G, int k_dtype) {
-    if (G != 6 && G != 8 && G != 16) return nullptr;
+    const int part = chain_part(G);
+    if (part < 0 || (k_dtype != RIP_F32 && k_dtype != RIP_F64)) return nullptr;
     const bool k64 = k_dtype == RIP_F64;
     switch (nplanes) {
         case 4:
-            return k64 ? rip_launch_chain2<4, double> : rip_launch_chain2<4, float>;
+            return k64 ? chain_launcher_of<4, double>(part) : chain_launcher_of<4, float>(part);
         case 9:
-            return k64 ? rip_launch_chain2<9, double> : rip_launch_chain2<9, float>;
+            return k64 ? chain_launcher_of<9, double>(part) : chain_launcher_of<9, float>(part);
         case 11:
-            return k64 ? rip_launch_chain2<11, double> : rip_launch_chain2<11, float>;
+            return k64 ? chain_launcher_of<11, double>(part) : chain_launcher_of<11, float>(part);
     }
     return nullptr;
 }
@@ -30,9 +58,34 @@ bool rip_chain_supported(const rip_ctx *ctx, int nplanes, int G, int k_dtype, in
     return gain_dtype == RIP_F32 && chain_launcher(nplanes, G, k_dtype);
 }
 
-// The f64-ipc4d form of up to 8 groups (C2Form, narrow = 1) fills the 160 KB of LDS of every CU with its partial K ring: the
-// pre-pass of the next ramp finds no room beside it.  (Also true for the f64 group counts below 8 that have no fused form.)
-bool rip_chain_fills_lds(int G, int k_dtype) { return k_dtype == RIP_F64 && G <= 8; }
+// Context-free form of the same question for callers (include/romanhip.h): 2 = a fused form is compiled for this configuration,
+// 0 = the stage kernels run
+int rip_chain_form_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype) {
+    return rip_chain_supported(nullptr, lin_nplanes, ngroups, ipc_dtype, gain_dtype) ? 2 : 0;
+}
+
+// Does the fused form of this ramp fill the LDS of every CU, so that the pre-pass of the next ramp finds no room beside it?  From
+// the form table: true for the form family whose K ring grows into what the rest of the layout leaves of the 160 KB (narrow = 1:
+// f64 ipc4d with 5 to 8 groups).  That the pre-pass does better in front of its own ramp there was measured at f64 x 8 groups
+// (profiles/r04_summary.md); 5, 6 and 7 groups inherit it with the form.  The family is the criterion, not a byte count: its
+// forms leave under 7 KB, every other form at least 10 KB (asserted below, so that a layout change that moves a form across
+// comes to notice).  Group counts WITHOUT a fused form keep the answer they always had (f64 ipc4d and up to 8 groups: true), so
+// that the stage-kernel path of those ramps is scheduled exactly as before.
+template <int GE, bool K64>
+static constexpr bool c2_fills_lds() {
+    using F = C2Form<GE, K64>;
+    static_assert((F::narrow == 1) == (160 * 1024 - F::lds_bytes < 7 * 1024), "the K-ring forms, and only they, fill the LDS");
+    return F::narrow == 1;
+}
+bool rip_chain_fills_lds(int G, int k_dtype) {
+    if (chain_part(G) < 0 || (k_dtype != RIP_F32 && k_dtype != RIP_F64)) return k_dtype == RIP_F64 && G <= 8;
+    const bool k64 = k_dtype == RIP_F64;
+#define RIP_FILLS(g) \
+    if (G == g) return k64 ? c2_fills_lds<g + (g & 1), true>() : c2_fills_lds<g + (g & 1), false>();
+    RIP_CHAIN_G_ALL(RIP_FILLS)
+#undef RIP_FILLS
+    return false;
+}
 
 // returns the launch status, or 1 when no fused kernel fits this plan / CALDIR set (the caller then takes the stage kernels)
 int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype) {

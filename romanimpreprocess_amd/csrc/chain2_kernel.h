@@ -1,4 +1,4 @@
-// The fused L1->L2 kernel (f32 gain; f32 or f64 ipc4d; 6, 8 or 16 groups), wave-specialised: one launch per
+// The fused L1->L2 kernel (f32 gain; f32 or f64 ipc4d; 5 to 16 groups), wave-specialised: one launch per
 // ramp does reference-pixel apply + bias + Legendre linearity + IPC deconvolution + ramp fit / jump detection / flag propagation
 // + dark rate + error split + flat (gen_cal_image.py:533-629; stage arithmetic and reference lines as in linearity.hip, ipc.hip,
 // rampfit.hip), every array read from HBM once.
@@ -25,6 +25,7 @@
 // refitted from registers (trunc_layers), so no per-pixel ramp staging in LDS.
 #pragma once
 #include "chain_common.h"
+#include "chain2_form.h"
 
 // Diagnostic builds only (RIP_TIMING_BUILD: rip_version() then reports a timing build and the Python binding refuses the library
 // unless told otherwise): -DC2_DBG switches phases off by ChainArgs::dbg (results invalid by construction), -DCH_STAMP records
@@ -134,8 +135,9 @@ __device__ __forceinline__ void c2_ipc9_batch(const VT (&v)[NBB][9], const doubl
 // scales nothing and v_div_fixup has nothing to fix -- which holds for 2^-60 < |b| < 2^60 and every quotient (rounded to f32)
 // finite, non-zero and within 2^-59 .. 2^59 (then 2^-119 < |a| < 2^119: far from every scaling rule of the instruction).  One
 // wave vote checks that; otherwise every lane takes the division operator.
-template <int NG>
-__device__ __forceinline__ void c2_div64_shared(const double (&a)[NG], float bf, bool use, float (&qf)[NG]) {
+template <int NG, int NA>
+__device__ __forceinline__ void c2_div64_shared(const double (&a)[NA], float bf, bool use, float (&qf)[NA]) {
+    static_assert(NA >= NG, "the first NG of NA values are divided");
     const double b = (double)bf;
     double y = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, y, 1.0);
@@ -158,94 +160,22 @@ __device__ __forceinline__ void c2_div64_shared(const double (&a)[NG], float bf,
     }
 }
 
-// The forms of the kernel, one per (group count, ipc4d dtype), and every choice that differs between them.  What does not fit the
-// 256-column form's LDS twice per CU runs a NARROW form: one wide workgroup per CU that drops rings, and what a dropped ring
-// carried the fit role loads itself, one step ahead (a second read of lines the ingest role fetched 1.5 steps earlier):
-//   ipc4d  groups  narrow  columns  waves/SIMD  rings
-//   f32    6, 8    0       256      4           every ring, two workgroups per CU (the bench path)
-//   f64    6, 8    1       384      3           a PARTIAL K ring (krn; every ring at 256 columns: 120 KB, one workgroup per CU)
-//   f32    16      2       384      3           no K ring, no gain / groupdq rings
-//   f64    16      2       256      2           no K ring, no gain / groupdq rings
-// Round 3 ran the narrow forms as 128-column workgroups, three (two) per CU: 3 (2) waves per SIMD at <= 168 (256) VGPRs.  What they
-// paid is windows at a 124-column pitch: a window row of a byte plane is one 128-byte line, misaligned it touches two (u16: two ->
-// three, f32: four -> five), and the lines shared with the neighbouring strip have left L2 by the time that strip wants them -- a
-// third of the algorithmic bytes fetched twice.  Round 4: ONE workgroup per CU of 384 columns (f64 x 16 groups: 256) -- the same
-// waves per SIMD and LDS per CU, a third (half) of the seams: 6-8 % faster, same bits.  Same arithmetic as the 256-column form,
-// which keeps 256 columns (128-column workgroups WITH every ring: 4 % slower, profiles/r03_summary.md; the narrow forms are slower
-// there too: same 16 waves per CU).
-// The half-step barrier falls after the first half of the fit in every form.  Same-box A/B of its place -- there / after the second
-// half of the fit and the saturated refits / after the flag propagation and the group-flag stores: f32 ipc4d x 8 groups 0.884 /
-// 0.887 / 0.895 ms (profiles/r03_summary.md); the wide narrow forms (round 4) 16 groups 1.704 / 1.770 / 1.751 ms per ramp, f64 x 16
-// groups 2.251 / 2.278 / 2.302, f64 x 8 groups 1.138 / 1.145 / 1.153.
-template <int G, bool K64>
-struct C2Form {
-    static constexpr int narrow = G > 8 ? 2 : (K64 ? 1 : 0);
-    // columns of a workgroup's window, and its threads (two roles of one thread per column)
-    static constexpr int cols = (narrow == 0 || (narrow == 2 && K64)) ? 256 : 384;
-    static constexpr int threads = 2 * cols;
-    // Strip geometry: the window of strip s starts at column s * outw; its lanes 2 .. cols-3 emit, lanes 0, 1 and cols-2, cols-1
-    // are the halo of the two 3 x 3 passes -- except at the frame's edge, where columns 0, 1 and nx-2, nx-1 are emitted by those
-    // lanes themselves (border pixels: no IPC, no neighbours needed; nb >= 2).  So n strips cover n * outw + 4 columns: 33 strips
-    // of 128 columns cover 4096 exactly (34 with a uniform 2-column offset), 17 of 256.
-    static constexpr int outw = cols - 4;
-    static constexpr int nstrips(int nx) { return (nx - 4 + outw - 1) / outw < 1 ? 1 : (nx - 4 + outw - 1) / outw; }
-    // waves per SIMD it is compiled for (register budget 512 / waves: 128, 168, 256 VGPRs) and launched with
-    static constexpr int wps = narrow == 0 ? 4 : ((narrow == 2 && K64) ? 2 : 3);
-
-    // The LDS layout, byte offsets; the ring slots of a row are `cols` columns wide:
-    static constexpr int ks = K64 ? 8 : 4;                               // bytes of a coefficient and of an O1 value
-    static constexpr int x_ofs = 0;                                      // [G/2][3] f2: x = gain*phi, pair-interleaved
-    static constexpr int o1_ofs = x_ofs + G / 2 * 3 * cols * 8;          // [G/2][3] f2 (f64 ipc4d: [G][3] double): first iterate
-    static constexpr int dq_ofs = o1_ofs + G * 3 * cols * ks;            // [3] u32: the flag word of the pixel
-    // the packed groupdq bytes and the gain of the pixel travel from the ingest thread of a column to its fit thread too --
-    // except in the 16-group forms, whose fit role loads them itself, like the coefficients
-    static constexpr bool wring = narrow < 2;
-    static constexpr int qs_ofs = dq_ofs + 3 * cols * 4;                          // [3][(G+3)/4] u32: groupdq bytes, packed
-    static constexpr int gn_ofs = qs_ofs + (wring ? 3 * ((G + 3) / 4) * cols * 4 : 0);  // [3] f32: gain
-    static constexpr int nlc = cols / RIP_CW + 1;                                 // channels a window can touch (not channel-aligned)
-    static constexpr int ln_ofs = gn_ofs + (wring ? 3 * cols * 4 : 0);            // [nlc][G][2] double: channel lines of this strip
-    static constexpr int kr_ofs = ln_ofs + nlc * G * 2 * 8;                       // [2][krn] KT: the K ring
-    // Coefficients the K ring holds: all nine, or what the rest of the layout leaves of the 160 KB of a CU.  That cap matters at
-    // f64 ipc4d x 8 groups (129.5 KB at 384 columns): the first five of the nine f64 coefficients travel from the ingest thread to
-    // the fit thread through LDS, the fit role reads only the other four planes a second time -- 32 instead of 72 bytes per pixel of
-    // re-read (traffic 1.33 -> 1.18 x), five loads fewer per step in flight in the fit role.  The 16-group forms have no K ring.
-    static constexpr int krn_room = (160 * 1024 - kr_ofs) / (2 * cols * ks);
-    static constexpr int krn = narrow == 2 ? 0 : (krn_room < 9 ? krn_room : 9);
-    static constexpr int lds_bytes = kr_ofs + 2 * krn * cols * ks;
-    static_assert(lds_bytes <= (narrow == 0 ? 80 : 160) * 1024, "the 256-column form runs two workgroups per CU, the others one");
-
-    // Cache policy of the ONCE-read arrays (aux bits of the buffer loads; 2 = nt: stream through the caches).  The narrow forms' fit
-    // role reads the IPC coefficients (16 groups: gain and groupdq bytes too) a second time one row step after the ingest role; a
-    // step of an XCD's 96 workgroups moves about 4 MB -- the size of its L2 -- so those lines have left L2 by then and come back
-    // over the fabric (1.4-1.5 x the algorithmic bytes at ~5 TB/s of fabric traffic).  With the hint on everything read once,
-    // same-box A/B (profiles/r04_summary.md): 16 groups 1.752 -> 1.730 / 1.780 -> 1.738 ms, f64 x 16 groups 2.414 -> 2.383 / 2.411 ->
-    // 2.399 ms, f64 x 8 groups 1.179 -> 1.237 ms SLOWER -- so it is on for the 16-group forms only.  Results are identical either
-    // way.  (256-column form, round 1: hints on the once-read arrays cost 11 %: no second read there.)
-    static constexpr int stream_aux = narrow == 2 ? 2 : 0;
-    // pairs per block of the linearity phase (their recurrences interleave): 2 at 128 and 168 registers; by same-box A/B at the
-    // 16-group forms (profiles/r04_ab_runs.txt): at 168 registers 1 (1.697 against 1.710 ms; 4 spills: 3.46), f64 ipc4d at 256
-    // registers 4 (2.24 against 2.27)
-    static constexpr int pb = narrow == 2 ? (K64 ? 4 : 1) : ((G / 2) % 2 == 0 ? 2 : 1);
-    // f64 ipc4d: pairs the first iterate evaluates in lockstep -- two at 256 registers (f64 x 16 groups: 2.23 / 2.25 ms for 2 / 1),
-    // one at 168
-    static constexpr int pbc = wps == 2 ? 2 : 1;
-    // f64 ipc4d: groups the second iterate evaluates in lockstep (16 groups: 256 registers, four)
-    static constexpr int nbo = G > 8 ? 4 : 2;
-};
-
 template <int NP, int G, int START, typename KT>
-__global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, sizeof(KT) == 8>::wps)) void chain2_kernel(
+__global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C2Form<G + (G & 1), sizeof(KT) == 8>::wps)) void chain2_kernel(
     ChainArgs a, const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars, const float *__restrict__ kvals,
     const RipDiff *__restrict__ diffs, double guard) {
-    static_assert(G % 2 == 0 && G > 4 && G <= 16, "pairs of groups; the groupdq bytes travel packed four to a word");
-    using F = C2Form<G, sizeof(KT) == 8>;
+    static_assert(G > 4 && G <= 16, "pairs of groups; the groupdq bytes travel packed four to a word");
+    // odd G: GE = G + 1 register / ring slots, the last one DEAD (see the note above C2Form); g < G guards are compile-time
+    constexpr int GE = G + (G & 1);
+    using F = C2Form<GE, sizeof(KT) == 8>;
     constexpr int COLS = F::cols;
     constexpr int KRN = F::krn;
     // narrow forms: the fit role requests the coefficients the K ring does not carry itself (k >= KRN: none at f64 ipc4d x 6
     // groups, where the partial ring has room for all nine)
     constexpr bool KFIT = F::narrow > 0;
     constexpr int QW = (G + 3) / 4;  // words of packed group flags per pixel
-    constexpr int GP = G / 2;
+    constexpr int GP = GE / 2;
+    static_assert(QW == (GE + 3) / 4, "the padded count packs into the same flag words");
     // f64 ipc4d (KT = double; the reference's production writer stores f64): x = gain*phi stays f32, the Neumann iterates and
     // the division by the gain are f64 (numpy promotion, ipc_linearity.py:95-142), so the O1 ring holds doubles, one plane per
     // group
@@ -428,7 +358,7 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
     if (!fit_role) {
         // =========================================================================== ingest waves
         // plane p of the calibration slab at row yl: scalar offset p*pl4 + yl*row4; groups likewise in their arrays
-        auto fetch_groups = [&](const RIP_K ChainArgs *ka, int y, int g0, int g1, RowRegs<NP, G> &rr) {
+        auto fetch_groups = [&](const RIP_K ChainArgs *ka, int y, int g0, int g1, RowRegs<NP, GE> &rr) {
             if ((dbg & 64) && y > R0 - 2) return;   // timing experiment: every row works on the first row's (valid) values
             __builtin_amdgcn_sched_barrier(0);
             const unsigned yl = (unsigned)min(max(y, ylo), yhi);
@@ -438,6 +368,9 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
                      o1 = yl * (row4 >> 2) + (unsigned)g0 * npix;
 #pragma unroll
             for (int g = g0; g < g1; ++g) {
+                if constexpr (GE > G) {
+                    if (g >= G) continue;   // the dead half of an odd ramp's last pair is never loaded
+                }
                 rr.S[g] = c2_ld_u16<SA>(rs, cc2, o2);
                 rr.q[g] = c2_ld_u8<F::wring ? SA : 0>(rq, cc1, o1);   // (16 groups: the fit role reads these bytes again)
                 rr.dk[g] = c2_ld_f32<SA>(rd, cc4, o4);
@@ -449,7 +382,7 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
             __builtin_amdgcn_sched_barrier(0);
         };
         // planes i0..i1-1 of [cf[0..NP-1], Smin, Smax, Sref, dq, gain]
-        auto fetch_coefs = [&](const RIP_K ChainArgs *ka, int y, int i0, int i1, RowRegs<NP, G> &rr) {
+        auto fetch_coefs = [&](const RIP_K ChainArgs *ka, int y, int i0, int i1, RowRegs<NP, GE> &rr) {
             if ((dbg & 64) && y > R0 - 2) return;
             __builtin_amdgcn_sched_barrier(0);
             const unsigned yl = (unsigned)min(max(y, ylo), yhi);
@@ -473,14 +406,15 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-        auto fetch_row = [&](int y, RowRegs<NP, G> &rr) {  // prologue: the whole first row at once
+        auto fetch_row = [&](int y, RowRegs<NP, GE> &rr) {  // prologue: the whole first row at once
             const RIP_K ChainArgs *ka = &kargs->a;
             fetch_coefs(ka, y, 0, NP + 5, rr);
             fetch_groups(ka, y, 0, G, rr);
         };
         constexpr int NCO = NP + 5;                 // coefficient-type planes per pixel
         constexpr int CO_STEP = (NCO + GP - 1) / GP;  // issued per pair of C
-        RowRegs<NP, G> rr;
+        RowRegs<NP, GE> rr;
+        if constexpr (GE > G) rr.S[G] = rr.q[G] = 0u, rr.dk[G] = rr.bs[G] = 0.0f;
         fetch_row(R0 - 2, rr);
         int so_c = (R0 - 5 + 2 + 3000) % 3;  // O1 ring slot of row yc = r + 2
         double rcn[G];  // row corrections of the row the next step ingests
@@ -536,6 +470,12 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
 #pragma unroll
                         for (int e = 0; e < 2; ++e) {
                             const int g = 2 * p + e;
+                            if constexpr (GE > G) {
+                                if (g >= G) {   // dead half: a copy of its partner (same z: no exception of its own), zeroed below
+                                    Sv[e] = Sv[0];
+                                    continue;
+                                }
+                            }
                             float S = (float)rr.S[g];
                             const float dk = rr.dk[g];
                             float v = S - dk;
@@ -638,6 +578,12 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
 #pragma unroll
                         for (int e = 0; e < 2; ++e) {
                             const int g = 2 * p + e;
+                            if constexpr (GE > G) {
+                                if (g >= G) {   // dead half: zero in the ring, no flag
+                                    vout[e] = 0.0f;
+                                    continue;
+                                }
+                            }
                             vout[e] = ((dq & bad) == 0) ? (e ? phi[b].y : phi[b].x) : (e ? fb.y : fb.x);
                             const bool first = (g == 0) && a.do_not_flag_first;
                             const uint32_t qg = w[g / 4] >> (8 * (g & 3));
@@ -645,6 +591,9 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
                         }
                         f2 xv = {vout[0], vout[1]};
                         if (act) xv = xv * rr.gain;
+                        if constexpr (GE > G) {
+                            if (2 * p + 1 >= G) xv.y = 0.0f;
+                        }
                         xs[p * XR * COLS] = col_ok ? xv : f2{0.0f, 0.0f};
                     }
                 } else if (do_a) {
@@ -800,7 +749,7 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
             // flat / dark_dq == null: read the first slab plane instead (value unused), keeps the loads in one block
             const float e_flat_raw = c2_ld_f32<SA>(c2_rsrc(kf->a.flat ? (const void *)kf->a.flat : (const void *)kf->a.planes), cc4, t_ld);
             const float e_flat = kf->a.flat ? e_flat_raw : 1.0f;
-            float d[G];
+            float d[GE];
             f2 dpair[GP];
             uint32_t qw[QW];  // the pixel's groupdq bytes, packed
 #pragma unroll
@@ -855,9 +804,9 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
                     // lockstep (their ring reads, then interleaved chains), the divisions together at the end.  Lanes that are not
                     // active (border pixels) evaluate on whatever the rings hold there and keep x.
                     constexpr int NBO = F::nbo;
-                    double o2v[G];
+                    double o2v[GE];
 #pragma unroll
-                    for (int gb = 0; gb < G; gb += NBO) {
+                    for (int gb = 0; gb < GE; gb += NBO) {
                         double v[NBO][9];
 #pragma unroll
                         for (int b = 0; b < NBO; ++b) {
@@ -877,10 +826,11 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
                             o2v[gb + b] = (v[b][0] + (double)xc) - f[b];
                         }
                     }
-                    float qf[G];
-                    c2_div64_shared<G>(o2v, e_gain, act, qf);
+                    float qf[GE];
+                    if constexpr (GE > G) qf[G] = 0.0f;
+                    c2_div64_shared<G>(o2v, e_gain, act, qf);   // (the dead half takes no part in its range vote)
 #pragma unroll
-                    for (int g = 0; g < G; ++g) {
+                    for (int g = 0; g < GE; ++g) {
                         const float xc = (g & 1) ? xnext[g / 2].y : xnext[g / 2].x;
                         d[g] = act ? qf[g] : xc;
                     }
@@ -949,6 +899,8 @@ __global__ __launch_bounds__((C2Form<G, sizeof(KT) == 8>::threads), (C2Form<G, s
                         }
                     }
                 }
+                // odd G: whatever the pair arithmetic left in the dead half (0 / gain), the fit sees a zero there
+                if constexpr (GE > G) d[G] = 0.0f, dpair[GP - 1].y = 0.0f;
                 // first half of the ramp fit (registers only): slope, errors, approximate jump significances
                 const bool unsat = ((qw[(G - 1) / 4] >> (8 * ((G - 1) & 3))) & DQ_SATURATED) == 0;
                 if (!(dbg & 4))
@@ -1136,7 +1088,7 @@ static inline long chain2_geometry(ChainArgs &a, int nstrips, int live_last, int
 
 template <int NP, int G, int START, typename KT>
 static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
-    using F = C2Form<G, sizeof(KT) == 8>;
+    using F = C2Form<G + (G & 1), sizeof(KT) == 8>;
     const size_t lds = F::lds_bytes;
     const int ncu = ctx->ncu;
     int per_cu = (int)((160 * 1024) / lds);
@@ -1161,7 +1113,9 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
     return RIP_OK;
 }
 
-// returns the launch status, or 1 when the plan is not one the specialised kernel was compiled for
+// returns the launch status, or 1 when the plan is not one the specialised kernel was compiled for: the dense table the kernel
+// reads (api.hip builds it from the plan's differences) must test exactly the differences of the compile-time mask -- for odd G
+// too, where no tested difference may touch the dead half of the last pair
 template <int NP, int G, typename KT>
 static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
     if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return launch_chain2_s<NP, G, 0, KT>(ctx, plan, a);
@@ -1169,18 +1123,21 @@ static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) 
     return 1;
 }
 
-// The fused kernel for NP Legendre planes and ipc4d coefficients of type KT, every group count it has a form for; chain.hip calls
-// it for the configurations it lists, chain_np*.hip instantiate it.  Returns the launch status, or 1 when no instantiation fits
-// (the caller then takes the stage kernels).
-template <int NP, typename KT>
+// The fused kernel for NP Legendre planes and ipc4d coefficients of type KT, the group counts of part PART of the list
+// (rip_common.h: RIP_CHAIN_G_PART*); chain.hip calls it for the configurations it lists, chain_np*.hip instantiate it.  Returns
+// the launch status, or 1 when no instantiation fits (the caller then takes the stage kernels).
+template <int NP, typename KT, int PART>
 int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
-    switch (a.ngrp) {
-        case 6:
-            return launch_chain2<NP, 6, KT>(ctx, plan, a);
-        case 8:
-            return launch_chain2<NP, 8, KT>(ctx, plan, a);
-        case 16:
-            return launch_chain2<NP, 16, KT>(ctx, plan, a);
+    static_assert(PART >= 0 && PART <= 2, "parts of RIP_CHAIN_G_ALL");
+#define C2_CASE(g) \
+    if (a.ngrp == g) return launch_chain2<NP, g, KT>(ctx, plan, a);
+    if constexpr (PART == 0) {
+        RIP_CHAIN_G_PART0(C2_CASE)
+    } else if constexpr (PART == 1) {
+        RIP_CHAIN_G_PART1(C2_CASE)
+    } else {
+        RIP_CHAIN_G_PART2(C2_CASE)
     }
+#undef C2_CASE
     return 1;
 }

@@ -1,4 +1,7 @@
 // The fused kernel for 4 Legendre planes and f64 ipc4d coefficients (chain2_kernel.h; dispatch: chain.hip).
 #include "chain2_kernel.h"
 
-template int rip_launch_chain2<4, double>(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
+#ifndef C2_PART
+#error "compiled once per part of the group-count list: -DC2_PART=0, 1, 2 (Makefile)"
+#endif
+template int rip_launch_chain2<4, double, C2_PART>(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);

@@ -389,11 +389,11 @@ struct RipDenseK {
 // VALID != 0: the tested differences are known at compile time (no plan-uniform branches: the eight difference
 // slots become one basic block the scheduler can interleave)
 template <int G, uint32_t VALID, typename TAB>
-__device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[G / 2], const RipFitConst fc, const RipVariant v,
+__device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
                                                 const TAB tabsrc, float gain, float rn, bool flag, double guard,
                                                 RipFitState &st) {
-    constexpr int GP = G / 2;
-    constexpr int NS = 2 * GP;  // pair slots
+    constexpr int GP = (G + 1) / 2;  // odd G: the second half of the last pair is dead (no weight, no tested difference)
+    constexpr int NS = 2 * GP;       // pair slots
     // scalar loads of the weights and of the first difference slot are issued before the slope arithmetic; slot
     // ps+1 is requested while slot ps is evaluated (scalar loads return out of order: every wait is lgkmcnt(0))
     float k2[G];
@@ -408,6 +408,13 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[G / 2], const Ri
 #pragma unroll
     for (int p = 0; p < GP; ++p) {
         const rf2 diff = dA[p] - d11;
+        if constexpr (G & 1) {   // the dead half of the last pair has no weight and adds nothing (not even a signed zero)
+            if (2 * p + 1 >= G) {
+                const float prod = k2[2 * p] * diff.x;
+                s = s + prod;
+                continue;
+            }
+        }
         const rf2 kk = {k2[2 * p], k2[2 * p + 1]};
         const rf2 prod = kk * diff;
         s = s + prod.x;
@@ -494,7 +501,7 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[G / 2], const Ri
 }
 
 template <int G, uint32_t VALID = 0u>
-__device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[G / 2], const RipFitConst fc, const RipVariant v,
+__device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
                                               const RipDense *__restrict__ dn, float gain, float rn, bool flag,
                                               double guard, RipFitState &st) {
     fit_full_pk_a_t<G, VALID, RipDenseK>(dA, fc, v, RipDenseK{dn}, gain, rn, flag, guard, st);
@@ -502,11 +509,11 @@ __device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[G / 2], const RipF
 
 // second half: exact re-evaluation where the approximate significance was not decisive, jump mask
 template <int G>
-__device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[G / 2], const RipPlanHeader *__restrict__ h,
+__device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[(G + 1) / 2], const RipPlanHeader *__restrict__ h,
                                               const RipFitConst fc, const RipDense *__restrict__ dn,
                                               const float *__restrict__ kv, const RipDiff *__restrict__ df, bool flag,
                                               const RipFitState &st, uint32_t &jmask) {
-    constexpr int GP = G / 2;
+    constexpr int GP = (G + 1) / 2;
     if (!st.live) return;
     const float s = st.s, dv = st.dv, s2 = st.s2, xc = st.xc;
     uint32_t jfast = st.jfast;
@@ -547,7 +554,7 @@ __device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[G / 2], const RipP
 }
 
 template <int G>
-__device__ __forceinline__ void fit_full_pk(const rf2 (&dA)[G / 2], const RipPlanHeader *__restrict__ h,
+__device__ __forceinline__ void fit_full_pk(const rf2 (&dA)[(G + 1) / 2], const RipPlanHeader *__restrict__ h,
                                             const RipFitConst fc, const RipVariant v, const RipDense *__restrict__ dn,
                                             const float *__restrict__ kv, const RipDiff *__restrict__ df, float gain,
                                             float rn, bool flag, double guard, float &s_out, float &er_out,
@@ -562,11 +569,11 @@ __device__ __forceinline__ void fit_full_pk(const rf2 (&dA)[G / 2], const RipPla
 
 // ---------------------------------------------------------------------------------------------
 // Saturation-truncated refits (fitting.py:326-337) with the ramp in registers: compile-time recursion over the
-// truncation length GV = G-1 ... 3.  A layer is evaluated only when some lane of the wave first saturates at
+// truncation length GV = G-1 ... 3 (d may be longer than G: the fused kernel pads an odd ramp to whole pairs).  A layer is evaluated only when some lane of the wave first saturates at
 // group GV (wave-uniform test); results and jump flags replace the running ones for those lanes, in the
 // reference's order (descending GV).
-template <int G, int GV>
-__device__ __forceinline__ void trunc_layers(const float (&d)[G], const uint32_t (&qe)[G],
+template <int G, int GV, int GA>
+__device__ __forceinline__ void trunc_layers(const float (&d)[GA], const uint32_t (&qe)[G],
                                              const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars,
                                              const float *__restrict__ kvals, const RipDiff *__restrict__ diffs,
                                              float gain, float rn, bool act, double guard, float &s, float &er,

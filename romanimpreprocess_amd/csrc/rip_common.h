@@ -297,6 +297,13 @@ struct ChainArgs {
     // whose four wave columns each march down their OWN range of geo_rows_q rows of that strip (0: every strip alike)
     int geo_nr, geo_rows, geo_nq, geo_rows_q;
 };
+// THE list of the group counts the fused kernel has a form for, in the parts its instantiations are compiled in (one translation
+// unit per part, Legendre order and ipc4d dtype: chain_np*.hip with -DC2_PART).  The launch switch (chain2_kernel.h), the
+// dispatch table, rip_chain_supported and rip_chain_form_for (chain.hip) are all expanded from it.
+#define RIP_CHAIN_G_PART0(X) X(5) X(6) X(7) X(8)
+#define RIP_CHAIN_G_PART1(X) X(9) X(10) X(11) X(12)
+#define RIP_CHAIN_G_PART2(X) X(13) X(14) X(15) X(16)
+#define RIP_CHAIN_G_ALL(X) RIP_CHAIN_G_PART0(X) RIP_CHAIN_G_PART1(X) RIP_CHAIN_G_PART2(X)
 bool rip_chain_supported(const rip_ctx *ctx, int nplanes, int G, int k_dtype, int gain_dtype);
 bool rip_chain_fills_lds(int G, int k_dtype);   // the pre-pass of the next ramp cannot run beside the fused kernel
 int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype);

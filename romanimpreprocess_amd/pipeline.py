@@ -79,6 +79,15 @@ class Calibrator:
     def slot_owner(self, slot):
         return self.ctx.__dict__.get("_caldir_owner", {}).get(slot)
 
+    def chain_form_for(self, slot, ngroups):
+        """2 where a ramp of ``ngroups`` groups on the CALDIR set of ``slot`` has a fused-kernel form (Legendre order, ipc4d and
+        gain dtypes of the set as uploaded), 0 where it takes the stage kernels.  The limits of ``_native.chain_form_for``
+        apply: the plan's difference mask and the set's flag words are not looked at."""
+        if int(slot) not in self.ctx.caldir_dtypes:
+            raise ValueError(f"chain_form_for: no CALDIR set is loaded in slot {slot}")
+        nplanes, ipc_dtype, gain_dtype = self.ctx.caldir_dtypes[int(slot)]
+        return _native.chain_form_for(nplanes, ngroups, ipc_dtype, gain_dtype)
+
     # ---- plans ----------------------------------------------------------------------------
     def plan_for(self, read_pattern, frame_time, exclude_first=True, ramp_opt_pars=None, jump_pars=None):
         """(plan id, meta) for an MA table; cached per configuration."""

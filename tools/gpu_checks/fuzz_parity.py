@@ -18,7 +18,10 @@ ctx = _native.default_context(0)
 cb = pipeline.Calibrator(ctx=ctx)
 
 
-def random_pattern():
+def random_pattern(gmin=3, gmax=16):
+    """one case in five each: the 8-, 6- and 16-group patterns of the tests; otherwise gmin..gmax groups of 1..4 reads.  The fused
+    kernel has a form for every count from 5 to 16, odd ones included; the default draw keeps 3 and 4 groups as well, so that the
+    stage kernels of the shortest ramps stay in the sweep (the multi-strip tenth of the cases draws 5..16 only)"""
     kind = rng.integers(0, 5)
     if kind == 0:
         return synth.READ_PATTERN_8
@@ -26,7 +29,7 @@ def random_pattern():
         return synth.READ_PATTERN_6
     if kind == 2:
         return synth.READ_PATTERN_16
-    g = int(rng.integers(3, 13))
+    g = int(rng.integers(gmin, gmax + 1))
     rp, t = [], 0
     for _ in range(g):
         n = int(rng.integers(1, 5))
@@ -45,14 +48,15 @@ def same(a, b, zero_sign_ok=False):
 
 
 fails, forms = 0, {0: 0, 1: 0, 2: 0, 3: 0}
+by_groups = {}   # group count -> [cases, of them on the fused kernel]
 t0 = time.time()
 for case in range(ncases):
     rp = random_pattern()
     ny, nx = int(rng.integers(4, 13)) * 8, int(rng.choice([128, 256, 384]))
     if rng.random() < 0.1:
         # a tenth of the cases: frames of several strips and row ranges (up to 9 strips of the narrow forms, ranges that do
-        # not divide the rows), with a read pattern the fused kernel is instantiated for
-        rp = [synth.READ_PATTERN_8, synth.READ_PATTERN_6, synth.READ_PATTERN_16][int(rng.integers(0, 3))]
+        # not divide the rows), with a group count the fused kernel is instantiated for
+        rp = random_pattern(5, 16)
         ny, nx = int(rng.integers(13, 76)) * 4, int(rng.choice([512, 640, 1024]))
     p = int(rng.choice([3, 8, 10]))
     gdt = np.float64 if rng.random() < 0.2 else np.float32
@@ -97,6 +101,9 @@ for case in range(ncases):
     dev_ramp = dict(ramp, groupdq=None, pixeldq=mask_dq) if sat else ramp
     got = cb.calibrate(1, dev_ramp, exclude_first=excl, jump_pars=jump, want_cube=True, channel_lines=lines, **sat_kw)
     forms[ctx.last_chain_form()] += 1
+    tally = by_groups.setdefault(len(rp), [0, 0])
+    tally[0] += 1
+    tally[1] += ctx.last_chain_form() == 2
     ok = (same(got["cube"], ref["data"], True) and same(got["groupdq"], ref["groupdq"]) and same(got["pixeldq"], ref["pixeldq"])
           and all(same(got[k], ref[k], True) for k in ("slope", "err_read", "err_poisson")))
     if not ok:
@@ -108,4 +115,5 @@ for case in range(ncases):
 ctx.set_option("fused", 1)
 ctx.set_option("chain2", 1)
 print(f"done: {ncases} cases, {fails} mismatches; kernel forms used (0 stage kernels, 2 fused kernel): {forms}")
+print("groups: cases / on the fused kernel --", ", ".join(f"{g}: {n} / {f}" for g, (n, f) in sorted(by_groups.items())))
 sys.exit(1 if fails else 0)
