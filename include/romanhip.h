@@ -444,7 +444,7 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
                 it covers the frame (up to 4096 rows, a reference output); 0 = refpix.hip always; 1 = refpix_one.hip wherever
                 it covers the frame;
    "chain_reserve" -- (default 8) workgroup slots the 256-column fused kernel's grid leaves free; "chain_quad" -- (default 1) a
-                last strip of at most 64 live columns is covered by workgroups whose four wave columns take a row range each
+                last strip of at most 64 live columns is covered by workgroups whose 64-column wave columns (four or six) take a row range each
                 (4096 x 4096: 504 workgroups of 139 steps instead of 510 of 143; timing-neutral, profiles/r04_summary.md);
    "pink_form" -- the complex-to-real transform of the 1/f frames: -1 (default) the library's own two-pass transform for
                 power-of-two frame lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise, 0 hipFFT for every length;
@@ -461,6 +461,23 @@ int rip_last_chain_form(rip_ctx *ctx);
    context and no GPU.  What it does not know: the plan (a difference mask other than the full one takes the stage kernels), the
    CALDIR set (flag words that cannot be merged do too), the call (a sub-chain, an f32 cube, "fused" / "chain2" switched off). */
 int rip_chain_form_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype);
+
+/* The launch geometry the fused kernel takes for such a ramp on a frame of ny rows and nx columns, on a device of ncu compute
+   units, with the options "chain_reserve" = reserve and "chain_quad" = quad_ok -- computed by the launcher's own code, on the
+   host: needs no context and no GPU.  Returns 0 where rip_chain_form_for does (or for a frame the chain does not take: ny < 16,
+   nx not a multiple of 128), else 2 and
+     out[0] columns of a workgroup's window (256 or 384)     out[1] column strips (pitch out[0] - 4)
+     out[2] columns of the last strip's window inside the frame (nx - (out[1] - 1) * (out[0] - 4))
+     out[3] row ranges of every full-width strip             out[4] rows of such a range
+     out[5] quad workgroups covering the last strip, 0 = uniform grid (the last strip like every other: out[3] ranges)
+     out[6] rows of the range of ONE 64-column wave column of a quad workgroup (out[0] / 64 of them each), 0 = uniform grid
+     out[7] grid size: out[3] * (out[1] - 1) + out[5] in quad mode, out[3] * out[1] in the uniform grid.
+   Row range i starts at row i * rows; ranges that start at or beyond ny are empty, the last non-empty one may be short.
+   The result depends on the group count and the ipc4d dtype only through the form (5-8 / 9-16 groups, f32 / f64). */
+int rip_chain_geometry_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype, int ny, int nx, int ncu, int reserve,
+                           int quad_ok, int out[8]);
+/* the geometry (as above) of the fused launch of the last rip_calibrate on this context; zeros when it ran the stage kernels */
+int rip_last_chain_geometry(rip_ctx *ctx, int out[8]);
 
 /* pseudo-Poisson noise layers ("O" directives, gen_noise_image.py:173-240): per element of I (n doubles, host memory) the
    member of the Pearson family with the moments tilnu_21 I, tilnu_31 I, 3 tilnu_21^2 I^2 + tilnu_41 I, replacing

@@ -149,6 +149,8 @@ SYMBOLS = {
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_last_chain_form": (_I, [_VP]),
     "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
+    "rip_chain_geometry_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "rip_last_chain_geometry": (_I, [_VP, C.POINTER(_I)]),
     "rip_profile_enable": (_I, [_VP, _I]),
     "rip_profile_read": (_I, [_VP, C.POINTER(C.c_double), C.POINTER(_I)]),
 }
@@ -192,6 +194,19 @@ def chain_form_for(lin_nplanes, ngroups, ipc_dtype=RIP_F32, gain_dtype=RIP_F32):
     know the plan or the CALDIR set: a ramp also takes the stage kernels when the plan's differences are not the full set or
     the set's flag words cannot be merged (``Context.last_chain_form`` tells what a call really ran)."""
     return int(load_library().rip_chain_form_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype)))
+
+
+GEOMETRY_FIELDS = ("cols", "nstrips", "live_last", "nr", "rows", "nq", "rows_q", "grid")
+
+
+def chain_geometry_for(lin_nplanes, ngroups, ipc_dtype, ny, nx, ncu, reserve=8, quad_ok=True, gain_dtype=RIP_F32):
+    """The fused kernel's launch geometry for such a ramp on an (ny, nx) frame and a device of ``ncu`` compute units, as a dict
+    with the keys ``GEOMETRY_FIELDS`` (``rip_chain_geometry_for``: ``nq`` > 0 means quad mode), or None where the stage kernels
+    run.  Needs no GPU; ``Context.last_chain_geometry`` tells what a call really used."""
+    out = (C.c_int * 8)()
+    rc = load_library().rip_chain_geometry_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype), int(ny), int(nx),
+                                               int(ncu), int(reserve), int(bool(quad_ok)), out)
+    return dict(zip(GEOMETRY_FIELDS, out)) if rc == 2 else None
 
 
 def dtype_code(arr):
@@ -278,6 +293,12 @@ class Context:
     def last_chain_form(self):
         """0 = stage kernels, 2 = the fused kernel (last calibrate call; 1 and 3 were the general and wave-private fused kernels of rounds 1-2)."""
         return int(self.lib.rip_last_chain_form(self.h))
+
+    def last_chain_geometry(self):
+        """launch geometry of the last calibrate call's fused kernel (keys ``GEOMETRY_FIELDS``); all zeros after a stage-kernel run"""
+        out = (C.c_int * 8)()
+        self.check(self.lib.rip_last_chain_geometry(self.h, out))
+        return dict(zip(GEOMETRY_FIELDS, out))
 
     def profile(self, on=True):
         self.check(self.lib.rip_profile_enable(self.h, int(bool(on))))

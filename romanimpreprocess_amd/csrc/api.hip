@@ -296,6 +296,11 @@ extern "C" int rip_prepass_stamps(rip_ctx *ctx, int nwg, unsigned long long *out
 }
 
 int rip_last_chain_form(rip_ctx *ctx) { return ctx ? ctx->last_form : RIP_EINVAL; }
+int rip_last_chain_geometry(rip_ctx *ctx, int out[8]) {
+    if (!ctx || !out) return RIP_EINVAL;
+    for (int i = 0; i < 8; ++i) out[i] = ctx->last_form == 2 ? ctx->last_geo[i] : 0;
+    return RIP_OK;
+}
 
 int rip_profile_enable(rip_ctx *ctx, int on) {
     ctx->prof = on != 0;
@@ -931,6 +936,7 @@ struct Calibration {
     // Level-1 (u16) cube; sub-chains and f32 cubes take the stage-by-stage kernels
     int fused_chain() {
         ctx->last_form = 0;
+        memset(ctx->last_geo, 0, sizeof ctx->last_geo);
         if (!(ctx->use_fused && do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
               rip_chain_supported(ctx, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype)))
             return RIP_OK;

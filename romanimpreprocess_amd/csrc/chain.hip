@@ -1,6 +1,8 @@
 // Dispatch of the fused chain kernel (chain2_kernel.h): the one list of the configurations it is compiled for.  Each (Legendre
 // order, ipc4d dtype, part of the group-count list) is one instantiation of rip_launch_chain2 in a translation unit of its own
 // (chain_np*.hip, compiled once per part), so that they compile in parallel.
+#include <string.h>
+
 #include "chain2_form.h"
 
 template <int NP, typename KT, int PART>
@@ -62,6 +64,31 @@ bool rip_chain_supported(const rip_ctx *ctx, int nplanes, int G, int k_dtype, in
 // 0 = the stage kernels run
 int rip_chain_form_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype) {
     return rip_chain_supported(nullptr, lin_nplanes, ngroups, ipc_dtype, gain_dtype) ? 2 : 0;
+}
+
+// The launch geometry the fused kernel would use for such a ramp on a (ny, nx) frame, on a device of ncu CUs with the options
+// "chain_reserve" = reserve and "chain_quad" = quad_ok: host arithmetic only, the launcher's own (c2_form_geometry).  0 = no
+// fused form (or no such frame: the chain takes ny >= 16 and nx a multiple of the channel width), 2 = out filled.
+int rip_chain_geometry_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain_dtype, int ny, int nx, int ncu, int reserve,
+                           int quad_ok, int out[8]) {
+    if (!out || !rip_chain_form_for(lin_nplanes, ngroups, ipc_dtype, gain_dtype)) return 0;
+    if (ny < 16 || nx < RIP_CW || nx % RIP_CW || ncu < 1) return 0;
+    ChainArgs a;
+    memset(&a, 0, sizeof a);
+    a.ny = ny, a.nx = nx, a.ngrp = ngroups;
+    if (reserve < 0) reserve = 0;   // as rip_set_option stores it
+    const bool k64 = ipc_dtype == RIP_F64;
+#define RIP_GEO(g)                                                                                   \
+    if (ngroups == g) {                                                                              \
+        if (k64)                                                                                     \
+            c2_form_geometry<C2Form<g + (g & 1), true>>(a, ncu, reserve, quad_ok != 0, out);         \
+        else                                                                                         \
+            c2_form_geometry<C2Form<g + (g & 1), false>>(a, ncu, reserve, quad_ok != 0, out);        \
+        return 2;                                                                                    \
+    }
+    RIP_CHAIN_G_ALL(RIP_GEO)
+#undef RIP_GEO
+    return 0;
 }
 
 // Does the fused form of this ramp fill the LDS of every CU, so that the pre-pass of the next ramp finds no room beside it?  From

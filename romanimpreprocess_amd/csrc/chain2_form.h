@@ -125,3 +125,57 @@ struct C2Form {
     // every blocked loop of the kernel steps by one of these over a count they divide: no block runs past its arrays or rings
     static_assert((G / 2) % pb == 0 && (G / 2) % pbc == 0 && G % nbo == 0, "block factors divide their counts");
 };
+
+// Launch geometry on `slots` co-resident workgroups, `reserve` of them left free where that costs nothing (the pre-pass of the NEXT
+// ramp runs in them beside this kernel): every strip gets the same number of row ranges -- except a last strip of at most 64 live
+// columns (nx = 4096 in the 256-column form: 16 strips of 252 + 64), which is covered in QUAD mode: nq workgroups whose wc wave
+// columns take a row range each.  4096 x 4096: 16 x 31 ranges of 133 rows + 8 quad workgroups (32 ranges of 128 rows) = 504 workgroups
+// of 139 steps; before (17 x 30 ranges of 137 rows): 510 of 143.  Returns the grid size.
+static inline long chain2_geometry(ChainArgs &a, int nstrips, int live_last, int slots, int reserve, int wc = 4, bool quad_ok = true) {
+    const int maxr = (a.ny + 7) / 8;   // at least 8 rows per range
+    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
+    int best_nr = 0, best_nq = 0, best_steps = 1 << 30;
+    if (quad_ok && nstrips > 1 && live_last <= 64) {
+        const int nfull = nstrips - 1;
+        for (int pass = 0; pass < 2 && !best_nr; ++pass) {   // (second pass: without the reserve, when it leaves no room)
+            const int avail = slots - (pass ? 0 : reserve);
+            for (int nq = 1; wc * nq <= maxr && nq < avail; ++nq) {
+                int nr = (avail - nq) / nfull;
+                if (nr > maxr) nr = maxr;
+                if (nr < 1) break;
+                const int steps = cdiv(a.ny, nr) > cdiv(a.ny, wc * nq) ? cdiv(a.ny, nr) : cdiv(a.ny, wc * nq);
+                if (steps < best_steps) best_steps = steps, best_nr = nr, best_nq = nq;
+            }
+        }
+    }
+    int nr_u = (slots - reserve) / nstrips;   // every strip alike
+    if (nr_u < 1) nr_u = slots / nstrips;
+    if (nr_u > maxr) nr_u = maxr;
+    if (nr_u < 1) nr_u = 1;
+    if (best_nr && best_steps < cdiv(a.ny, nr_u)) {
+        a.geo_nr = best_nr, a.geo_rows = cdiv(a.ny, best_nr), a.geo_nq = best_nq, a.geo_rows_q = cdiv(a.ny, wc * best_nq);
+        return (long)best_nr * (nstrips - 1) + best_nq;
+    }
+    a.geo_nr = nr_u, a.geo_rows = cdiv(a.ny, nr_u), a.geo_nq = 0, a.geo_rows_q = 0;
+    return (long)nr_u * nstrips;
+}
+
+// The launch geometry of form F for the frame in a (ny, nx) on a device of ncu CUs: the workgroup slots of the form (per CU as many
+// as the LDS holds, at most as many as its waves per SIMD allow), the reserve (narrow forms fill their CUs: none), the strip
+// count and the live columns of the last strip.  THE one place that computes it: the launcher (chain2_kernel.h) and the query
+// rip_chain_geometry_for (chain.hip) both call it.  Sets a.geo_*, returns the grid size; geo (may be null) receives window
+// columns, strip count, live columns of the last strip, geo_nr, geo_rows, geo_nq, geo_rows_q, grid size.
+template <typename F>
+static inline long c2_form_geometry(ChainArgs &a, int ncu, int reserve, bool quad_ok, int *geo) {
+    int per_cu = (160 * 1024) / F::lds_bytes;
+    if (per_cu < 1) per_cu = 1;
+    const int max_wg = 4 * F::wps / (F::threads / 64);
+    if (per_cu > max_wg) per_cu = max_wg;
+    const int nstrips = F::nstrips(a.nx), live_last = a.nx - (nstrips - 1) * F::outw;
+    const long grid = chain2_geometry(a, nstrips, live_last, ncu * per_cu, F::narrow ? 0 : reserve, F::cols / 64, quad_ok);
+    if (geo) {
+        geo[0] = F::cols, geo[1] = nstrips, geo[2] = live_last, geo[3] = a.geo_nr, geo[4] = a.geo_rows, geo[5] = a.geo_nq,
+        geo[6] = a.geo_rows_q, geo[7] = (int)grid;
+    }
+    return grid;
+}

@@ -1052,54 +1052,13 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
 #endif
 }
 
-// Launch geometry on `slots` co-resident workgroups, `reserve` of them left free where that costs nothing (the pre-pass of the NEXT
-// ramp runs in them beside this kernel): every strip gets the same number of row ranges -- except a last strip of at most 64 live
-// columns (nx = 4096 in the 256-column form: 16 strips of 252 + 64), which is covered in QUAD mode: nq workgroups whose wc wave
-// columns take a row range each.  4096 x 4096: 16 x 31 ranges of 133 rows + 8 quad workgroups (32 ranges of 128 rows) = 504 workgroups
-// of 139 steps; before (17 x 30 ranges of 137 rows): 510 of 143.  Returns the grid size.
-static inline long chain2_geometry(ChainArgs &a, int nstrips, int live_last, int slots, int reserve, int wc = 4, bool quad_ok = true) {
-    const int maxr = (a.ny + 7) / 8;   // at least 8 rows per range
-    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
-    int best_nr = 0, best_nq = 0, best_steps = 1 << 30;
-    if (quad_ok && nstrips > 1 && live_last <= 64) {
-        const int nfull = nstrips - 1;
-        for (int pass = 0; pass < 2 && !best_nr; ++pass) {   // (second pass: without the reserve, when it leaves no room)
-            const int avail = slots - (pass ? 0 : reserve);
-            for (int nq = 1; wc * nq <= maxr && nq < avail; ++nq) {
-                int nr = (avail - nq) / nfull;
-                if (nr > maxr) nr = maxr;
-                if (nr < 1) break;
-                const int steps = cdiv(a.ny, nr) > cdiv(a.ny, wc * nq) ? cdiv(a.ny, nr) : cdiv(a.ny, wc * nq);
-                if (steps < best_steps) best_steps = steps, best_nr = nr, best_nq = nq;
-            }
-        }
-    }
-    int nr_u = (slots - reserve) / nstrips;   // every strip alike
-    if (nr_u < 1) nr_u = slots / nstrips;
-    if (nr_u > maxr) nr_u = maxr;
-    if (nr_u < 1) nr_u = 1;
-    if (best_nr && best_steps < cdiv(a.ny, nr_u)) {
-        a.geo_nr = best_nr, a.geo_rows = cdiv(a.ny, best_nr), a.geo_nq = best_nq, a.geo_rows_q = cdiv(a.ny, wc * best_nq);
-        return (long)best_nr * (nstrips - 1) + best_nq;
-    }
-    a.geo_nr = nr_u, a.geo_rows = cdiv(a.ny, nr_u), a.geo_nq = 0, a.geo_rows_q = 0;
-    return (long)nr_u * nstrips;
-}
-
 template <int NP, int G, int START, typename KT>
 static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
     using F = C2Form<G + (G & 1), sizeof(KT) == 8>;
     const size_t lds = F::lds_bytes;
-    const int ncu = ctx->ncu;
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu < 1) per_cu = 1;
-    // workgroups per CU: as many as the LDS holds, at most as many as the form's waves per SIMD allow
-    const int max_wg = 4 * F::wps / (F::threads / 64);
-    if (per_cu > max_wg) per_cu = max_wg;
     if (a.nb < 2) return 1;   // (the frame-edge lanes of the first / last strip emit without neighbours: border pixels)
     ChainArgs ag = a;
-    const long grid = chain2_geometry(ag, F::nstrips(a.nx), a.nx - (F::nstrips(a.nx) - 1) * F::outw, ncu * per_cu,
-                                      F::narrow ? 0 : ctx->chain_reserve, F::cols / 64, ctx->chain_quad);
+    const long grid = c2_form_geometry<F>(ag, ctx->ncu, ctx->chain_reserve, ctx->chain_quad, ctx->last_geo);
     static bool lds_set[64] = {};   // per device, once per instantiation (contexts are used from one thread each)
     if (lds > 48 * 1024 && !lds_set[ctx->device & 63]) {
         RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT>),

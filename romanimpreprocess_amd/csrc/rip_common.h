@@ -166,6 +166,7 @@ struct rip_ctx {
     void *prepass_stamps = nullptr;   // diagnostic: device buffer of 16 clock stamps per workgroup of the single-launch pre-pass
     bool chain_quad = true;     // a last strip of <= 64 live columns in quad mode (chain2_geometry); false: every strip alike (A/B timing)
     int chain_reserve = 8;      // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
+    int last_geo[8] = {};       // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
     // reference-pixel tables: -1 = by situation (a pre-pass that overlaps the previous ramp's fused kernel: the nine small launches
     // of refpix.hip, which slip into that kernel's tail; a pre-pass in front of its own ramp on the same stream: the single launch
     // of refpix_one.hip where it covers the frame); 0 = refpix.hip always, 1 = refpix_one.hip wherever it covers the frame
@@ -292,9 +293,9 @@ struct ChainArgs {
     int merged_dq;     // plane index (relative to NP) of the flag word that already holds flat flags / dark dq as this call applies them
     int dbg;           // timing experiments only (rip_set_option "chain_dbg"): skips phases, results invalid
     int ny, nx, nb, ngrp;
-    // launch geometry (set by the launcher, chain2_kernel.h): geo_nr row ranges of geo_rows rows for each full-width strip; where
+    // launch geometry (set by the launcher through c2_form_geometry, chain2_form.h): geo_nr row ranges of geo_rows rows for each full-width strip; where
     // the last strip has at most 64 live columns (nx = 4096: 17th strip of the 256-column form) it is covered by geo_nq workgroups
-    // whose four wave columns each march down their OWN range of geo_rows_q rows of that strip (0: every strip alike)
+    // whose COLS / 64 wave columns (four or six) each march down their OWN range of geo_rows_q rows of that strip (0: every strip alike)
     int geo_nr, geo_rows, geo_nq, geo_rows_q;
 };
 // THE list of the group counts the fused kernel has a form for, in the parts its instantiations are compiled in (one translation

@@ -88,6 +88,16 @@ class Calibrator:
         nplanes, ipc_dtype, gain_dtype = self.ctx.caldir_dtypes[int(slot)]
         return _native.chain_form_for(nplanes, ngroups, ipc_dtype, gain_dtype)
 
+    def chain_geometry_for(self, slot, ngroups, ncu, reserve=8, quad_ok=True):
+        """Launch geometry of the fused kernel (``_native.chain_geometry_for``) for a ramp of ``ngroups`` groups on the CALDIR set
+        of ``slot`` -- its frame shape and dtypes -- on a device of ``ncu`` compute units; None where the stage kernels run.
+        ``Context.last_chain_geometry`` tells what a call really used."""
+        if int(slot) not in self.ctx.caldir_dtypes:
+            raise ValueError(f"chain_geometry_for: no CALDIR set is loaded in slot {slot}")
+        nplanes, ipc_dtype, gain_dtype = self.ctx.caldir_dtypes[int(slot)]
+        ny, nx = self.shapes[slot]
+        return _native.chain_geometry_for(nplanes, ngroups, ipc_dtype, ny, nx, ncu, reserve, quad_ok, gain_dtype)
+
     # ---- plans ----------------------------------------------------------------------------
     def plan_for(self, read_pattern, frame_time, exclude_first=True, ramp_opt_pars=None, jump_pars=None):
         """(plan id, meta) for an MA table; cached per configuration."""

@@ -49,15 +49,20 @@ def same(a, b, zero_sign_ok=False):
 
 fails, forms = 0, {0: 0, 1: 0, 2: 0, 3: 0}
 by_groups = {}   # group count -> [cases, of them on the fused kernel]
+by_geometry = {}   # (window columns, 5-8 / 9-16 groups, uniform / quad) -> fused launches, from rip_last_chain_geometry
 t0 = time.time()
 for case in range(ncases):
     rp = random_pattern()
     ny, nx = int(rng.integers(4, 13)) * 8, int(rng.choice([128, 256, 384]))
     if rng.random() < 0.1:
         # a tenth of the cases: frames of several strips and row ranges (up to 9 strips of the narrow forms, ranges that do
-        # not divide the rows), with a group count the fused kernel is instantiated for
+        # not divide the rows), with a group count the fused kernel is instantiated for; 768 and 1152 columns -- multiples of 384,
+        # where the 384-column forms have a last strip narrow enough for quad mode -- with heights up to 1400 rows, tall enough
+        # for quad mode to win on a device of 256 CUs (the tally at the end tells what the sweep reached)
         rp = random_pattern(5, 16)
-        ny, nx = int(rng.integers(13, 76)) * 4, int(rng.choice([512, 640, 1024]))
+        ny, nx = int(rng.integers(13, 76)) * 4, int(rng.choice([512, 640, 768, 1024, 1152]))
+        if nx in (768, 1152) or rng.random() < 0.25:
+            ny = int(rng.integers(52, 1401))
     p = int(rng.choice([3, 8, 10]))
     gdt = np.float64 if rng.random() < 0.2 else np.float32
     kdt = np.float64 if rng.random() < 0.4 else np.float32
@@ -104,6 +109,11 @@ for case in range(ncases):
     tally = by_groups.setdefault(len(rp), [0, 0])
     tally[0] += 1
     tally[1] += ctx.last_chain_form() == 2
+    if ctx.last_chain_form() == 2:
+        geo = ctx.last_chain_geometry()
+        key = (f"{'f64' if kdt == np.float64 else 'f32'} ipc4d, {'5-8' if len(rp) <= 8 else '9-16'} groups, {geo['cols']} columns",
+               "quad" if geo["nq"] else "uniform")
+        by_geometry[key] = by_geometry.get(key, 0) + 1
     ok = (same(got["cube"], ref["data"], True) and same(got["groupdq"], ref["groupdq"]) and same(got["pixeldq"], ref["pixeldq"])
           and all(same(got[k], ref[k], True) for k in ("slope", "err_read", "err_poisson")))
     if not ok:
@@ -116,4 +126,5 @@ ctx.set_option("fused", 1)
 ctx.set_option("chain2", 1)
 print(f"done: {ncases} cases, {fails} mismatches; kernel forms used (0 stage kernels, 2 fused kernel): {forms}")
 print("groups: cases / on the fused kernel --", ", ".join(f"{g}: {n} / {f}" for g, (n, f) in sorted(by_groups.items())))
+print("fused launches by (form, launch geometry) --", ", ".join(f"{form} {mode}: {n}" for (form, mode), n in sorted(by_geometry.items())))
 sys.exit(1 if fails else 0)
