@@ -223,7 +223,9 @@ int rip_calibrate_batch(rip_ctx *ctx, int sca_slot, int plan_id, unsigned stages
    after an error return every stream has been drained, outputs [0, this) are valid and the rest are not. */
 int rip_calibrate_batch_completed(rip_ctx *ctx);
 
-/* ---- stage-level entry points (host arrays; for function-level drop-in and parity tests) ----- */
+/* ---- stage-level entry points (for function-level drop-in and parity tests) ------------------
+   Array arguments of this section are HOST arrays.  (Which stage-level entry points also take device pointers is stated at
+   each; the list is at the top of romanimpreprocess_amd/csrc/rip_host.h.) */
 
 /* reference_subtraction.ref_subtraction_row(image, use_ref_channel=True, slope) followed by
    ref_subtraction_channel(image, use_ref_channel=True) on one (ny, nx+128) f32 image, in place: rip_stage_refpix_row
@@ -364,7 +366,7 @@ int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, 
 /* ipc_linearity.invlinearity (ipc_linearity.py:347-394): 24 bisection steps on z in (-1, 1) of the Legendre series evaluated
    as ipc_linearity._lin does without the extrapolation branch, then S = Smin + (Smax - Smin)/2 * (1 + z).  slin (ny,nx) f32 or
    f64 (dtype); coefs (nplanes,ny,nx), smin, smax f32 already cut to the block; S has slin's dtype; exflag (ny,nx) u8 or NULL
-   (|z| > 1 at the last evaluation: the reference's second return value).  Host arrays.  Exact. */
+   (|z| > 1 at the last evaluation: the reference's second return value).  Host arrays (no device pointers).  Exact. */
 int rip_stage_invlinearity(rip_ctx *ctx, const void *slin, int dtype, int ny, int nx, int nplanes, const float *coefs,
                            const float *smin, const float *smax, void *S, uint8_t *exflag);
 
@@ -373,7 +375,8 @@ int rip_stage_invlinearity(rip_ctx *ctx, const void *slin, int dtype, int ny, in
    data' = u16(rint(clip(f32(data) + f32(f64(normal) * (f64(read) / sqrt(f64(N_k)))), 0, 65535))); border pixels unchanged.
    cube, out (ngrp,ny,nx) u16; read_noise (ny,nx) f32; nreads[ngrp]; normals (ngrp,ny-2nb,nx-2nb) f32 standard normal
    deviates from the caller, or NULL: drawn on the device from a counter-based generator keyed by (seed, layer, group,
-   pixel).  Host arrays.  Exact given the normals. */
+   pixel).  cube, read_noise, normals and out are host arrays or device pointers; out may be cube (in place).  Exact given the
+   normals. */
 int rip_stage_noise_inject(rip_ctx *ctx, const uint16_t *cube, int ngrp, int ny, int nx, int nb, const float *read_noise,
                            const int32_t *nreads, const float *normals, uint64_t seed, uint32_t layer, uint16_t *out);
 
@@ -381,7 +384,8 @@ int rip_stage_noise_inject(rip_ctx *ctx, const uint16_t *cube, int ngrp, int ny,
    logarithmic frequency range), the generator behind the correlated part of a read-noise layer (:376-399).  For each frame
    L = 2*rows*width complex samples (n_k + i n_{L+k}) |k|^-1/2 are Fourier transformed in f64 (hipFFT), the real part of the
    first L/2 outputs / sqrt(2) minus its mean is the frame, cast to f32.  normals (nframes, 2L) f64 standard normal deviates
-   from the caller, or NULL: drawn on the device (seed, stream_id).  out (nframes, rows, width) f32.  Host arrays.  Agrees
+   from the caller, or NULL: drawn on the device (seed, stream_id).  out (nframes, rows, width) f32.  Host arrays (no device
+   pointers: rip_synth_noise_1f leaves the frames on the device).  Agrees
    with the reference's numpy FFT to rounding (~1e-12 relative before the cast), not bit for bit. */
 int rip_stage_noise_1f(rip_ctx *ctx, int rows, int width, int nframes, const double *normals, uint64_t seed,
                        uint32_t stream_id, float *out);
@@ -392,7 +396,8 @@ int rip_stage_noise_1f(rip_ctx *ctx, int rows, int width, int nframes, const dou
    delta[j] with the weight vector of the ramp's end slice (weights (ngrp,ngrp) f32 row-major, has_weights[es] = 0 where the
    reference has no vector; endslice (n) i8 already mapped as the reference does, <= 0 -> ngrp - 1).  samples (nsamp,n) f64
    Poisson deviates from the caller, or NULL: drawn on the device (inversion / PTRS on Philox uniforms keyed by seed, layer,
-   read, pixel).  gain (n) f32 or f64, already clipped to [1e-4, 1e4].  Up to 16 groups.  Host arrays; diff in/out.
+   read, pixel).  gain (n) f32 or f64, already clipped to [1e-4, 1e4].  Up to 16 groups.  skylevel, gain, endslice, samples and
+   diff (in/out) are host arrays or device pointers; the group tables and weights are host arrays.
    Exact given the deviates. */
 int rip_stage_poisson_resample(rip_ctx *ctx, const float *skylevel, const void *gain, int gain_dtype, size_t n,
                                double frame_time, int ngrp, const int32_t *group_first, const int32_t *group_count,
@@ -479,14 +484,15 @@ int rip_chain_geometry_for(int lin_nplanes, int ngroups, int ipc_dtype, int gain
 /* the geometry (as above) of the fused launch of the last rip_calibrate on this context; zeros when it ran the stage kernels */
 int rip_last_chain_geometry(rip_ctx *ctx, int out[8]);
 
-/* pseudo-Poisson noise layers ("O" directives, gen_noise_image.py:173-240): per element of I (n doubles, host memory) the
+/* pseudo-Poisson noise layers ("O" directives, gen_noise_image.py:173-240): per element of I (n doubles) the
    member of the Pearson family with the moments tilnu_21 I, tilnu_31 I, 3 tilnu_21^2 I^2 + tilnu_41 I, replacing
    L1_to_L2/GalPoisson/draw_with_tilnus.py:draw_from_Pearson (:12-135) and the solvers / samplers it calls.
    types  (n int32, or NULL): 0 = outside the admissible region (deviate 0), 1, 3, 4, 5, 6 = Pearson type;
    params (4 n doubles, or NULL): type 1: a, b, mean, c; 3: shape, scale, shift, sign; 4: m, nu, a, lambda; 5: a, b, mu, sign;
           6: alpha, beta, scale, shift -- the reference's formulas in f64 (pinned by goldens);
    draws  (n doubles, or NULL): one deviate each from a counter-based generator keyed by (seed, stream, element); the
-          reference's scipy / numpy streams cannot be reproduced: parity of the random part unpinned (moments tested). */
+          reference's scipy / numpy streams cannot be reproduced: parity of the random part unpinned (moments tested).
+   I, draws, types and params are host arrays or device pointers. */
 int rip_stage_pearson(rip_ctx *ctx, size_t n, const double *I, double tilnu21, double tilnu31, double tilnu41, uint64_t seed,
                       uint32_t stream, double *draws, int32_t *types, double *params);
 

@@ -6,14 +6,7 @@
 // directions at once (measured: 10.6 ms per 4096 x 4096 x 8 ramp with all outputs, 17.6 ms for single calls); pageable
 // arrays work but serialise.  Streams map onto a few hardware queues (four by default), which is why the entry makes none of
 // its own: with two extra streams the copies did not overlap at all.
-#include "rip_common.h"
-
-// api.hip: the staging of a host ramp that rip_calibrate's host branch uses as well
-size_t rip_host_ramp_bytes(const rip_ramp_desc &in, int ny, int nx);
-int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev);
-size_t rip_result_bytes(int G, size_t npix, bool groupdq);
-rip_outputs rip_result_planes(char *w, const rip_outputs &host, size_t npix);
-int rip_download_results(rip_ctx *ctx, const rip_outputs &dev, const rip_outputs &host, int G, size_t npix, hipStream_t st);
+#include "rip_host.h"   // the staging of a host ramp that rip_calibrate's host branch (calibrate.hip) uses as well
 
 namespace {
 

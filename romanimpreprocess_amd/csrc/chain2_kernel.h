@@ -1073,7 +1073,7 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
 }
 
 // returns the launch status, or 1 when the plan is not one the specialised kernel was compiled for: the dense table the kernel
-// reads (api.hip builds it from the plan's differences) must test exactly the differences of the compile-time mask -- for odd G
+// reads (plan.hip builds it from the plan's differences) must test exactly the differences of the compile-time mask -- for odd G
 // too, where no tested difference may touch the dead half of the last pair
 template <int NP, int G, typename KT>
 static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {

@@ -8,30 +8,10 @@
 //     z += phi < Slin ? 2^-j : -2^-j
 // then S = Smin + (Smax - Smin) / 2 * (1 + z).  One thread per pixel; coefficient planes are read once per pixel (registers).
 // Host arrays in and out, like the other stage entries.  Exact.
-#include "rip_common.h"
+#include "rip_host.h"
 #include "invlin_device.h"
 
 namespace {
-
-template <typename T>
-struct DevBuf {
-    rip_ctx *ctx;
-    T *p = nullptr;
-    explicit DevBuf(rip_ctx *c) : ctx(c) {}
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "invlinearity: %zu bytes", n * sizeof(T));
-        return RIP_OK;
-    }
-    int upload(const void *src, size_t n) {
-        int rc = alloc(n);
-        if (rc) return rc;
-        RIP_HIP(ctx, hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        return RIP_OK;
-    }
-};
 
 template <typename ZT, int NP>
 __global__ __launch_bounds__(256) void invlin_kernel(const ZT *__restrict__ slin, const float *__restrict__ coefs,
@@ -73,8 +53,9 @@ extern "C" int rip_stage_invlinearity(rip_ctx *ctx, const void *slin, int dtype,
     if (!slin || !coefs || !smin || !smax || !S || ny < 1 || nx < 1 || (dtype != RIP_F32 && dtype != RIP_F64))
         return rip_fail(ctx, RIP_EINVAL, "invlinearity: bad arguments");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t npix = (size_t)ny * nx, es = dtype == RIP_F64 ? 8 : 4;
-    DevBuf<unsigned char> din(ctx), dout(ctx), dex(ctx);
+    const size_t npix = (size_t)ny * nx, es = dsize(dtype);
+    DevBuf<> din(ctx), dout(ctx);
+    DevBuf<uint8_t> dex(ctx);
     DevBuf<float> dc(ctx), dmin(ctx), dmax(ctx);
     int rc;
     if ((rc = din.upload(slin, npix * es)) || (rc = dc.upload(coefs, (size_t)nplanes * npix)) || (rc = dmin.upload(smin, npix)) ||
@@ -85,8 +66,6 @@ extern "C" int rip_stage_invlinearity(rip_ctx *ctx, const void *slin, int dtype,
     else
         rc = launch<float>(ctx, nplanes, (const float *)din.p, dc.p, dmin.p, dmax.p, npix, (float *)dout.p, exflag ? dex.p : nullptr);
     if (rc) return rc;
-    RIP_HIP(ctx, hipMemcpyAsync(S, dout.p, npix * es, hipMemcpyDeviceToHost, ctx->stream));
-    if (exflag) RIP_HIP(ctx, hipMemcpyAsync(exflag, dex.p, npix, hipMemcpyDeviceToHost, ctx->stream));
-    RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RIP_OK;
+    if ((rc = dout.download(S, npix * es)) || (exflag && (rc = dex.download(exflag, npix)))) return rc;
+    return dev_sync(ctx);
 }

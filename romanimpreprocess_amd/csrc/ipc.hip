@@ -283,7 +283,7 @@ static int ipc_image_typed(rip_ctx *ctx, int reverse, int order, const void *img
 }
 
 int rip_launch_ipc_image(rip_ctx *ctx, int reverse, int order, const void *img, int img_dtype, int ny, int nx,
-                         const void *kern, int k_dtype, const void *gain, int g_dtype, void *out, int) {
+                         const void *kern, int k_dtype, const void *gain, int g_dtype, void *out) {
     const bool i64 = img_dtype == RIP_F64, k64 = k_dtype == RIP_F64, g64 = gain && g_dtype == RIP_F64;
 #define RIP_IPC_CASE(TI, TK, TG)                                                                      \
     if (i64 == (sizeof(TI) == 8) && k64 == (sizeof(TK) == 8) && g64 == (sizeof(TG) == 8)) {           \

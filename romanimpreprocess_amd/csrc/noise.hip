@@ -5,8 +5,9 @@
 // The standard normal deviates come from the caller (the reference draws them with galsim.GaussianDeviate; which generator
 // is used is the driver's business) -- or, normals == NULL, from a counter-based generator on the device (Philox-4x32-10 +
 // Box-Muller, keyed by seed, layer, group and pixel), so that a layer is reproducible and needs no host random numbers.
-// Border pixels (reference pixels) pass through unchanged.  Host arrays in and out.  Exact given the normals.
-#include "rip_common.h"
+// Border pixels (reference pixels) pass through unchanged.  Arrays in and out are host arrays or device pointers, out == cube
+// (in place) included: rip_host.h.  Exact given the normals.
+#include "rip_host.h"
 #include <cstring>
 
 namespace {
@@ -71,41 +72,19 @@ extern "C" int rip_stage_noise_inject(rip_ctx *ctx, const uint16_t *cube, int ng
         if (nreads[k] < 1) return rip_fail(ctx, RIP_EINVAL, "noise_inject: group %d has %d reads", k, nreads[k]);
         rs[k] = sqrt((double)nreads[k]);   // the kernel divides: read / sqrt(N) as numpy does
     }
-    void *d_cube = nullptr, *d_out = nullptr, *d_read = nullptr, *d_nrm = nullptr, *d_rs = nullptr;
-    int rc = RIP_OK;
-    auto done = [&]() {
-        for (void *p : {d_cube, d_out, d_read, d_nrm, d_rs})
-            if (p) (void)hipFree(p);
-    };
-#define NZ_HIP(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            rc = rip_fail(ctx, RIP_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-            done();                                                                    \
-            return rc;                                                                 \
-        }                                                                              \
-    } while (0)
-    NZ_HIP(hipMalloc(&d_cube, (size_t)ngrp * npix * 2));
-    NZ_HIP(hipMalloc(&d_out, (size_t)ngrp * npix * 2));
-    NZ_HIP(hipMalloc(&d_read, npix * 4));
-    NZ_HIP(hipMalloc(&d_rs, sizeof(double) * RIP_MAX_GROUPS));
-    NZ_HIP(hipMemcpyAsync(d_cube, cube, (size_t)ngrp * npix * 2, hipMemcpyDefault, ctx->stream));
-    NZ_HIP(hipMemcpyAsync(d_read, read_noise, npix * 4, hipMemcpyDefault, ctx->stream));
-    NZ_HIP(hipMemcpyAsync(d_rs, rs, sizeof(double) * ngrp, hipMemcpyDefault, ctx->stream));
-    if (normals) {
-        NZ_HIP(hipMalloc(&d_nrm, (size_t)ngrp * nact * 4));
-        NZ_HIP(hipMemcpyAsync(d_nrm, normals, (size_t)ngrp * nact * 4, hipMemcpyDefault, ctx->stream));
-    }
-    hipLaunchKernelGGL(noise_inject_kernel, dim3((nx + 255) / 256, ny, ngrp), dim3(256), 0, ctx->stream, (const uint16_t *)d_cube,
-                       (const float *)d_nrm, (const float *)d_read, (const double *)d_rs, ngrp, ny, nx, nb, seed, layer,
-                       (uint16_t *)d_out);
-    NZ_HIP(hipGetLastError());
-    NZ_HIP(hipMemcpyAsync(out, d_out, (size_t)ngrp * npix * 2, hipMemcpyDefault, ctx->stream));
-    NZ_HIP(hipStreamSynchronize(ctx->stream));
-#undef NZ_HIP
-    done();
-    return RIP_OK;
+    DevBuf<uint16_t> d_cube(ctx), d_out(ctx);
+    DevBuf<float> d_read(ctx), d_nrm(ctx);
+    DevBuf<double> d_rs(ctx);
+    int rc;
+    if ((rc = d_cube.upload(cube, (size_t)ngrp * npix)) || (rc = d_out.alloc((size_t)ngrp * npix)) || (rc = d_read.upload(read_noise, npix)) ||
+        (rc = d_rs.upload(rs, ngrp)))
+        return rc;
+    if (normals && (rc = d_nrm.upload(normals, (size_t)ngrp * nact))) return rc;
+    hipLaunchKernelGGL(noise_inject_kernel, dim3((nx + 255) / 256, ny, ngrp), dim3(256), 0, ctx->stream, (const uint16_t *)d_cube.p,
+                       (const float *)d_nrm.p, (const float *)d_read.p, (const double *)d_rs.p, ngrp, ny, nx, nb, seed, layer, d_out.p);
+    RIP_HIP(ctx, hipGetLastError());
+    if ((rc = d_out.download(out, (size_t)ngrp * npix))) return rc;
+    return dev_sync(ctx);
 }
 
 // ------------------------------------------------------------------------------------------ resampled Poisson ('P..r')
@@ -117,7 +96,7 @@ extern "C" int rip_stage_noise_inject(rip_ctx *ctx, const uint16_t *cube, int ng
 // the two-point weights for truncated ones) and endslice comes from the L2 file (SLICEOUT).  The Poisson deviates come from
 // the caller (samples (nsamp, n) f64, the reference order) or, samples == NULL, from the device generator: inversion by
 // sequential search below a mean of 10, Hoermann's transformed rejection (PTRS) above, uniforms from Philox keyed by (seed,
-// layer, read, pixel, attempt).  Everything but the deviates is exact.
+// layer, read, pixel, attempt).  Everything but the deviates is exact.  Host arrays or device pointers, like the injection above.
 namespace {
 
 __device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t a, uint32_t b, uint32_t c_, uint32_t d, int which) {
@@ -228,42 +207,23 @@ extern "C" int rip_stage_poisson_resample(rip_ctx *ctx, const float *skylevel, c
         t.has[j] = has_weights[j] ? 1 : 0;
         for (int k = 0; k < ngrp; ++k) t.w[j][k] = weights[j * ngrp + k];
     }
-    const size_t gs = gain_dtype == RIP_F64 ? 8 : 4;
-    void *d_sky = nullptr, *d_gain = nullptr, *d_end = nullptr, *d_smp = nullptr, *d_diff = nullptr;
-    int rc = RIP_OK;
-    auto done = [&]() {
-        for (void *p : {d_sky, d_gain, d_end, d_smp, d_diff})
-            if (p) (void)hipFree(p);
-    };
-#define PR_HIP(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            rc = rip_fail(ctx, RIP_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-            done();                                                                    \
-            return rc;                                                                 \
-        }                                                                              \
-    } while (0)
-    PR_HIP(hipMalloc(&d_sky, n * 4));
-    PR_HIP(hipMalloc(&d_gain, n * gs));
-    PR_HIP(hipMalloc(&d_end, n));
-    PR_HIP(hipMalloc(&d_diff, n * 4));
-    PR_HIP(hipMemcpyAsync(d_sky, skylevel, n * 4, hipMemcpyDefault, ctx->stream));
-    PR_HIP(hipMemcpyAsync(d_gain, gain, n * gs, hipMemcpyDefault, ctx->stream));
-    PR_HIP(hipMemcpyAsync(d_end, endslice, n, hipMemcpyDefault, ctx->stream));
-    PR_HIP(hipMemcpyAsync(d_diff, diff, n * 4, hipMemcpyDefault, ctx->stream));
-    if (samples) {
-        PR_HIP(hipMalloc(&d_smp, (size_t)nsamp * n * 8));
-        PR_HIP(hipMemcpyAsync(d_smp, samples, (size_t)nsamp * n * 8, hipMemcpyDefault, ctx->stream));
-    }
+    DevBuf<float> d_sky(ctx), d_diff(ctx);
+    DevBuf<> d_gain(ctx);
+    DevBuf<int8_t> d_end(ctx);
+    DevBuf<double> d_smp(ctx);
+    int rc;
+    if ((rc = d_sky.upload(skylevel, n)) || (rc = d_gain.upload(gain, n * dsize(gain_dtype))) || (rc = d_end.upload(endslice, n)) ||
+        (rc = d_diff.upload(diff, n)))
+        return rc;
+    if (samples && (rc = d_smp.upload(samples, (size_t)nsamp * n))) return rc;
     ResampleArgs a;
-    a.sky = (const float *)d_sky;
-    a.gain = d_gain;
+    a.sky = d_sky.p;
+    a.gain = d_gain.p;
     a.gain_f64 = gain_dtype == RIP_F64;
     a.t_frame = frame_time;
-    a.endslice = (const int8_t *)d_end;
-    a.samples = (const double *)d_smp;
-    a.diff = (float *)d_diff;
+    a.endslice = d_end.p;
+    a.samples = d_smp.p;
+    a.diff = d_diff.p;
     a.n = n;
     a.ngrp = ngrp;
     a.nsamp = nsamp;
@@ -274,10 +234,7 @@ extern "C" int rip_stage_poisson_resample(rip_ctx *ctx, const float *skylevel, c
         hipLaunchKernelGGL(resample_kernel<double>, grid, dim3(256), 0, ctx->stream, a, t);
     else
         hipLaunchKernelGGL(resample_kernel<float>, grid, dim3(256), 0, ctx->stream, a, t);
-    PR_HIP(hipGetLastError());
-    PR_HIP(hipMemcpyAsync(diff, d_diff, n * 4, hipMemcpyDefault, ctx->stream));
-    PR_HIP(hipStreamSynchronize(ctx->stream));
-#undef PR_HIP
-    done();
-    return RIP_OK;
+    RIP_HIP(ctx, hipGetLastError());
+    if ((rc = d_diff.download(diff, n))) return rc;
+    return dev_sync(ctx);
 }

@@ -17,7 +17,7 @@
 // the method the reference calls "Devroye"), here always in standard form (a = 1: acceptance ~ 1/4 for every parameter set, so
 // the reference's second sampler for low acceptance is not needed); the normalisation needs Re lgamma(m + i nu/2), evaluated
 // by the recurrence + Stirling series.
-#include "rip_common.h"
+#include "rip_host.h"
 
 namespace {
 
@@ -246,41 +246,21 @@ __global__ __launch_bounds__(256) void pearson_kernel(const double *__restrict__
 
 }   // namespace
 
-// host arrays in and out; draws / types / params may each be NULL
+// host arrays or device pointers in and out (rip_host.h); draws / types / params may each be NULL
 extern "C" int rip_stage_pearson(rip_ctx *ctx, size_t n, const double *I, double tilnu21, double tilnu31, double tilnu41,
                                  uint64_t seed, uint32_t stream, double *draws, int32_t *types, double *params) {
     if (!I || (!draws && !types && !params)) return rip_fail(ctx, RIP_EINVAL, "pearson: NULL argument");
     if (n == 0) return RIP_OK;
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    double *d_I = nullptr, *d_o = nullptr, *d_p = nullptr;
-    int32_t *d_t = nullptr;
-    int rc = RIP_OK;
-    auto done = [&]() {
-        for (void *p : {(void *)d_I, (void *)d_o, (void *)d_p, (void *)d_t})
-            if (p) (void)hipFree(p);
-    };
-#define PX_HIP(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            rc = rip_fail(ctx, RIP_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-            done();                                                                    \
-            return rc;                                                                 \
-        }                                                                              \
-    } while (0)
-    PX_HIP(hipMalloc((void **)&d_I, n * 8));
-    if (draws) PX_HIP(hipMalloc((void **)&d_o, n * 8));
-    if (types) PX_HIP(hipMalloc((void **)&d_t, n * 4));
-    if (params) PX_HIP(hipMalloc((void **)&d_p, n * 32));
-    PX_HIP(hipMemcpyAsync(d_I, I, n * 8, hipMemcpyDefault, ctx->stream));
-    hipLaunchKernelGGL(pearson_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_I, n, tilnu21, tilnu31,
-                       tilnu41, seed, stream, draws ? 1 : 0, d_o, d_t, d_p);
-    PX_HIP(hipGetLastError());
-    if (draws) PX_HIP(hipMemcpyAsync(draws, d_o, n * 8, hipMemcpyDefault, ctx->stream));
-    if (types) PX_HIP(hipMemcpyAsync(types, d_t, n * 4, hipMemcpyDefault, ctx->stream));
-    if (params) PX_HIP(hipMemcpyAsync(params, d_p, n * 32, hipMemcpyDefault, ctx->stream));
-    PX_HIP(hipStreamSynchronize(ctx->stream));
-#undef PX_HIP
-    done();
-    return RIP_OK;
+    DevBuf<double> d_I(ctx), d_o(ctx), d_p(ctx);
+    DevBuf<int32_t> d_t(ctx);
+    int rc;
+    if ((rc = d_I.upload(I, n)) || (draws && (rc = d_o.alloc(n))) || (types && (rc = d_t.alloc(n))) || (params && (rc = d_p.alloc(n * 4))))
+        return rc;
+    hipLaunchKernelGGL(pearson_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)d_I.p, n, tilnu21,
+                       tilnu31, tilnu41, seed, stream, draws ? 1 : 0, d_o.p, d_t.p, d_p.p);
+    RIP_HIP(ctx, hipGetLastError());
+    if ((draws && (rc = d_o.download(draws, n))) || (types && (rc = d_t.download(types, n))) || (params && (rc = d_p.download(params, n * 4))))
+        return rc;
+    return dev_sync(ctx);
 }

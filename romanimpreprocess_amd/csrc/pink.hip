@@ -15,7 +15,7 @@
 #include <algorithm>
 
 #include "pink_fft.h"
-#include "rip_common.h"
+#include "rip_host.h"
 
 namespace {
 
@@ -202,22 +202,9 @@ int noise_1f_impl(rip_ctx *ctx, hipStream_t st, int rows, int width, int nframes
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->ev_pink_valid && ctx->pink_stream != st) RIP_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_pink, 0));
     const size_t L = (size_t)2 * rows * width, half = L / 2;
-    double *d_n = nullptr;
-    float *d_o = nullptr;
-    int rc = RIP_OK;
-    auto done = [&]() {   // per-call buffers; the plan and the transform buffers stay with the context
-        for (void *p : {(void *)d_n, (void *)d_o})
-            if (p) (void)hipFree(p);
-    };
-#define PK_HIP(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            rc = rip_fail(ctx, RIP_EHIP, "%s: %s", #call, hipGetErrorString(e_));      \
-            done();                                                                    \
-            return rc;                                                                 \
-        }                                                                              \
-    } while (0)
+    DevBuf<double> d_n(ctx);   // per-call buffers, used on `st`; the plan and the transform buffers stay with the context
+    DevBuf<float> d_o(ctx);
+    int rc;
     // frames are transformed in chunks so that the complex buffer stays at about 1 GB: equal chunks (272 frames of 2^20 points:
     // 5 x 55, not 4 x 64 + 16 padded to 64 -- the transform runs its full batch every time).  The device generator's streams are
     // laid out in blocks of `fblock` frames whatever the chunk is (pink_fill_kernel)
@@ -227,14 +214,14 @@ int noise_1f_impl(rip_ctx *ctx, hipStream_t st, int rows, int width, int nframes
     // power-of-two frames: the hand-written two-pass transform (pink_fft.h); otherwise (and with option "pink_form" = 0) the library's
     const bool own = ctx->pink_form != 0 && pf::supported(L);
     if (ctx->pink_L != L || ctx->pink_chunk != chunk || ctx->pink_own != own) {   // another frame length or batch: new plan and buffers
-        PK_HIP(hipStreamSynchronize(ctx->stream));       // (either stream may still be using the old ones)
-        if (ctx->stream2) PK_HIP(hipStreamSynchronize(ctx->stream2));
+        RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (either stream may still be using the old ones)
+        if (ctx->stream2) RIP_HIP(ctx, hipStreamSynchronize(ctx->stream2));
         rip_pink_release(ctx);
         // one buffer: the folded coefficients (chunk x (L/2+1) complex), then the real series (chunk x L), then the block sums
-        PK_HIP(hipMalloc(&ctx->pink_z, (size_t)chunk * (half + 1) * sizeof(hipfftDoubleComplex) + (size_t)chunk * L * sizeof(double)));
-        PK_HIP(hipMalloc(&ctx->pink_s, ((size_t)chunk * 256 + L) * sizeof(double)));   // the block sums, then the amplitudes a_k
+        RIP_HIP(ctx, hipMalloc(&ctx->pink_z, (size_t)chunk * (half + 1) * sizeof(hipfftDoubleComplex) + (size_t)chunk * L * sizeof(double)));
+        RIP_HIP(ctx, hipMalloc(&ctx->pink_s, ((size_t)chunk * 256 + L) * sizeof(double)));   // the block sums, then the amplitudes a_k
         hipLaunchKernelGGL(pink_amp_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, (double *)ctx->pink_s + (size_t)chunk * 256, L);
-        PK_HIP(hipStreamSynchronize(st));   // (once per frame length: later calls may come on the context's other stream)
+        RIP_HIP(ctx, hipStreamSynchronize(st));   // (once per frame length: later calls may come on the context's other stream)
         if (own) {
             pf::Tables *t = new pf::Tables();
             ctx->pink_tab = t;
@@ -242,7 +229,6 @@ int noise_1f_impl(rip_ctx *ctx, hipStream_t st, int rows, int width, int nframes
             if (e != hipSuccess) {
                 rc = rip_fail(ctx, RIP_EHIP, "noise_1f: transform tables for %zu points: %s", L, hipGetErrorString(e));
                 rip_pink_release(ctx);
-                done();
                 return rc;
             }
         } else {
@@ -251,7 +237,6 @@ int noise_1f_impl(rip_ctx *ctx, hipStream_t st, int rows, int width, int nframes
             if (hipfftPlanMany(&made, 1, &n1, nullptr, 1, (int)(half + 1), nullptr, 1, n1, HIPFFT_Z2D, chunk) != HIPFFT_SUCCESS) {
                 rc = rip_fail(ctx, RIP_EHIP, "noise_1f: hipfftPlanMany(%zu points x %d) failed", L, chunk);
                 rip_pink_release(ctx);
-                done();
                 return rc;
             }
             ctx->pink_plan = (void *)made;
@@ -265,50 +250,39 @@ int noise_1f_impl(rip_ctx *ctx, hipStream_t st, int rows, int width, int nframes
     double *d_s = (double *)ctx->pink_s;
     const double *d_amp = d_s + (size_t)chunk * 256;
     hipfftHandle plan = (hipfftHandle)ctx->pink_plan;
-    if (!out_dev) PK_HIP(hipMalloc((void **)&d_o, (size_t)chunk * half * sizeof(float)));
-    if (normals) PK_HIP(hipMalloc((void **)&d_n, (size_t)chunk * 2 * L * sizeof(double)));
-    if (!own && hipfftSetStream(plan, st) != HIPFFT_SUCCESS) {
-        rc = rip_fail(ctx, RIP_EHIP, "noise_1f: hipfftSetStream failed");
-        done();
-        return rc;
-    }
+    if (!out_dev && (rc = d_o.alloc((size_t)chunk * half))) return rc;
+    if (normals && (rc = d_n.alloc((size_t)chunk * 2 * L))) return rc;
+    if (!own && hipfftSetStream(plan, st) != HIPFFT_SUCCESS) return rip_fail(ctx, RIP_EHIP, "noise_1f: hipfftSetStream failed");
     for (int f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = std::min(chunk, nframes - f0);
-        if (normals)
-            PK_HIP(hipMemcpyAsync(d_n, normals + (size_t)f0 * 2 * L, (size_t)nf * 2 * L * sizeof(double), hipMemcpyHostToDevice, st));
+        if (normals && (rc = d_n.copy_in(normals + (size_t)f0 * 2 * L, (size_t)nf * 2 * L, st))) return rc;
         if (own) {
             const pf::Tables &t = *(const pf::Tables *)ctx->pink_tab;
             double2 *w = reinterpret_cast<double2 *>(z);
-            hipLaunchKernelGGL(pink_fill_w_kernel, dim3((unsigned)((half / 2 + 1 + 255) / 256), nf), dim3(256), 0, st, (const double *)d_n, d_amp,
+            hipLaunchKernelGGL(pink_fill_w_kernel, dim3((unsigned)((half / 2 + 1 + 255) / 256), nf), dim3(256), 0, st, (const double *)d_n.p, d_amp,
                                w, L, seed, stream_id, f0, fblock);
             hipLaunchKernelGGL(pf::pf_cols_kernel, dim3(t.dev.n2 / pf::TW, nf), dim3(pf::NT1), t.lds1, st, w, t.dev);
             hipLaunchKernelGGL(pf::pf_rows_kernel, dim3(t.dev.n1 / pf::TW, nf), dim3(pf::NT2), t.lds2, st, (const double2 *)w, x, t.dev);
         } else {
-            hipLaunchKernelGGL(pink_fill_kernel, dim3((unsigned)((half + 1 + 255) / 256), nf), dim3(256), 0, st, (const double *)d_n, d_amp, z, L,
+            hipLaunchKernelGGL(pink_fill_kernel, dim3((unsigned)((half + 1 + 255) / 256), nf), dim3(256), 0, st, (const double *)d_n.p, d_amp, z, L,
                                nf, seed, stream_id, f0, fblock);
             if (nf < chunk)
-                PK_HIP(hipMemsetAsync(z + (size_t)nf * (half + 1), 0, (size_t)(chunk - nf) * (half + 1) * sizeof(hipfftDoubleComplex), st));
-            if (hipfftExecZ2D(plan, z, x) != HIPFFT_SUCCESS) {
-                rc = rip_fail(ctx, RIP_EHIP, "noise_1f: hipfftExecZ2D failed");
-                done();
-                return rc;
-            }
+                RIP_HIP(ctx, hipMemsetAsync(z + (size_t)nf * (half + 1), 0, (size_t)(chunk - nf) * (half + 1) * sizeof(hipfftDoubleComplex), st));
+            if (hipfftExecZ2D(plan, z, x) != HIPFFT_SUCCESS) return rip_fail(ctx, RIP_EHIP, "noise_1f: hipfftExecZ2D failed");
         }
         hipLaunchKernelGGL(pink_sum_kernel, dim3(256, nf), dim3(256), 0, st, (const double *)x, L, d_s);
-        float *dst = out_dev ? out + (size_t)f0 * half : d_o;
+        float *dst = out_dev ? out + (size_t)f0 * half : d_o.p;
         hipLaunchKernelGGL(pink_mean_kernel, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, st, d_s, half, nf);
         hipLaunchKernelGGL(pink_out_kernel, dim3((unsigned)(((half + 1) / 2 + 255) / 256), nf), dim3(256), 0, st, (const double *)x, L,
                            (const double *)d_s, dst);
-        PK_HIP(hipGetLastError());
-        if (!out_dev) PK_HIP(hipMemcpyAsync(out + (size_t)f0 * half, d_o, (size_t)nf * half * sizeof(float), hipMemcpyDeviceToHost, st));
-        if (!out_dev) PK_HIP(hipStreamSynchronize(st));   // device output: the next chunk follows in stream order
+        RIP_HIP(ctx, hipGetLastError());
+        // host output: d_o is free for the next chunk once it has been read back (device output follows in stream order)
+        if (!out_dev && ((rc = d_o.download(out + (size_t)f0 * half, (size_t)nf * half, st)) || (rc = dev_sync(ctx, st)))) return rc;
     }
-    if (!ctx->ev_pink) PK_HIP(hipEventCreateWithFlags(&ctx->ev_pink, hipEventDisableTiming));
-    PK_HIP(hipEventRecord(ctx->ev_pink, st));
+    if (!ctx->ev_pink) RIP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pink, hipEventDisableTiming));
+    RIP_HIP(ctx, hipEventRecord(ctx->ev_pink, st));
     ctx->pink_stream = st;
     ctx->ev_pink_valid = true;
-#undef PK_HIP
-    done();
     return RIP_OK;
 }
 

@@ -7,38 +7,13 @@
 //   sky.py:100-191           medfit: block nan-medians, Legendre model, subtraction       -> rip_stage_select_ranks, rip_stage_legendre2d (exact)
 //   gen_cal_image.py:697-712 SLICEOUT endslice                                            -> rip_stage_endslice     (exact)
 //   coordutils.py:17-82      pixelarea of a FITS zenithal (+SIP) WCS -> AreaFactor plane  -> rip_stage_pixel_area   (f64)
-// Host arrays in and out (these are per-image calls on planes the caller already holds); the area map may also be written to
-// device memory.
+// Arrays in and out are host arrays or device pointers (rip_host.h; these are per-image calls on planes the caller already
+// holds, the noise-layer driver in HBM); the area map may also be written to device memory in place.
 #include <cmath>
 
-#include "rip_common.h"
+#include "rip_host.h"
 
 namespace {
-
-template <typename T>
-struct DevBuf {
-    rip_ctx *ctx;
-    T *p = nullptr;
-    explicit DevBuf(rip_ctx *c) : ctx(c) {}
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "post: %zu bytes", n * sizeof(T));
-        return RIP_OK;
-    }
-    int upload(const T *src, size_t n) {
-        int rc = alloc(n);
-        if (rc) return rc;
-        RIP_HIP(ctx, hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyDefault, ctx->stream));
-        return RIP_OK;
-    }
-    int download(T *dst, size_t n) {
-        RIP_HIP(ctx, hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDefault, ctx->stream));
-        RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return RIP_OK;
-    }
-};
 
 // ------------------------------------------------------------------------------------------ mask
 // layer(bit) grown by its kernel: 1 = copy, 5 = plus, 9 = 3x3, 25 = 5x5 (zero padded, scipy.signal.convolve mode="same")
@@ -326,7 +301,8 @@ int rip_stage_build_mask(rip_ctx *ctx, const uint32_t *dq, int ny, int nx, const
     if ((rc = d.upload(dq, n)) || (rc = o.alloc(n))) return rc;
     hipLaunchKernelGGL(mask_build_kernel, dim3((nx + 255) / 256, ny), dim3(256), 0, ctx->stream, d.p, o.p, ny, nx, m1, m5, m9, m25);
     RIP_HIP(ctx, hipGetLastError());
-    return o.download(mask, n);
+    if ((rc = o.download(mask, n))) return rc;
+    return dev_sync(ctx);
 }
 
 int rip_stage_endslice(rip_ctx *ctx, const uint8_t *rdq, int ngrp, int ny, int nx, int nb, int8_t *out) {
@@ -341,7 +317,8 @@ int rip_stage_endslice(rip_ctx *ctx, const uint8_t *rdq, int ngrp, int ny, int n
     hipLaunchKernelGGL(endslice_kernel, dim3((nx - 2 * nb + 255) / 256, ny - 2 * nb), dim3(256), 0, ctx->stream, d.p, o.p, ngrp, ny, nx,
                        nb);
     RIP_HIP(ctx, hipGetLastError());
-    return o.download(out, na);
+    if ((rc = o.download(out, na))) return rc;
+    return dev_sync(ctx);
 }
 
 int rip_stage_bin_mean(rip_ctx *ctx, const float *arr, const uint8_t *mask, int ny, int nx, int k, float *out) {
@@ -357,7 +334,8 @@ int rip_stage_bin_mean(rip_ctx *ctx, const float *arr, const uint8_t *mask, int 
     hipLaunchKernelGGL(bin_mean_kernel, dim3((nxo + 255) / 256, nyo), dim3(256), 0, ctx->stream, d.p, mask ? m.p : nullptr, o.p, nx, nyo,
                        nxo, k);
     RIP_HIP(ctx, hipGetLastError());
-    return o.download(out, no);
+    if ((rc = o.download(out, no))) return rc;
+    return dev_sync(ctx);
 }
 
 // counts[blk] = number of non-NaN elements; vals[blk * nranks + r] = element of 0-based rank ranks[blk * nranks + r]
@@ -385,8 +363,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
     RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * PS_BINS * 4, ctx->stream));
     hipLaunchKernelGGL(ps_hist_kernel, dim3(chunks, nblk), dim3(256), 0, ctx->stream, d.p, g, prefix.p, hist.p, -1);
     std::vector<uint32_t> hh((size_t)nblk * PS_BINS);
-    RIP_HIP(ctx, hipMemcpyAsync(hh.data(), hist.p, hh.size() * 4, hipMemcpyDefault, ctx->stream));
-    RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = hist.download(hh.data(), hh.size())) || (rc = dev_sync(ctx))) return rc;
     std::vector<int64_t> cnt(nblk);
     for (int b = 0; b < nblk; ++b) cnt[b] = hh[(size_t)b * PS_BINS];
     if (counts)
@@ -398,7 +375,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
             const int64_t want = ranks[(size_t)b * nranks + q];
             r[b] = (want >= 0 && want < cnt[b]) ? (unsigned long long)want : 0ull;
         }
-        RIP_HIP(ctx, hipMemcpyAsync(rk.p, r.data(), (size_t)nblk * 8, hipMemcpyDefault, ctx->stream));
+        if ((rc = rk.copy_in(r.data(), nblk))) return rc;
         RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * PS_BINS * 4, ctx->stream));
         for (int level = 0; level < 3; ++level) {
             hipLaunchKernelGGL(ps_hist_kernel, dim3(chunks, nblk), dim3(256), 0, ctx->stream, d.p, g, prefix.p, hist.p, level);
@@ -406,7 +383,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
         }
         hipLaunchKernelGGL(ps_finish_kernel, dim3((nblk + 63) / 64), dim3(64), 0, ctx->stream, prefix.p, o.p, nblk);
         RIP_HIP(ctx, hipGetLastError());
-        if ((rc = o.download(v.data(), nblk))) return rc;
+        if ((rc = o.download(v.data(), nblk)) || (rc = dev_sync(ctx))) return rc;   // the host reads v: one wait per rank
         for (int b = 0; b < nblk; ++b) {
             const int64_t want = ranks[(size_t)b * nranks + q];
             vals[(size_t)b * nranks + q] = (want >= 0 && want < cnt[b]) ? v[b] : NAN;
@@ -427,7 +404,8 @@ int rip_stage_gauss_hist(rip_ctx *ctx, const float *arr, int64_t n, const double
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(gauss_hist_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d.p, (size_t)n, dz.p, nz, scale, o.p);
     RIP_HIP(ctx, hipGetLastError());
-    return o.download(out, nz);
+    if ((rc = o.download(out, nz))) return rc;
+    return dev_sync(ctx);
 }
 
 int rip_stage_legendre2d(rip_ctx *ctx, float *arr, int ny, int nx, int order, const double *LPX, const double *LPY, const double *coef,
@@ -449,7 +427,7 @@ int rip_stage_legendre2d(rip_ctx *ctx, float *arr, int ny, int nx, int order, co
     RIP_HIP(ctx, hipGetLastError());
     if (subtract && (rc = d.download(arr, n))) return rc;
     if (model_out && (rc = mo.download(model_out, n))) return rc;
-    return RIP_OK;
+    return dev_sync(ctx);
 }
 
 int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, double scale, int out_location, double *out) {
@@ -481,5 +459,6 @@ int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, 
     if ((rc = o.alloc(n))) return rc;
     hipLaunchKernelGGL(pixel_area_kernel, grid, dim3(256), 0, ctx->stream, *wcs, ny, nx, scale, o.p);
     RIP_HIP(ctx, hipGetLastError());
-    return o.download(out, n);
+    if ((rc = o.download(out, n))) return rc;
+    return dev_sync(ctx);
 }

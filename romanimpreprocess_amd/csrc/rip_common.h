@@ -139,43 +139,65 @@ enum RipWs {
     RIP_WS_COUNT
 };
 
-struct rip_ctx {
+struct rip_ctx {   // host-only: no kernel reads it
     int device = 0;
+    int ncu = 0;             // launch geometry of the fused kernel, per CONTEXT (a second context may sit on another device): CU count
+    std::string err;
+    std::vector<RipCal> cals;
+    std::vector<RipPlan *> plans;
+
+    // ---- streams and events of the chain (rip_calibrate)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;          // reference-pixel pre-pass of the NEXT ramp (device-resident inputs)
     hipEvent_t ev_tab[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     bool ev_done_valid[2] = {false, false};
     int parity = 0;
-    bool use_overlap = true;
-    int overlap_mode = -1;   // -1: by situation (see rip_calibrate), 1: wherever possible
-    bool use_chain2 = true;  // wave-specialised fused kernel where it applies
-    int last_form = 0;       // diagnostic: how the last rip_calibrate ran (0 stage kernels, 2 the fused kernel; 1 and 3 were the general and the wave-private fused kernels of rounds 1-2)
-    std::string err;
-    std::vector<RipCal> cals;
-    std::vector<RipPlan *> plans;
-    // workspace (grown on demand)
-    // per-stage device timing (HIP events on `stream`), see rip_profile_enable / rip_profile_read
-    int chain_dbg = 0;
-    unsigned long long *chain_dbg_buf = nullptr;  // 4096 waves x 6 phases (diagnostic builds)
-    bool use_fused = true;  // rip_set_option("fused", 0) forces the stage-by-stage kernels
-    double guard_band = 1e-5;  // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
-    bool prof = false;
-    std::vector<hipEvent_t> prof_events;  // 6 per rip_calibrate call
+    // set by the entry points that queue work on `stream` with device pointers (rip_synth_*, rip_stats_*): the next overlapped
+    // rip_calibrate then orders its second-stream pre-pass behind that work (it may have produced the call's inputs) through
+    // ev_in, recorded on the main stream
+    bool stream_dirty = false;
+    hipEvent_t ev_in = nullptr;
+    // the pre-pass / saturation pass share workspaces (selection histograms, row tables in the making, exceed bits): when two
+    // consecutive calls run them on different streams (a non-overlapped call between overlapped ones), the later waits for the
+    // earlier through this event
+    hipEvent_t ev_pre = nullptr;
+    hipStream_t pre_stream = nullptr;
+    bool ev_pre_valid = false;
+
+    // ---- workspaces (rip_ws: grown on demand, kept between calls)
     void *ws[RIP_WS_COUNT] = {};   // RipWs
     size_t ws_bytes[RIP_WS_COUNT] = {};
-    void *prepass_stamps = nullptr;   // diagnostic: device buffer of 16 clock stamps per workgroup of the single-launch pre-pass
+
+    // ---- options (rip_set_option, rip_set_option_f64)
+    bool use_overlap = true;
+    int overlap_mode = -1;   // -1: by situation (see rip_calibrate), 1: wherever possible
+    bool use_fused = true;   // rip_set_option("fused", 0) forces the stage-by-stage kernels
+    bool use_chain2 = true;  // wave-specialised fused kernel where it applies
+    double guard_band = 1e-5;  // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
     bool chain_quad = true;     // a last strip of <= 64 live columns in quad mode (chain2_geometry); false: every strip alike (A/B timing)
     int chain_reserve = 8;      // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
-    int last_geo[8] = {};       // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
     // reference-pixel tables: -1 = by situation (a pre-pass that overlaps the previous ramp's fused kernel: the nine small launches
     // of refpix.hip, which slip into that kernel's tail; a pre-pass in front of its own ramp on the same stream: the single launch
     // of refpix_one.hip where it covers the frame); 0 = refpix.hip always, 1 = refpix_one.hip wherever it covers the frame
     int prepass_form = -1;
-    // rip_calibrate_batch (batch.hip): download stream and the two sets of device buffers, kept between calls
+
+    // ---- diagnostics and profiling
+    int last_form = 0;       // diagnostic: how the last rip_calibrate ran (0 stage kernels, 2 the fused kernel; 1 and 3 were the general and the wave-private fused kernels of rounds 1-2)
+    int last_geo[8] = {};    // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
+    int chain_dbg = 0;       // timing experiments only (option "chain_dbg"): the fused kernel skips phases, results invalid
+    unsigned long long *chain_dbg_buf = nullptr;  // 4096 waves x 6 phases (diagnostic builds)
+    void *prepass_stamps = nullptr;   // diagnostic: device buffer of 16 clock stamps per workgroup of the single-launch pre-pass
+    // per-stage device timing (HIP events on `stream`), see rip_profile_enable / rip_profile_read
+    bool prof = false;
+    std::vector<hipEvent_t> prof_events;  // 6 per rip_calibrate call
+
+    // ---- rip_calibrate_batch (batch.hip): download stream and the two sets of device buffers, kept between calls
     hipStream_t stream3 = nullptr;
     void *batch_buf[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t batch_bytes[4] = {0, 0, 0, 0};
-    // 1/f frames (pink.hip): transform plan and buffers of the last (length, batch) kept between calls
+    int batch_completed = 0;  // of the last rip_calibrate_batch: ramps completed (all of them unless it returned an error)
+
+    // ---- 1/f frames (pink.hip): transform plan and buffers of the last (length, batch) kept between calls
     void *pink_plan = nullptr, *pink_z = nullptr, *pink_s = nullptr, *pink_tab = nullptr;   // (library plan OR own tables: pink_own)
     bool pink_own = false;
     int pink_form = -1;   // option "pink_form": 0 = the library's transform for every frame length
@@ -184,26 +206,15 @@ struct rip_ctx {
     bool ev_pink_valid = false;
     size_t pink_L = 0;
     int pink_chunk = 0;
-    // set by the entry points that queue work on `stream` with device pointers (rip_synth_*, rip_stats_*): the next overlapped
-    // rip_calibrate then orders its second-stream pre-pass behind that work (it may have produced the call's inputs)
-    bool stream_dirty = false;
-    // the pre-pass / saturation pass share workspaces (selection histograms, row tables in the making, exceed bits): when two
-    // consecutive calls run them on different streams (a non-overlapped call between overlapped ones), the later waits for the
-    // earlier through this event
-    // launch geometry of the fused kernel, per CONTEXT (a second context may sit on another device): CU count
-    int ncu = 0;
+
+    // ---- Level-1 synthesis (synth.hip)
     // 1/f frames made AHEAD on the second stream (rip_synth_frames_ahead, pink.hip) for the next rip_synth_fill: the transforms
     // (HBM-bound) then run beside the apportioning and the inverse-linearity kernels (arithmetic-bound) of the same exposure
     hipEvent_t ev_frames = nullptr, ev_fill = nullptr, ev_ahead = nullptr;
     bool frames_pending = false, ev_fill_valid = false;
     uint64_t frames_seed = 0;
     int frames_geom[3] = {0, 0, 0};   // rows, channel width, frames
-    std::vector<double> share_tab;   // synth.hip: the read-share table whose device copy sits in workspace slot 10
-    hipEvent_t ev_pre = nullptr;
-    hipStream_t pre_stream = nullptr;
-    bool ev_pre_valid = false;
-    hipEvent_t ev_in = nullptr;
-    int batch_completed = 0;  // of the last rip_calibrate_batch: ramps completed (all of them unless it returned an error)
+    std::vector<double> share_tab;   // the read-share table whose device copy sits in workspace slot 10
 };
 
 // ---------------------------------------------------------------- host helpers
@@ -321,8 +332,7 @@ struct IpcArgs {
 int rip_launch_ipc_cube(rip_ctx *ctx, const IpcArgs &a);
 // generic single-image forward / reverse operator (stage API + CALDIR-derived planes)
 int rip_launch_ipc_image(rip_ctx *ctx, int reverse, int order, const void *img, int img_dtype, int ny, int nx,
-                         const void *kern /* (9,ny,nx) */, int k_dtype, const void *gain, int g_dtype, void *out,
-                         int gain_div_clip /*unused*/);
+                         const void *kern /* (9,ny,nx) */, int k_dtype, const void *gain, int g_dtype, void *out);
 
 // refpix.hip
 struct RefpixArgs {

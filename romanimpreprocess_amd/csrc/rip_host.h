@@ -1,0 +1,80 @@
+// Host-only helpers of libromanhip, defined once: the scoped device buffer of the stage-level entry points and the
+// declarations the host translation units share.  Included by host code in .hip files only -- never by rip_common.h or by a
+// header that holds device code.
+//
+// Pointer kinds of the ARRAY arguments of the stage-level entry points (include/romanhip.h says the same at each):
+//   host arrays OR device pointers   rip_stage_noise_inject (in-place calls, out == cube, included), rip_stage_poisson_resample,
+//                                    rip_stage_pearson, and the post-path entries of post.hip (rip_stage_build_mask, _endslice,
+//                                    _bin_mean, _select_ranks, _gauss_hist, _legendre2d; rip_stage_pixel_area by out_location).
+//                                    The noise-layer driver (L1_to_L2/gen_noise_image.py) hands them planes that live in HBM.
+//   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
+// Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
+// DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
+// copy for a host array, so the one helper serves both rows.  A copy direction "tidied" to an explicit kind breaks the first.
+#pragma once
+
+#include "rip_common.h"
+
+#define RIP_SHARED __attribute__((visibility("hidden")))   // shared between translation units, not part of the interface
+
+inline size_t dsize(int dtype) { return dtype == RIP_F64 ? 8 : (dtype == RIP_U16 ? 2 : 4); }
+inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+// Scoped device allocation of n elements of T for one call of an entry point (`who`: its name, for the error text).
+// upload / download queue their copies on `stream` (null: the context's main stream) and do not wait: an entry point that
+// reads back several arrays pays one dev_sync at its end.
+template <typename T = char>
+struct DevBuf {
+    rip_ctx *ctx;
+    const char *who;
+    T *p = nullptr;
+    explicit DevBuf(rip_ctx *c, const char *who_ = __builtin_FUNCTION()) : ctx(c), who(who_) {}
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t n) {   // n = 0 yields a valid buffer too
+        const size_t bytes = n * sizeof(T);
+        const hipError_t e = hipMalloc((void **)&p, bytes ? bytes : 1);
+        if (e != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "%s: hipMalloc(%zu bytes): %s", who, bytes, hipGetErrorString(e));
+        return RIP_OK;
+    }
+    int copy_in(const void *src, size_t n, hipStream_t stream = nullptr) {   // into the buffer as it stands
+        RIP_HIP(ctx, hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyDefault, stream ? stream : ctx->stream));
+        return RIP_OK;
+    }
+    int upload(const void *src, size_t n, hipStream_t stream = nullptr) {
+        if (const int rc = alloc(n)) return rc;
+        return copy_in(src, n, stream);
+    }
+    int download(void *dst, size_t n, hipStream_t stream = nullptr) const {
+        RIP_HIP(ctx, hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDefault, stream ? stream : ctx->stream));
+        return RIP_OK;
+    }
+};
+
+// waits for what an entry point has queued (its downloads among it)
+inline int dev_sync(rip_ctx *ctx, hipStream_t stream = nullptr) {
+    RIP_HIP(ctx, hipStreamSynchronize(stream ? stream : ctx->stream));
+    return RIP_OK;
+}
+
+// caldir.hip
+RIP_SHARED void free_cal(RipCal &c);
+// plan.hip
+struct PlanFree {   // a plan and its device image
+    void operator()(RipPlan *p) const {
+        if (p->dev) (void)hipFree(p->dev);
+        delete p;
+    }
+};
+RIP_SHARED RipPlan *get_plan(rip_ctx *ctx, int id);   // nullptr (error recorded) where the plan does not exist
+
+// calibrate.hip: a ramp in HOST memory is staged into device buffers, its results laid out there and copied back, by
+// rip_calibrate and by rip_calibrate_batch (batch.hip)
+RIP_SHARED size_t rip_host_ramp_bytes(const rip_ramp_desc &in, int ny, int nx);
+RIP_SHARED int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev);
+RIP_SHARED size_t rip_result_bytes(int G, size_t npix, bool groupdq);
+RIP_SHARED rip_outputs rip_result_planes(char *w, const rip_outputs &host, size_t npix);
+RIP_SHARED int rip_download_results(rip_ctx *ctx, const rip_outputs &dev, const rip_outputs &host, int G, size_t npix, hipStream_t st);

@@ -515,7 +515,7 @@ def test_batch_of_host_ramps_equals_single_calls(flag_sat):
 def test_back_to_back_device_calls_without_sync(flag_sat, inputs_complete):
     """Different device-resident ramps issued back to back with no synchronisation in between (the reference-pixel pre-pass and
     the saturation pass of call n+1 run ahead on the second stream while the chain of call n is still reading ITS tables and
-    flag copies: they are double-buffered by call parity, api.hip): results must equal those of synchronised single calls."""
+    flag copies: they are double-buffered by call parity, calibrate.hip): results must equal those of synchronised single calls."""
     dev = torch.device("cuda", 0)
     rp = synth.READ_PATTERN_8
     ny, nx = 1024, 1024
@@ -610,7 +610,7 @@ def test_mixed_overlap_modes_back_to_back():
     """Calls that run their pre-pass / saturation pass on the MAIN stream (overlap off, or a sub-chain without the reference-pixel
     step that flags saturation) queued between overlapped calls, no synchronisation: every call takes a parity of the
     double-buffered tables and flag copies and leaves its completion event, so a following overlapped call can neither reuse
-    nor overwrite buffers a queued kernel still reads (round-2 advisor finding on api.hip)."""
+    nor overwrite buffers a queued kernel still reads (round-2 advisor finding on calibrate.hip)."""
     n = 6
     cb, pid, ramps, outputs = _small_resident_set(9, n)
     no_ref = pipeline.STAGE_ALL & ~pipeline.STAGE_REFPIX

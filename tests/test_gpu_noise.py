@@ -6,7 +6,7 @@ import torch
 from conftest import assert_same_bits, gpu_context
 
 from oracle import noise as onoise
-from romanimpreprocess_amd import calio, pipeline, synth
+from romanimpreprocess_amd import _native, calio, pipeline, synth
 from romanimpreprocess_amd.L1_to_L2 import gen_cal_image, gen_noise_image
 
 pytestmark = pytest.mark.gpu
@@ -192,6 +192,40 @@ def test_poisson_resampling_is_exact_given_the_deviates(gdt):
     want = onoise.poisson_resample(start.copy(), sky_, gain, t_fr, rp, w, has, endslice, samples)
     got = gen_noise_image.poisson_resample(start.copy(), sky_, gain, t_fr, rp, w, has, endslice, samples=samples, ctx=gpu_context())
     assert_same_bits(got, want, "resampled Poisson layer")
+
+
+@pytest.mark.parametrize("gdt", [np.float32, np.float64])
+def test_poisson_resampling_takes_device_pointers(gdt):
+    """rip_stage_poisson_resample with sky, gain, end slices, deviates and the layer itself in HBM (csrc/rip_host.h: host arrays
+    or device pointers) against the host-array call, which the test above pins to the numpy loop.  1000 pixels: the last block of
+    256 threads is partly empty."""
+    ctx = gpu_context()
+    rng = np.random.default_rng(19)
+    rp = synth.READ_PATTERN_6
+    ngrp, ny, nx = len(rp), 25, 40
+    sky_ = (0.4 + 3.0 * rng.random((ny, nx)) ** 4).astype(np.float32)
+    sky_[3, 3] = -0.2
+    gain = np.clip((1.5 + 0.1 * rng.standard_normal((ny, nx))).astype(gdt), 1e-4, 1e4)
+    t_fr = 3.04
+    pinfo = {"meta": {"tbar": [t_fr * np.mean(g) for g in rp]}, "weights": rng.standard_normal(ngrp).astype(np.float32),
+             "exclude_first": True, "endslice": rng.integers(-1, ngrp, size=(ny, nx)).astype(np.int8)}
+    w, has, endslice = gen_noise_image.ramp_weight_vectors(pinfo, ngrp)
+    nsamp = rp[-1][-1] + 1
+    samples = np.stack([rng.poisson(np.clip(sky_ * gain * t_fr, 0.0, None).astype(np.float64)).astype(np.float64) for _ in range(nsamp)])
+    start = (0.01 * rng.standard_normal((ny, nx))).astype(np.float32)
+    start[0, 0] = -0.0
+    want = gen_noise_image.poisson_resample(start.copy(), sky_, gain, t_fr, rp, w, has, endslice, samples=samples, ctx=ctx)
+    assert not np.array_equal(want, start)
+    dev = torch.device("cuda", ctx.device)
+    t_sky, t_gain, t_end, t_smp, t_diff = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (sky_, gain, endslice, samples, start))
+    first = np.array([g[0] for g in rp], dtype=np.int32)
+    count = np.array([len(g) for g in rp], dtype=np.int32)
+    w32, has8 = np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(has, dtype=np.uint8)
+    torch.cuda.synchronize()
+    ctx.check(ctx.lib.rip_stage_poisson_resample(
+        ctx.h, t_sky.data_ptr(), t_gain.data_ptr(), _native.dtype_code(gain), ny * nx, t_fr, ngrp, first.ctypes.data,
+        count.ctypes.data, w32.ctypes.data, has8.ctypes.data, t_end.data_ptr(), t_smp.data_ptr(), nsamp, 0, 0, t_diff.data_ptr()))
+    assert_same_bits(t_diff.cpu().numpy(), want, "resampled Poisson layer through device pointers")
 
 
 def test_device_poisson_deviates():

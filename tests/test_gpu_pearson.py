@@ -7,7 +7,8 @@ moments are tested against the targets the sampler is built to match."""
 
 import numpy as np
 import pytest
-from conftest import gpu_context, load_golden
+import torch
+from conftest import assert_same_bits, gpu_context, load_golden
 
 from romanimpreprocess_amd.L1_to_L2.GalPoisson import draw_with_tilnus as dw
 
@@ -60,3 +61,33 @@ def test_inadmissible_and_edge_inputs():
     assert t.tolist()[:4] == [0, 0, 0, 0] and t[4] == 6
     assert np.all(x[:4] == 0.0) and np.isfinite(x[4])
     assert dw.draw_from_Pearson(1.0, 1.0, 1.0, np.zeros((0,)), ctx=gpu_context()).shape == (0,)
+
+
+def test_host_arrays_and_device_pointers_give_the_same_bits():
+    """rip_stage_pearson takes host arrays or device pointers for I, draws, types and params (csrc/rip_host.h): the noise-layer
+    loop hands it tensors that live in HBM.  4133 elements: the last block of 256 threads is partly empty."""
+    g = load_golden("pearson_params")
+    ctx = gpu_context()
+    dev = torch.device("cuda", ctx.device)
+    n, seed, stream = 4133, 20250101, 7
+    for name, I in (("poisson_like", 3.0), ("neg_skew", 20.0), ("beta_prime", 30.0), ("heavy_tail", 40.0), ("light_tail", 50.0)):
+        t21, t31, t41 = (float(v) for v in g[f"cl_{name}_t"])
+        h_I = np.full(n, I)
+        d_I = torch.from_numpy(h_I).to(dev)
+        h_draw = np.empty(n, np.float64)
+        d_draw = torch.empty(n, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        ctx.check(ctx.lib.rip_stage_pearson(ctx.h, n, h_I.ctypes.data, t21, t31, t41, seed, stream, h_draw.ctypes.data, None, None))
+        ctx.check(ctx.lib.rip_stage_pearson(ctx.h, n, d_I.data_ptr(), t21, t31, t41, seed, stream, d_draw.data_ptr(), None, None))
+        assert np.all(np.isfinite(h_draw)) and np.unique(h_draw).size > n // 2
+        assert_same_bits(d_draw.cpu().numpy(), h_draw, f"{name}: draws through device pointers")
+        # no draws: types and parameters only
+        h_t, h_p = np.empty(n, np.int32), np.empty((n, 4), np.float64)
+        d_t = torch.empty(n, dtype=torch.int32, device=dev)
+        d_p = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        ctx.check(ctx.lib.rip_stage_pearson(ctx.h, n, h_I.ctypes.data, t21, t31, t41, seed, stream, None, h_t.ctypes.data, h_p.ctypes.data))
+        ctx.check(ctx.lib.rip_stage_pearson(ctx.h, n, d_I.data_ptr(), t21, t31, t41, seed, stream, None, d_t.data_ptr(), d_p.data_ptr()))
+        assert h_t.min() == h_t.max() != 0
+        assert_same_bits(d_t.cpu().numpy(), h_t, f"{name}: types through device pointers")
+        assert_same_bits(d_p.cpu().numpy(), h_p, f"{name}: parameters through device pointers")
