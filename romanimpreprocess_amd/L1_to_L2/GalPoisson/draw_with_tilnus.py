@@ -6,6 +6,7 @@ taken from ``rng`` -- the reference's scipy / numpy streams are not reproduced (
 import numpy as np
 
 from ... import _native
+from ...devarray import DevArray, is_dev
 
 _calls = [0]
 
@@ -30,12 +31,18 @@ def classify(tilnu_21, tilnu_31, tilnu_41, I_arr, ctx=None):
 
 
 def draw_from_Pearson(tilnu_21, tilnu_31, tilnu_41, I_arr, *, atol=0.0, rng=None, ctx=None, stream=None):
-    """One deviate per element of ``I_arr`` (f64 array of the same shape; 0 outside the admissible region)."""
+    """One deviate per element of ``I_arr`` (f64 array of the same shape; 0 outside the admissible region).  Intensities in a
+    ``DevArray`` (f64, resident in HBM) give the deviates in one as well."""
     if atol != 0.0:
         raise NotImplementedError("equality bands (atol > 0) are not built: the reference's caller uses the default 0")
     ctx = ctx or _native.default_context()
-    I = np.ascontiguousarray(I_arr, dtype=np.float64)
-    out = np.empty(I.shape, np.float64)
+    if is_dev(I_arr):
+        if I_arr.dtype != np.float64:
+            raise TypeError("device intensities must be float64")
+        I, out = I_arr, DevArray(I_arr.t.new_empty(I_arr.shape))
+    else:
+        I = np.ascontiguousarray(I_arr, dtype=np.float64)
+        out = np.empty(I.shape, np.float64)
     if I.size == 0:
         return out
     _calls[0] += 1

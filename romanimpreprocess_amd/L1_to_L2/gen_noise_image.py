@@ -4,8 +4,8 @@
 A layer re-runs the whole L1 -> L2 chain on a noise-injected copy of the Level-1 cube and keeps the difference of the
 two slope images.  What runs where
   * both chain runs: ``calibrateimage`` of this package (HIP kernels);
-  * the injection of white read noise into the cube (``:120-134``): ``rip_stage_noise_inject`` (HIP kernel; exact given the
-    normal deviates);
+  * the injection of white read noise into the cube (``:120-134``): ``inject_read_noise`` (HIP kernel of ``csrc/noise.hip``;
+    exact given the normal deviates);
   * clipping (``z``) and sky-mode removal (``S``): ``utils/sky.py`` (HIP kernels);
 Random numbers.  The reference draws from ``galsim`` generators, which are not available offline and whose streams cannot be
 reproduced; here ``rng`` may be ``None`` / an integer seed (deviates drawn ON THE DEVICE from a counter-based generator:
@@ -20,8 +20,10 @@ and handed to the kernel).  Layers are therefore statistically, not bit-wise, co
     with device deviates, the white deviates from the device or, with a host generator, from it in the reference's order
     (``NOISE: {CORRELATED: false}`` switches the step off).
 The pseudo-Poisson layers (``O``): moment ratios on the host (``GalPoisson/find_tilnus.py``), Pearson-family deviates on the
-    device (``rip_stage_pearson``, ``GalPoisson/draw_with_tilnus.py``; parameters pinned by goldens, deviates from the device's
-    counter-based generator).
+    device (``GalPoisson/draw_with_tilnus.draw_from_Pearson``, ``csrc/pearson.hip``; parameters pinned by goldens, deviates from
+    the device's counter-based generator).
+The directives are interpreted by ONE layer loop (``make_noise_cube``); it works on numpy arrays or, by default, on arrays that
+stay in HBM across the layers, through two small back ends that differ in where an array lives and how a chain run is invoked.
 """
 
 import re
@@ -31,9 +33,9 @@ from copy import deepcopy
 import numpy as np
 
 from .. import _native, calio, pars
+from ..devarray import DevArray, is_dev
 from ..utils import sky
 from .GalPoisson.draw_with_tilnus import draw_from_Pearson
-from .GalPoisson.draw_with_tilnus import _seed_from as draw_seed
 from .GalPoisson.find_tilnus import get_tilde_nus
 from .gen_cal_image import calibrateimage
 
@@ -46,19 +48,23 @@ def _get_subscript(arr, ch):
 
 def inject_read_noise(data, read_noise, read_pattern, nb=pars.nborder, normals=None, seed=0, layer=0, ctx=None):
     """White read noise into a u16 cube (gen_noise_image.py:120-134).  ``normals`` (ngrp, ny-2nb, nx-2nb) f32 or None
-    (drawn on the device from ``seed``, ``layer``)."""
+    (drawn on the device from ``seed``, ``layer``).  Host arrays give a new cube; a ``DevArray`` cube (u16 bits in an int16
+    tensor; the read-noise plane may be one too) is updated in place and returned."""
     ctx = ctx or _native.default_context()
-    data = np.ascontiguousarray(data)
+    if not is_dev(data):
+        data = np.ascontiguousarray(data)
     if data.dtype != np.uint16:
         raise TypeError(f"the Level-1 cube is {data.dtype}, expected uint16")
     G, ny, nx = data.shape
-    read = np.ascontiguousarray(read_noise, dtype=np.float32)
+    read = read_noise if is_dev(read_noise) else np.ascontiguousarray(read_noise, dtype=np.float32)
+    if read.dtype != np.float32 or read.size != ny * nx:
+        raise ValueError("the read noise must be a float32 plane of the cube's frame")
     nreads = np.array([len(g) for g in read_pattern], dtype=np.int32)
     if normals is not None:
         normals = np.ascontiguousarray(normals, dtype=np.float32)
         if normals.shape != (G, ny - 2 * nb, nx - 2 * nb):
             raise ValueError(f"normals have shape {normals.shape}")
-    out = np.empty_like(data)
+    out = data if is_dev(data) else np.empty_like(data)   # the entry point allows in == out
     ctx.check(ctx.lib.rip_stage_noise_inject(ctx.h, data.ctypes.data, G, ny, nx, nb, read.ctypes.data, nreads.ctypes.data,
                                              None if normals is None else normals.ctypes.data, int(seed) & (2**64 - 1),
                                              int(layer), out.ctypes.data))
@@ -105,8 +111,7 @@ def poisson_resample(diff, skylevel, gain, frame_time, read_pattern, weights, ha
     """Adds a resampled-Poisson realisation to ``diff`` (f32, in place; gen_noise_image.py:262-331).  ``gain`` already
     clipped; ``samples`` (nsamp, ny, nx) f64 Poisson deviates of mean clip(skylevel*gain*frame_time, 0) or None (device)."""
     ctx = ctx or _native.default_context()
-    from ..devarray import is_dev   # every array may be a DevArray (resident in HBM): the entry point takes either kind of pointer
-
+    # every array may be a DevArray (resident in HBM): the entry point takes either kind of pointer
     if not ((isinstance(diff, np.ndarray) or is_dev(diff)) and diff.dtype == np.float32 and diff.flags.c_contiguous):
         raise TypeError("diff must be a C-contiguous float32 array (updated in place)")
     ngrp = len(read_pattern)
@@ -158,7 +163,7 @@ class _Files:
 
 
 def _device_path_applies(config, rng):
-    """The HBM-resident layer loop runs when the exposures stay in memory, the deviates are the device's and nothing asks for a
+    """The layer loop keeps its arrays in HBM when the exposures stay in memory, the deviates are the device's and nothing asks for a
     host-side ingredient (an ``AREAFACTOR`` file; a ``FITSWCS`` pixel-area map is made on the device and stays there)."""
     if not bool(config["NOISE"].get("IN_MEMORY", True)) or not bool(config["NOISE"].get("DEVICE_RESIDENT", True)):
         return False
@@ -167,345 +172,313 @@ def _device_path_applies(config, rng):
     return "saturation" in config["CALDIR"]
 
 
-def _make_noise_cube_device(config, seed, files, base_tree):
-    """``make_noise_cube`` with every full-frame array resident in HBM across the layers ("natural batch for
-    the GPU"): the Level-1 cube and its dark-based counterpart, the L2 planes the layers refer to, the masks and weights are
-    uploaded ONCE; a layer is then injection -> fresh reference pixels + correlated noise -> the fused chain -> sky model ->
-    difference -> clip / resampled Poisson / pseudo-Poisson -> sky model, all through the same kernels as the host-array path
+class _HostArrays:
+    """Back end of ``make_noise_cube`` on numpy arrays: a chain run is a ``calibrateimage`` call on an L1 tree."""
+
+    ctx = None   # the mirrors take the default context
+
+    def __init__(self, config, files, base_tree, host_rng):
+        self.config, self.tree, self.rng = config, base_tree, host_rng
+        # config["NOISE"]["IN_MEMORY"] (default true): the noise-injected exposures and their L2 images stay in memory instead of going
+        # through the TEMP files of the reference (same arithmetic; a layer then costs its two chain runs and the noise generation,
+        # not four full-frame ASDF round trips); the dark-based reference image of the layers without 'a' is computed once
+        self.in_memory = bool(config["NOISE"].get("IN_MEMORY", True))
+        self.orig = np.asarray(files.roman(config["OUT"])["data"])
+        self.dark_ref = None   # L2 "data" of the dark cube itself
+
+    def up(self, a):
+        return np.ascontiguousarray(a)
+
+    def host(self, a):
+        return a
+
+    def zeros(self):
+        return np.zeros(self.orig.shape, dtype=np.float32)
+
+    def exposure(self, dark):
+        """A fresh copy of the Level-1 cube (or of the dark standing in for it) and of amp33, and the L2 image they refer to."""
+        roman = self.tree["roman"]
+        cube = np.array(roman["data"] if dark is None else dark)
+        a33 = None if roman.get("amp33") is None else np.array(roman["amp33"])
+        if dark is None:
+            return cube, a33, self.orig
+        if not self.in_memory:
+            return cube, a33, self.l2_data(cube, a33, "_refL2.asdf")
+        if self.dark_ref is None:
+            self.dark_ref = self.l2_data(cube, a33)
+        return cube, a33, self.dark_ref
+
+    def l2_data(self, cube, a33, out="_L2.asdf"):
+        roman = dict(self.tree["roman"], data=cube)
+        if a33 is not None:
+            roman["amp33"] = a33
+        tree = dict(self.tree, roman=roman)
+        if self.in_memory:
+            return np.asarray(calibrateimage(dict(self.config, IN=tree, OUT=None))["roman"]["data"])
+        temp = self.config["NOISE"]["TEMP"]
+        calio.write_asdf(temp, tree)
+        config2 = deepcopy(self.config)
+        config2["IN"] = temp
+        config2["OUT"] = temp[:-5] + out
+        calibrateimage(config2)
+        with calio.open_tree(config2["OUT"]) as f_out:
+            return np.array(f_out["roman"]["data"])
+
+    def fill(self, synth, cube, a33, seed):
+        """``L1Synth.fill`` on an upload of the exposure; the white deviates of a host generator are handed in in the reference's
+        order, otherwise everything is drawn on the device."""
+        import torch
+
+        t_cube = torch.from_numpy(np.ascontiguousarray(cube).view(np.int16)).to(synth.dev)
+        t_a33 = None if a33 is None else torch.from_numpy(np.ascontiguousarray(a33).view(np.int16)).to(synth.dev)
+        normals = white33 = None
+        if self.rng is not None:
+            normals = self.rng.standard_normal((cube.shape[0] + 1,) + cube.shape[1:], dtype=np.float32)
+            if t_a33 is not None:
+                white33 = self.rng.standard_normal(tuple(t_a33.shape), dtype=np.float32)
+        synth.fill(t_cube, t_a33, seed, banding=True, normals=normals, white33=white33)
+        synth.ctx.synchronize()
+        return t_cube.cpu().numpy().view(np.uint16), None if t_a33 is None else t_a33.cpu().numpy().view(np.uint16)
+
+    def sub(self, a, b):
+        return a - b
+
+    def clip(self, a, lo, hi):
+        return np.clip(a, lo, hi)
+
+    def product(self, a, b):
+        return a * b
+
+    def add_ratio(self, diff, noise, gain):
+        return (diff + noise / gain).astype(np.float32)   # f32 array += (f32 / gain dtype), cast back
+
+    def pixels(self, endslice, k):
+        pix = np.where(endslice == k)
+        return pix, len(pix[0])
+
+    def take(self, a, pix):
+        return a[pix]
+
+    def put(self, a, pix, values):
+        a[pix] = values
+
+
+class _DeviceArrays:
+    """Back end of ``make_noise_cube`` with every full-frame array resident in HBM across the layers ("natural
+    batch for the GPU"): the Level-1 cube and its dark-based counterpart, the L2 planes the layers refer to, the masks and weights
+    are uploaded ONCE; a layer is then injection -> fresh reference pixels + correlated noise -> the fused chain -> sky model ->
+    difference -> clip / resampled Poisson / pseudo-Poisson -> sky model, all through the same kernels as with host arrays
     (whose results it reproduces bit for bit: tests/test_gpu_noise.py), with only the finished layer (67 MB) going back to the
     host.  The few scalar steps (percentile interpolation, the 6 x 6 normal equations of the sky model, the moment ratios of the
-    pseudo-Poisson layers) stay on the host as in the mirrors."""
-    import torch
+    pseudo-Poisson layers) stay on the host as in the mirrors.  Arrays are ``DevArray``s whose torch work is complete (the
+    library runs on its own stream)."""
 
-    from .. import pipeline
-    from ..devarray import DevArray
-    from ..from_sim.sim_to_isim import L1Synth
-    from .gen_cal_image import _caldir_slot, wcs_from_config
+    def __init__(self, config, files, base_tree, read_pattern):
+        import torch
 
-    layers = config["NOISE"]["LAYER"]
-    nb = pars.nborder
-    caldir = config["CALDIR"]
-    cb = pipeline.Calibrator()
-    ctx = cb.ctx
-    slot = _caldir_slot(cb, caldir)
-    dev = torch.device("cuda", ctx.device)
-    roman = base_tree["roman"]
-    read_pattern = [list(map(int, g)) for g in roman["meta"]["exposure"]["read_pattern"]]
-    frame_time = float(roman["meta"]["exposure"]["frame_time"])
-    exclude_first = config.get("EXCLUDE_FIRST", True)
-    pid, _meta = cb.plan_for(read_pattern, frame_time, exclude_first, config.get("RAMP_OPT_PARS"), config.get("JUMP_DETECT_PARS"))
-    backup = config.get("SATURATION_BACKUP", 1)
-    skyorder = int(config["SKYORDER"]) if "SKYORDER" in config else None
+        from .. import pipeline
+        from .gen_cal_image import _caldir_slot, wcs_from_config
 
-    def up(a, view=None):
-        a = np.ascontiguousarray(a)
-        return torch.from_numpy(a.view(view) if view is not None else a).to(dev)
+        self.torch = torch
+        caldir, roman = config["CALDIR"], base_tree["roman"]
+        self.cb = cb = pipeline.Calibrator()
+        self.ctx = cb.ctx
+        self.slot = _caldir_slot(cb, caldir)
+        self.dev = torch.device("cuda", self.ctx.device)
+        self.read_pattern = read_pattern
+        self.pid, _meta = cb.plan_for(read_pattern, float(roman["meta"]["exposure"]["frame_time"]), config.get("EXCLUDE_FIRST", True),
+                                      config.get("RAMP_OPT_PARS"), config.get("JUMP_DETECT_PARS"))
+        self.backup = config.get("SATURATION_BACKUP", 1)
+        self.skyorder = int(config["SKYORDER"]) if "SKYORDER" in config else None
+        self.cube = self.up(roman["data"])
+        self.a33 = None if roman.get("amp33") is None else self.up(roman["amp33"])
+        _G, ny, nx = self.cube.shape
+        if "mask" in caldir:
+            self.mask = self.up(np.array(files.roman(caldir["mask"])["dq"], dtype=np.uint32).view(np.int32))
+        else:
+            self.mask = self._done(torch.zeros((ny, nx), dtype=torch.int32, device=self.dev))
+        thewcs = wcs_from_config(config)   # AreaFactor in HBM, the same map calibrateimage divides by
+        self.area = None if thewcs is None else cb.area_factor(thewcs, ny, nx, device=True)
+        self.orig = self.up(np.asarray(files.roman(config["OUT"])["data"], dtype=np.float32))
+        self.outs = [torch.empty((ny, nx), dtype=torch.float32, device=self.dev) for _ in range(3)] + \
+                    [torch.empty((ny, nx), dtype=torch.int32, device=self.dev)]
+        self.dark_ref = None
 
-    base_cube = np.ascontiguousarray(roman["data"])
-    if base_cube.dtype != np.uint16:
-        return None   # the chain's u16 path is what this loop drives; anything else takes the host-array path
-    G, ny, nx = base_cube.shape
-    t_base = up(base_cube, np.int16)
-    t_a33_base = up(roman["amp33"], np.int16) if roman.get("amp33") is not None else None
-    if "mask" in caldir:
-        t_mask = up(np.array(files.roman(caldir["mask"])["dq"], dtype=np.uint32), np.int32)
-    else:
-        t_mask = torch.zeros((ny, nx), dtype=torch.int32, device=dev)
-    read = np.asarray(files.roman(caldir["read"])["data"], dtype=np.float32)
-    t_read = up(read)
-    thewcs = wcs_from_config(config)   # AreaFactor in HBM, the same map calibrateimage divides by
-    t_area = None if thewcs is None else cb.area_factor(thewcs, ny, nx, device=True)
-    area_ptr = None if t_area is None else t_area.data_ptr()
-    nreads = np.array([len(g) for g in read_pattern], dtype=np.int32)
-    l2 = files.tree(config["OUT"])
-    t_orig = up(np.asarray(l2["roman"]["data"], dtype=np.float32))
-    na = tuple(t_orig.shape)
-    outs = [torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((ny, nx), dtype=torch.int32, device=dev)]
-    synth_dev = None
-    t_dark = t_dark_ref = None
-    t_gain_act = t_withsky = t_endslice = None
-    sky_models = {}
-    noiseimage = np.zeros((len(layers),) + na, dtype=np.float32)
+    def _done(self, t, dtype=None):
+        return DevArray(t.contiguous(), dtype).sync()
 
-    def tsync():
-        torch.cuda.current_stream(dev).synchronize()
+    def up(self, a):
+        a = np.ascontiguousarray(a)   # u16 bits travel in an int16 tensor
+        return self._done(self.torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(self.dev), a.dtype)
 
-    def l2_data(t_cube, t_a33):
+    def host(self, a):
+        return a.numpy()
+
+    def zeros(self):
+        return self._done(self.torch.zeros(self.orig.shape, dtype=self.torch.float32, device=self.dev))
+
+    def exposure(self, dark):
+        """A clone of the Level-1 cube (or of the dark standing in for it) and of amp33, and the L2 image they refer to."""
+        cube = self._done((self.cube if dark is None else dark).t.clone(), np.uint16)
+        a33 = None if self.a33 is None else self._done(self.a33.t.clone(), np.uint16)
+        if dark is None:
+            return cube, a33, self.orig
+        if self.dark_ref is None:
+            self.dark_ref = self.l2_data(dark, self.a33)
+        return cube, a33, self.dark_ref
+
+    def l2_data(self, cube, a33):
         """roman.data of calibrateimage for a device-resident exposure: the chain, the active region, minus the sky model"""
-        tsync()
-        cb.calibrate_device(slot, pid, G, t_cube.data_ptr(), True, None if t_a33 is None else t_a33.data_ptr(), None, t_mask.data_ptr(),
-                            outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), area_ptr=area_ptr,
-                            flag_saturation=True, saturation_backup=backup, read_pattern=read_pattern)
-        cb.synchronize()
-        data = outs[0][nb:ny - nb, nb:nx - nb].contiguous()
-        if skyorder is not None:
-            tsync()
-            sky.medfit(DevArray(data), order=skyorder, subtract=True, ctx=ctx, want_model=False)
+        nb, o = pars.nborder, self.outs
+        G, ny, nx = cube.shape
+        self.cb.calibrate_device(self.slot, self.pid, G, cube.ctypes.data, True, None if a33 is None else a33.ctypes.data, None,
+                                 self.mask.ctypes.data, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(),
+                                 area_ptr=None if self.area is None else self.area.data_ptr(), flag_saturation=True,
+                                 saturation_backup=self.backup, read_pattern=self.read_pattern)
+        self.cb.synchronize()
+        data = self._done(o[0][nb:ny - nb, nb:nx - nb])
+        if self.skyorder is not None:
+            sky.medfit(data, order=self.skyorder, subtract=True, ctx=self.ctx, want_model=False)
         return data
 
-    for i_noise, cmd in enumerate(layers):
-        diff = torch.zeros(na, dtype=torch.float32, device=dev)
-        if "R" in cmd:
-            noiseflags = _get_subscript(cmd, "R")
-            t_ref = t_orig
-            t_cube = t_base.clone()
-            t_a33 = None if t_a33_base is None else t_a33_base.clone()
-            if "a" not in noiseflags:   # start from the dark instead of the data
-                if t_dark is None:
-                    dark = np.asarray(files.roman(caldir["dark"])["data"])
-                    de = dark.shape[0] - G
-                    if de not in [0, 1]:
-                        raise ValueError("Dark date cube has the wrong shape.")
-                    t_dark = up(dark.astype(np.uint16)[de:], np.int16)
-                    t_dark_ref = l2_data(t_dark, t_a33_base)
-                t_cube = t_dark.clone()
-                t_ref = t_dark_ref
-            tsync()
-            ctx.check(ctx.lib.rip_stage_noise_inject(ctx.h, t_cube.data_ptr(), G, ny, nx, nb, t_read.data_ptr(), nreads.ctypes.data, None,
-                                                     int(seed) & (2**64 - 1), int(i_noise), t_cube.data_ptr()))
-            if synth_dev is None:
-                cal_fill = {k: files.roman(caldir[k]) for k in ("read", "gain", "dark")}
-                synth_dev = L1Synth(cal_fill, read_pattern, 1.0, ctx=ctx, nb=nb)
-            synth_dev.fill(t_cube, t_a33, (int(seed) + 7919 * (i_noise + 1)) & (2**64 - 1), banding=True)
-            diff = l2_data(t_cube, t_a33) - t_ref
-            if "z" in noiseflags:
-                zclip = float(_get_subscript(noiseflags.upper(), "Z"))
-                tsync()
-                p25, med, p75 = sky.nanpercentiles(DevArray(diff), [25.0, 50.0, 75.0], ctx=ctx)
-                iqr = p75 - p25
-                print("***", noiseflags, zclip, iqr, med)
-                diff = torch.clamp(diff, float(med - zclip * iqr / 1.34896), float(med + zclip * iqr / 1.34896))
-        if "O" in cmd or "P" in cmd:
-            pinfo = l2["processinfo"]
-            if t_withsky is None:
-                gain = np.clip(np.asarray(files.roman(caldir["gain"])["data"]), 1e-4, 1e4)
-                withsky = np.asarray(l2["roman"]["data_withsky"], dtype=np.float32)
-                d = (gain.shape[-1] - withsky.shape[-1]) // 2
-                gain_act = np.ascontiguousarray(gain[d:-d, d:-d] if d > 0 else gain)
-                t_gain_act, t_withsky = up(gain_act), up(withsky)
-                w_all, has_all, endslice = ramp_weight_vectors(pinfo, G)
-                t_endslice = up(endslice)
-        if "O" in cmd:
-            # pseudo-Poisson layer (gen_noise_image.py:173-240): the moment ratios per end slice on the host, one Pearson deviate per
-            # pixel of that end slice on the device, scaled by the pixel's gain * rate
-            t_fr = l2["roman"]["meta"]["exposure"]["frame_time"]
-            gI = t_gain_act.to(torch.float64) * t_withsky.to(torch.float64) if t_gain_act.dtype == torch.float64 else \
-                (t_gain_act * t_withsky).to(torch.float64)
-            start = 1 if pinfo["exclude_first"] else 0
-            rp_l2 = pinfo["meta"].get("read_pattern", read_pattern)
-            a_beta = np.array([rp_l2[k][0] for k in range(G)], dtype=int)
-            N_beta = np.array([len(rp_l2[k]) for k in range(G)], dtype=int)
-            noise_array = torch.zeros(na, dtype=torch.float32, device=dev)
-            for k in range(start + 1, G):
-                tilnu21, tilnu31, tilnu41, _tilnu42 = get_tilde_nus(N_beta, a_beta, w_all[k])
-                tilnu21 *= t_fr
-                tilnu31 *= t_fr**2
-                tilnu41 *= t_fr**3
-                sel = torch.nonzero(t_endslice == k, as_tuple=True)
-                npx = int(sel[0].numel())
-                print("n pix", npx, "tilnus", tilnu21, tilnu31, tilnu41)
-                sys.stdout.flush()
-                if npx:
-                    t_I = gI[sel].contiguous()
-                    t_draw = torch.empty_like(t_I)
-                    tsync()
-                    ctx.check(ctx.lib.rip_stage_pearson(
-                        ctx.h, npx, t_I.data_ptr(), float(tilnu21), float(tilnu31), float(tilnu41),
-                        draw_seed(np.random.default_rng([int(seed) & 0xFFFFFFFF, i_noise, k])), (100 * (i_noise + 1) + k) & 0xFFFFFFFF,
-                        t_draw.data_ptr(), None, None))
-                    noise_array[sel] = t_draw.to(torch.float32)
-            diff = (diff + noise_array / t_gain_act).to(torch.float32)   # numpy: f32 array += (f32 / gain dtype), cast back
-        if "P" in cmd:
-            noiseflags = _get_subscript(cmd, "P")
-            t_fr = roman["meta"]["exposure"]["frame_time"]
-            if "b" in noiseflags:   # background only: the low-order sky model (one per order for the whole list)
-                sky_order = int("0" + _get_subscript(noiseflags.upper(), "B"))
-                if sky_order not in sky_models:
-                    sky_models[sky_order] = up(sky.medfit(DevArray(t_withsky), order=sky_order, ctx=ctx)[1])
-                skylevel = sky_models[sky_order]
-            else:
-                skylevel = t_withsky.clone()
-            if "r" in noiseflags:
-                diff = diff.contiguous()
-                tsync()
-                poisson_resample(DevArray(diff), DevArray(skylevel), DevArray(t_gain_act), t_fr, read_pattern, w_all, has_all,
-                                 DevArray(t_endslice), seed=seed, layer=1000 + i_noise, ctx=ctx)
-        if "S" in cmd:
-            sky_order = int("0" + _get_subscript(cmd, "S"))
-            diff = diff.contiguous()
-            tsync()
-            sky.medfit(DevArray(diff), order=sky_order, subtract=True, ctx=ctx, want_model=False)
-        noiseimage[i_noise] = diff.cpu().numpy()
-    return noiseimage
+    def fill(self, synth, cube, a33, seed):
+        synth.fill(cube.t, None if a33 is None else a33.t, seed, banding=True)   # in place, on the context's stream like the chain
+        return cube, a33
+
+    def sub(self, a, b):
+        return self._done(a.t - b.t)
+
+    def clip(self, a, lo, hi):
+        return self._done(self.torch.clamp(a.t, float(lo), float(hi)))
+
+    def product(self, a, b):
+        return self._done((a.t * b.t).to(self.torch.float64))   # promoted like numpy's product, then the f64 the draws take
+
+    def add_ratio(self, diff, noise, gain):
+        return self._done((diff.t + noise.t / gain.t).to(self.torch.float32))   # numpy: f32 array += (f32 / gain dtype), cast back
+
+    def pixels(self, endslice, k):
+        pix = self.torch.nonzero(endslice.t == k, as_tuple=True)
+        return pix, int(pix[0].numel())
+
+    def take(self, a, pix):
+        return self._done(a.t[pix])
+
+    def put(self, a, pix, values):
+        a.t[pix] = values.t.to(a.t.dtype)
+        a.sync()
 
 
 def make_noise_cube(config, rng=None):
-    """The noise realisations listed in ``config["NOISE"]["LAYER"]``: array (N_noise, ny_active, nx_active) f32."""
+    """The noise realisations listed in ``config["NOISE"]["LAYER"]``: array (N_noise, ny_active, nx_active) f32.  One layer loop;
+    where the arrays live (numpy, or HBM when ``_device_path_applies``) and how a chain run is invoked is the back end's."""
     layers = config["NOISE"]["LAYER"]
+    caldir = config["CALDIR"]
     files = _Files()
-    if _device_path_applies(config, rng):
-        with calio.open_tree(config["IN"]) as f_in:
-            base_tree_ = calio._materialise(f_in if isinstance(f_in, dict) else dict(f_in))
-        seed_ = config["NOISE"].get("SEED", 0) if rng is None else int(rng)
-        got = _make_noise_cube_device(config, seed_, files, base_tree_)
-        if got is not None:
-            return got
-    synth_dev = None   # from_sim.sim_to_isim.L1Synth of this CALDIR set: reference pixels and correlated noise on the device
     host_rng = rng if isinstance(rng, np.random.Generator) else None
     seed = config["NOISE"].get("SEED", 0) if (rng is None or host_rng is not None) else int(rng)
     nb = pars.nborder
-    noiseimage = None
-    # config["NOISE"]["IN_MEMORY"] (default true): the noise-injected exposures and their L2 images stay in memory instead of going
-    # through the TEMP files of the reference (same arithmetic; a layer then costs its two chain runs and the noise generation,
-    # not four full-frame ASDF round trips); the dark-based reference image of the layers without 'a' is computed once
-    in_memory = bool(config["NOISE"].get("IN_MEMORY", True))
     with calio.open_tree(config["IN"]) as f_in:
         base_tree = calio._materialise(f_in if isinstance(f_in, dict) else dict(f_in))
-    orig_data = np.asarray(files.roman(config["OUT"])["data"])
-    dark_ref = None   # L2 "data" of the dark cube itself
+    exposure = base_tree["roman"]["meta"]["exposure"]
+    read_pattern = [list(map(int, g)) for g in exposure["read_pattern"]]
+    ngrp = len(read_pattern)
+    cube_dtype = np.asarray(base_tree["roman"]["data"]).dtype
+    # the chain's u16 path is what the HBM-resident back end drives; a cube of anything else stays on the host
+    if _device_path_applies(config, rng) and cube_dtype == np.uint16:
+        be = _DeviceArrays(config, files, base_tree, read_pattern)
+    else:
+        be = _HostArrays(config, files, base_tree, host_rng)
+    read = be.up(np.asarray(files.roman(caldir["read"])["data"], dtype=np.float32))
+    dark = synth = gain = None   # dark cube as data; from_sim.sim_to_isim.L1Synth of this CALDIR set; the inputs of 'O' and 'P' layers
+    sky_models = {}
+    noiseimage = np.zeros((len(layers),) + be.orig.shape, dtype=np.float32)
     for i_noise, cmd in enumerate(layers):
-        mytree = {k: v for k, v in base_tree.items()}
-        mytree["roman"] = {k: (v.copy() if k in ("data", "amp33") and isinstance(v, np.ndarray) else v)
-                           for k, v in base_tree["roman"].items()}
-        diff = np.zeros_like(orig_data)
-        if noiseimage is None:
-            noiseimage = np.zeros((len(layers),) + diff.shape, dtype=np.float32)
-        read_pattern = mytree["roman"]["meta"]["exposure"]["read_pattern"]
-
+        diff = be.zeros()
         if "R" in cmd:
             noiseflags = _get_subscript(cmd, "R")
-            ref_data = orig_data
-            if "a" not in noiseflags:  # start from the dark instead of the data
-                dark = np.asarray(files.roman(config["CALDIR"]["dark"])["data"])
-                de = dark.shape[0] - np.shape(mytree["roman"]["data"])[0]
+            if "a" not in noiseflags and dark is None:  # start from the dark instead of the data
+                d = np.asarray(files.roman(caldir["dark"])["data"])
+                de = d.shape[0] - ngrp
                 if de not in [0, 1]:
                     raise ValueError("Dark date cube has the wrong shape.")
-                mytree["roman"]["data"] = dark.astype(mytree["roman"]["data"].dtype)[de:, :, :]
-                if in_memory:
-                    if dark_ref is None:
-                        dark_ref = np.asarray(calibrateimage(dict(config, IN=mytree, OUT=None))["roman"]["data"])
-                    ref_data = dark_ref
-                else:
-                    calio.write_asdf(config["NOISE"]["TEMP"], mytree)
-                    config3 = deepcopy(config)
-                    config3["IN"] = config["NOISE"]["TEMP"]
-                    config3["OUT"] = config["NOISE"]["TEMP"][:-5] + "_refL2.asdf"
-                    calibrateimage(config3)
-                    with calio.open_tree(config3["OUT"]) as f_ref:
-                        ref_data = np.asarray(f_ref["roman"]["data"])
-            read = np.asarray(files.roman(config["CALDIR"]["read"])["data"], dtype=np.float32)
-            data = np.ascontiguousarray(mytree["roman"]["data"])
+                dark = be.up(d.astype(cube_dtype)[de:, :, :])
+            cube, a33, ref_data = be.exposure(None if "a" in noiseflags else dark)
             normals = None
             if host_rng is not None:  # one draw per group, in the reference's order
-                na = (data.shape[1] - 2 * nb, data.shape[2] - 2 * nb)
-                normals = np.stack([host_rng.standard_normal(na, dtype=np.float32) for _ in range(data.shape[0])])
-            mytree["roman"]["data"] = inject_read_noise(data, read, read_pattern, nb=nb, normals=normals, seed=seed,
-                                                        layer=i_noise)
+                na = (cube.shape[1] - 2 * nb, cube.shape[2] - 2 * nb)
+                normals = np.stack([host_rng.standard_normal(na, dtype=np.float32) for _ in range(cube.shape[0])])
+            cube = inject_read_noise(cube, read, read_pattern, nb=nb, normals=normals, seed=seed, layer=i_noise, ctx=be.ctx)
             # correlated noise: fresh reference pixels, reference output and 1/f noise (sim_to_isim.fill_in_refdata_and_1f), on the
-            # device (from_sim.sim_to_isim.L1Synth.fill: the white deviates of a host generator are handed in in the reference's
-            # order, otherwise everything is drawn there)
+            # device (from_sim.sim_to_isim.L1Synth.fill)
             if config["NOISE"].get("CORRELATED", True):
-                import torch
+                if synth is None:
+                    from ..from_sim.sim_to_isim import L1Synth
 
-                from ..from_sim.sim_to_isim import L1Synth
-
-                if synth_dev is None:
-                    cal_fill = {k: files.roman(config["CALDIR"][k]) for k in ("read", "gain", "dark")}
-                    synth_dev = L1Synth(cal_fill, read_pattern, 1.0, nb=nb)
-                cube = np.ascontiguousarray(mytree["roman"]["data"])
-                a33 = mytree["roman"].get("amp33")
-                t_cube = torch.from_numpy(cube.view(np.int16)).to(synth_dev.dev)
-                t_a33 = None if a33 is None else torch.from_numpy(np.ascontiguousarray(a33).view(np.int16)).to(synth_dev.dev)
-                normals = white33 = None
-                if host_rng is not None:
-                    normals = host_rng.standard_normal((cube.shape[0] + 1,) + cube.shape[1:], dtype=np.float32)
-                    if t_a33 is not None:
-                        white33 = host_rng.standard_normal(tuple(t_a33.shape), dtype=np.float32)
-                synth_dev.fill(t_cube, t_a33, (int(seed) + 7919 * (i_noise + 1)) & (2**64 - 1), banding=True, normals=normals,
-                               white33=white33)
-                synth_dev.ctx.synchronize()
-                mytree["roman"]["data"] = t_cube.cpu().numpy().view(np.uint16)
-                if t_a33 is not None:
-                    mytree["roman"]["amp33"] = t_a33.cpu().numpy().view(np.uint16)
-            if in_memory:
-                diff = np.asarray(calibrateimage(dict(config, IN=mytree, OUT=None))["roman"]["data"]) - ref_data
-            else:
-                calio.write_asdf(config["NOISE"]["TEMP"], mytree)
-                config2 = deepcopy(config)
-                config2["IN"] = config["NOISE"]["TEMP"]
-                config2["OUT"] = config["NOISE"]["TEMP"][:-5] + "_L2.asdf"
-                calibrateimage(config2)
-                with calio.open_tree(config2["OUT"]) as f_out:
-                    diff = np.asarray(f_out["roman"]["data"]) - ref_data
+                    synth = L1Synth({k: files.roman(caldir[k]) for k in ("read", "gain", "dark")}, read_pattern, 1.0, ctx=be.ctx, nb=nb)
+                cube, a33 = be.fill(synth, cube, a33, (int(seed) + 7919 * (i_noise + 1)) & (2**64 - 1))
+            diff = be.sub(be.l2_data(cube, a33), ref_data)
             if "z" in noiseflags:
                 zclip = float(_get_subscript(noiseflags.upper(), "Z"))
-                p25, med, p75 = sky.nanpercentiles(diff, [25.0, 50.0, 75.0])
+                p25, med, p75 = sky.nanpercentiles(diff, [25.0, 50.0, 75.0], ctx=be.ctx)
                 iqr = p75 - p25
                 print("***", noiseflags, zclip, iqr, med)
-                diff = np.clip(diff, med - zclip * iqr / 1.34896, med + zclip * iqr / 1.34896)
+                diff = be.clip(diff, med - zclip * iqr / 1.34896, med + zclip * iqr / 1.34896)
+        if ("O" in cmd or "P" in cmd) and gain is None:
+            l2 = files.tree(config["OUT"])
+            pinfo = l2["processinfo"]
+            g = np.clip(np.asarray(files.roman(caldir["gain"])["data"]), 1e-4, 1e4)
+            ws = np.asarray(l2["roman"]["data_withsky"], dtype=np.float32)
+            d = (g.shape[-1] - ws.shape[-1]) // 2
+            gain, withsky = be.up(g[d:-d, d:-d] if d > 0 else g), be.up(ws)
+            w_all, has_all, es = ramp_weight_vectors(pinfo, ngrp)
+            endslice = be.up(es)
         if "O" in cmd:
             # pseudo-Poisson layer (gen_noise_image.py:173-240): per end slice, the moment ratios of the ramp-fit slope under
-            # Poisson noise (host), then one Pearson-family deviate per pixel (device) scaled by the pixel's gain * rate
-            gain = np.clip(np.asarray(files.roman(config["CALDIR"]["gain"])["data"]), 1e-4, 1e4)
-            f_L2 = files.tree(config["OUT"])
-            withsky = np.asarray(f_L2["roman"]["data_withsky"])
-            pinfo = f_L2["processinfo"]
-            t_fr = f_L2["roman"]["meta"]["exposure"]["frame_time"]
-            d = (gain.shape[-1] - withsky.shape[-1]) // 2
-            if d > 0:
-                gain = gain[d:-d, d:-d]
-            gI = gain * withsky
-            ngrp_o = len(read_pattern)
-            w, _has, endslice = ramp_weight_vectors(pinfo, ngrp_o)
+            # Poisson noise (host), then one Pearson-family deviate per pixel of that end slice (device) scaled by the pixel's
+            # gain * rate
+            t_fr = l2["roman"]["meta"]["exposure"]["frame_time"]   # from the L2 file, like the read pattern below
+            gI = be.product(gain, withsky)
             start = 1 if pinfo["exclude_first"] else 0
             rp_l2 = pinfo["meta"].get("read_pattern", read_pattern)   # from the L2 file, as gen_noise_image.py:208-212 reads it
-            a_beta = np.array([rp_l2[k][0] for k in range(ngrp_o)], dtype=int)
-            N_beta = np.array([len(rp_l2[k]) for k in range(ngrp_o)], dtype=int)
-            noise_array = np.zeros(endslice.shape, dtype=np.float32)
-            for k in range(start + 1, ngrp_o):
-                tilnu21, tilnu31, tilnu41, _tilnu42 = get_tilde_nus(N_beta, a_beta, w[k])
+            a_beta = np.array([rp_l2[k][0] for k in range(ngrp)], dtype=int)
+            N_beta = np.array([len(rp_l2[k]) for k in range(ngrp)], dtype=int)
+            noise_array = be.zeros()
+            for k in range(start + 1, ngrp):
+                tilnu21, tilnu31, tilnu41, _tilnu42 = get_tilde_nus(N_beta, a_beta, w_all[k])
                 tilnu21 *= t_fr          # e/frame -> e/s
                 tilnu31 *= t_fr**2
                 tilnu41 *= t_fr**3
-                pixels = np.where(endslice == k)
-                print("n pix", len(pixels[0]), "tilnus", tilnu21, tilnu31, tilnu41)
+                pixels, npx = be.pixels(endslice, k)
+                print("n pix", npx, "tilnus", tilnu21, tilnu31, tilnu41)
                 sys.stdout.flush()
-                if len(pixels[0]):
-                    noise_array[pixels] = draw_from_Pearson(
-                        tilnu21, tilnu31, tilnu41, gI[pixels],
+                if npx:
+                    be.put(noise_array, pixels, draw_from_Pearson(
+                        tilnu21, tilnu31, tilnu41, be.take(gI, pixels),
                         rng=host_rng if host_rng is not None else np.random.default_rng([int(seed) & 0xFFFFFFFF, i_noise, k]),
-                        stream=100 * (i_noise + 1) + k)
-            diff = np.asarray(diff, dtype=np.float32).copy()
-            diff[:, :] += noise_array / gain
+                        stream=100 * (i_noise + 1) + k, ctx=be.ctx))
+            diff = be.add_ratio(diff, noise_array, gain)
         if "P" in cmd:
             noiseflags = _get_subscript(cmd, "P")
-            f_L2 = files.tree(config["OUT"])
-            withsky = np.asarray(f_L2["roman"]["data_withsky"], dtype=np.float32)
-            pinfo = f_L2["processinfo"]
-            t_fr = mytree["roman"]["meta"]["exposure"]["frame_time"]
-            if "b" in noiseflags:  # background only: the low-order sky model
+            t_fr = exposure["frame_time"]   # from the Level-1 file
+            skylevel = withsky
+            if "b" in noiseflags:  # background only: the low-order sky model (one per order for the whole list)
                 sky_order = int("0" + _get_subscript(noiseflags.upper(), "B"))
-                skylevel = sky.medfit(withsky, order=sky_order)[1]
-            else:
-                skylevel = withsky.copy()
+                if sky_order not in sky_models:
+                    sky_models[sky_order] = be.up(sky.medfit(withsky, order=sky_order, ctx=be.ctx)[1])
+                skylevel = sky_models[sky_order]
             if "r" in noiseflags:
-                gain = np.clip(np.asarray(files.roman(config["CALDIR"]["gain"])["data"]), 1e-4, 1e4)
-                d = (gain.shape[-1] - skylevel.shape[-1]) // 2
-                if d > 0:
-                    gain = gain[d:-d, d:-d]
-                w, has, endslice = ramp_weight_vectors(pinfo, len(read_pattern))
                 samples = None
                 if host_rng is not None:
                     e = np.clip(skylevel * gain * t_fr, 0.0, None)
                     samples = np.stack([host_rng.poisson(e.astype(np.float64)).astype(np.float64)
                                         for _ in range(int(read_pattern[-1][-1]) + 1)])
-                diff = np.ascontiguousarray(diff, dtype=np.float32)
-                poisson_resample(diff, skylevel, np.ascontiguousarray(gain), t_fr, read_pattern, w, has, endslice, samples=samples,
-                                 seed=seed, layer=1000 + i_noise)
+                poisson_resample(diff, skylevel, gain, t_fr, read_pattern, w_all, has_all, endslice, samples=samples, seed=seed,
+                                 layer=1000 + i_noise, ctx=be.ctx)
         if "S" in cmd:
             sky_order = int("0" + _get_subscript(cmd, "S"))
-            diff = diff - sky.medfit(diff, order=sky_order)[1]
-        noiseimage[i_noise, :, :] = diff
+            sky.medfit(diff, order=sky_order, subtract=True, ctx=be.ctx, want_model=False)
+        noiseimage[i_noise] = be.host(diff)
     return noiseimage
 
 

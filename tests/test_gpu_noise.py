@@ -162,6 +162,18 @@ def test_noise_layers_end_to_end(tmp_path):
         ratio = np.std(noise[i][use] / predicted[use])
         print('P layer', i, 'scatter / prediction', ratio, 'scatter / err_poisson', np.std(noise[i][good]) / np.sqrt(np.mean(err_p**2)))
         assert 0.95 < ratio < 1.05, (i, ratio)
+    # every directive with a host generator (deviates drawn on the host in the reference's order): equally seeded generators
+    # give the same bits, and the resampled Poisson layers have the predicted variance there as well
+    every = dict(config["NOISE"], LAYER=["Raz3S1", "Pr", "Pb2r", "OS2"])
+    drawn = gen_noise_image.make_noise_cube(dict(config, NOISE=every), np.random.default_rng(3))
+    redrawn = gen_noise_image.make_noise_cube(dict(config, NOISE=every), np.random.default_rng(3))
+    assert_same_bits(redrawn, drawn, "host-generator layers from equally seeded generators")
+    for i, level in ((1, withsky), (2, sky.medfit(withsky, order=2, ctx=gpu_context())[1])):
+        predicted = np.sqrt(k2 * np.clip(level, 0.0, None) * synth.FRAME_TIME / gain_act)
+        use = full & (predicted > 0)
+        ratio = np.std(drawn[i][use] / predicted[use])
+        print('P layer', i, 'with host deviates: scatter / prediction', ratio)
+        assert 0.95 < ratio < 1.05, (i, ratio)
     # pseudo-Poisson layer ('O': Pearson-family deviates with the slope's second to fourth moments under Poisson noise): its
     # scatter is the Poisson error of the slope as well, its mean is zero
     ratio = np.std(noise[7][good]) / np.sqrt(np.mean(err_p**2))
