@@ -322,12 +322,13 @@ int rip_stage_bin_mean(rip_ctx *ctx, const float *arr, const uint8_t *mask, int 
 /* Order statistics ignoring NaN, per block of ky x kx pixels (nby x nbx blocks from (y0,x0)) of an (ny,nx) f32 image:
    the building block of np.nanpercentile (sky.py:72-74) and of the block nan-medians of medfit (sky.py:152).
    counts[blk] = non-NaN elements; vals[blk*nranks + r] = element of 0-based ascending rank ranks[blk*nranks + r] (NaN
-   when out of range).  ranks may be NULL with nranks = 0 (counts only).  Exact. */
+   when out of range).  ranks may be NULL with nranks = 0 (counts only).  Exact.  At most 65535 blocks (nby * nbx) a call:
+   more is RIP_EINVAL. */
 int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y0, int x0, int ky, int kx, int nby, int nbx,
                            int nranks, const int64_t *ranks, int64_t *counts, float *vals);
 
 /* smoothed histogram of smooth_mode (sky.py:80-84): out[i] = sum over non-NaN x of exp(-0.5 ((z[i]-x)/scale)^2), nz <= 32,
-   f64 (summation order differs from numpy: ~1e-13 relative). */
+   f64 (summation order differs from numpy: ~1e-13 relative; it is fixed, so a call is reproducible to the bit). */
 int rip_stage_gauss_hist(rip_ctx *ctx, const float *arr, int64_t n, const double *z, int nz, double scale, double *out);
 
 /* Legendre model of medfit (sky.py:183-191): model = f32(sum_k coef[k] * outer(LPY[j_k], LPX[i_k])) accumulated in f64 in

@@ -30,6 +30,10 @@ def build_mask(dq, growth=PIXELMASK1):
     mask = np.zeros(dq.shape, dtype=bool)
     for bit, grow in growth.items():
         layer = (dq & np.uint32(1 << bit)) != 0
+        if grow not in (0, 1, 5, 9, 25):
+            raise ValueError(f"growth {grow} of bit {bit} is not one of 0, 1, 5, 9, 25")
+        if grow == 0:
+            continue
         if grow == 1:
             mask |= layer
             continue
@@ -97,7 +101,8 @@ def medfit(arr, N=8, order=2):
 
 
 def endslice(rdq, nb):
-    act = (slice(nb, -nb), slice(nb, -nb))
+    ny, nx = rdq.shape[1:]
+    act = (slice(nb, ny - nb), slice(nb, nx - nb))   # not slice(nb, -nb): nb = 0 keeps the whole plane
     out = np.zeros(rdq[0][act].shape, dtype=np.int8) - 1
     for iend in range(1, rdq.shape[0]):
         first = ((rdq[iend][act] & ~rdq[iend - 1][act]) & np.uint8(2)) != 0

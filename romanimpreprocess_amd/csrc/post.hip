@@ -81,6 +81,7 @@ __global__ __launch_bounds__(256) void bin_mean_kernel(const float *__restrict__
 // Blocks: nby x nbx rectangles of ky x kx pixels starting at (y0, x0) of an (ny, nx) f32 image.  NaNs are ignored.
 // Three radix levels (11 + 11 + 10 bits) on the order-preserving integer image of the float.
 #define PS_BINS 2048
+#define PS_MAX_BLOCKS 65535   // grid.y of the histogram launches
 __device__ __forceinline__ uint32_t ps_key(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -148,9 +149,11 @@ __global__ void ps_finish_kernel(const uint32_t *__restrict__ prefix, float *__r
 }
 
 // ------------------------------------------------------------------------------------------ smoothed histogram
-// out[i] = sum over the non-NaN x of exp(-0.5 ((z[i] - x) / scale)^2), i < nz <= 32, in f64
+// out[i] = sum over the non-NaN x of exp(-0.5 ((z[i] - x) / scale)^2), i < nz <= 32, in f64.  Two steps without atomics, so
+// that the order of the sum -- and with it every bit of the result -- is the same from run to run: each workgroup leaves
+// its partial sums in part[block * nz + i], gauss_hist_finish_kernel adds them in block order.
 __global__ __launch_bounds__(256) void gauss_hist_kernel(const float *__restrict__ arr, size_t n, const double *__restrict__ z, int nz,
-                                                         double scale, double *__restrict__ out) {
+                                                         double scale, double *__restrict__ part) {
     __shared__ double red[256];
     double acc[32];
     for (int i = 0; i < 32; ++i) acc[i] = 0.0;
@@ -170,9 +173,17 @@ __global__ __launch_bounds__(256) void gauss_hist_kernel(const float *__restrict
             if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
             __syncthreads();
         }
-        if (threadIdx.x == 0) atomicAdd(&out[i], red[0]);
+        if (threadIdx.x == 0) part[(size_t)blockIdx.x * nz + i] = red[0];
         __syncthreads();
     }
+}
+
+__global__ void gauss_hist_finish_kernel(const double *__restrict__ part, int nblocks, int nz, double *__restrict__ out) {
+    const int i = threadIdx.x;
+    if (i >= nz) return;
+    double s = 0.0;
+    for (int b = 0; b < nblocks; ++b) s += part[(size_t)b * nz + i];
+    out[i] = s;
 }
 
 // ------------------------------------------------------------------------------------------ Legendre model
@@ -345,6 +356,11 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
     if (!arr || ky < 1 || kx < 1 || nby < 1 || nbx < 1 || y0 < 0 || x0 < 0 || y0 + (long)nby * ky > ny || x0 + (long)nbx * kx > nx ||
         nranks < 0 || (nranks > 0 && (!ranks || !vals)))
         return rip_fail(ctx, RIP_EINVAL, "select_ranks: bad geometry or arguments");
+    // the histogram launches index the block by blockIdx.y: more blocks than grid.y can hold would fail at launch and leave
+    // every count 0
+    if ((long)nby * nbx > PS_MAX_BLOCKS)
+        return rip_fail(ctx, RIP_EINVAL, "select_ranks: %ld blocks (%d x %d) is more than the %d one launch can index", (long)nby * nbx,
+                        nby, nbx, PS_MAX_BLOCKS);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const int nblk = nby * nbx;
     const size_t n = (size_t)ny * nx;
@@ -362,6 +378,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
     if (chunks > 1024) chunks = 1024;
     RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * PS_BINS * 4, ctx->stream));
     hipLaunchKernelGGL(ps_hist_kernel, dim3(chunks, nblk), dim3(256), 0, ctx->stream, d.p, g, prefix.p, hist.p, -1);
+    RIP_HIP(ctx, hipGetLastError());
     std::vector<uint32_t> hh((size_t)nblk * PS_BINS);
     if ((rc = hist.download(hh.data(), hh.size())) || (rc = dev_sync(ctx))) return rc;
     std::vector<int64_t> cnt(nblk);
@@ -396,13 +413,15 @@ int rip_stage_gauss_hist(rip_ctx *ctx, const float *arr, int64_t n, const double
     if (!arr || !z || !out || n < 1 || nz < 1 || nz > 32 || !(scale > 0.0)) return rip_fail(ctx, RIP_EINVAL, "gauss_hist: bad arguments");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<float> d(ctx);
-    DevBuf<double> dz(ctx), o(ctx);
-    int rc;
-    if ((rc = d.upload(arr, (size_t)n)) || (rc = dz.upload(z, nz)) || (rc = o.alloc(nz))) return rc;
-    RIP_HIP(ctx, hipMemsetAsync(o.p, 0, (size_t)nz * 8, ctx->stream));
+    DevBuf<double> dz(ctx), part(ctx), o(ctx);
     unsigned blocks = (unsigned)(((size_t)n + 256 * 8 - 1) / (256 * 8));
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(gauss_hist_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d.p, (size_t)n, dz.p, nz, scale, o.p);
+    int rc;
+    if ((rc = d.upload(arr, (size_t)n)) || (rc = dz.upload(z, nz)) || (rc = part.alloc((size_t)blocks * nz)) || (rc = o.alloc(nz)))
+        return rc;
+    hipLaunchKernelGGL(gauss_hist_kernel, dim3(blocks), dim3(256), 0, ctx->stream, d.p, (size_t)n, dz.p, nz, scale, part.p);
+    RIP_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(gauss_hist_finish_kernel, dim3(1), dim3(32), 0, ctx->stream, part.p, (int)blocks, nz, o.p);
     RIP_HIP(ctx, hipGetLastError());
     if ((rc = o.download(out, nz))) return rc;
     return dev_sync(ctx);

@@ -94,7 +94,8 @@ def smooth_mode(arr, pc=25.0, pksmooth=0.5, niter=3, ctx=None):
 
     Start: centre = median, sigma from the inter-percentile range of a Gaussian.  Each iteration evaluates the
     Gaussian-smoothed density on the 19 interior nodes of a 21-node grid over centre +- sigma (GPU reduction over the
-    image) and moves the centre to the vertex of the parabola through the highest node and its two neighbours."""
+    image) and moves the centre to the vertex of the parabola through the highest node and its two neighbours.  An image
+    without spread (constant: sigma = 0; no valid pixel: sigma = NaN) has mode NaN, as in the reference."""
     ctx = ctx or _native.default_context()
     img = _f32(arr)
     p_lo, p_mid, p_hi = nanpercentiles(img, (pc, 50.0, 100.0 - pc), ctx=ctx)
@@ -102,6 +103,11 @@ def smooth_mode(arr, pc=25.0, pksmooth=0.5, niter=3, ctx=None):
     centre = p_mid
     nodes = 21
     for _ in range(niter):
+        if not sigma > 0:
+            # a constant (sigma = 0) or fully masked (sigma = NaN) image: the reference's weights are all NaN, its
+            # densities all 0, and the parabola's vertex 0 / 0 -- it reports a NaN mode and goes on (medsky = nan)
+            centre = np.float64(np.nan)
+            break
         grid = centre + np.linspace(-1, 1, nodes) * sigma
         inner = np.ascontiguousarray(grid[1:nodes - 1], dtype=np.float64)
         dens = np.zeros(nodes)
