@@ -573,6 +573,44 @@ int rip_synth_frames_ahead(rip_ctx *ctx, int rows, int width, int nframes, uint6
    offset), 0, 65535) for k = 1..ngrp-1, in place (the caller drops plane 0).  Used for the cube and for amp33.  Exact. */
 int rip_synth_extract_ref(rip_ctx *ctx, uint16_t *data, int ngrp, size_t n, int offset, uint16_t *reference_read);
 
+/* Cosmic-ray hits (the model of romanisim's cr module, restated in DESIGN.md 7: romanisim is absent from the reference tree, so
+   parity is unpinned and every constant is a parameter).  Defaults in brackets. */
+typedef struct rip_cr_params {
+    double flux, area;               /* tracks per cm^2 and second [8], detector area in cm^2 [16.8]                         */
+    double conversion_factor;        /* eV per electron as romanisim names it [0.5]: electrons per pixel length =            */
+                                     /* dEdx * pixel_size / conversion_factor                                                */
+    double pixel_size, pixel_depth;  /* micrometres [10, 5]                                                                  */
+    double min_dedx, max_dedx;       /* range of the energy loss in eV per micrometre [10, 10000]                            */
+    double moyal_location, moyal_scale;   /* its Moyal density exp(-(s + exp(-s)) / 2), s = (x - location) / scale [120, 50] */
+    double min_len, max_len;         /* range of the track length in micrometres [10, 2000]                                  */
+    double len_slope;                /* its density x ** slope [-4.33]                                                       */
+    int32_t grid_size, _pad;         /* points of the two tabulated CDFs [10000]                                             */
+} rip_cr_params;
+
+/* The tracks of an exposure.  Read r of nreads has Poisson(flux * area * read_time) of them; each starts at (u1 nya, u2 nxa) in
+   (row, column) pixel coordinates, points along phi = 2 pi u3 and has length F_len^-1(u4) and energy loss F_dEdx^-1(u5), F^-1
+   the linear interpolation scipy.interpolate.interp1d(c, x) evaluates on x = linspace(lo, hi, grid_size), c = cumsum(pdf(x)) -
+   pdf(x[0]), c /= max(c): the tables are made on the host in f64 and kept in the context until a parameter that shapes them
+   changes (new tables first wait for the work queued on the stream).
+   tracks (capacity,6) f64 rows = read index, i0, j0, phi, length, dEdx; offsets (nreads+1) i32 = first row of each read,
+   offsets[nreads] = number of rows, clamped to capacity (rows past it are lost: size it for the mean plus ten sigma).
+   counts (nreads) i32 or NULL: device Poisson deviates; uniforms (capacity,5) f64 in [0,1) or NULL: device generator (Philox
+   under tags of its own).  Exact given counts and uniforms up to the host's exp / pow in the tables. */
+int rip_synth_cr_tracks(rip_ctx *ctx, const rip_cr_params *params, int nreads, double read_time, int nya, int nxa, uint64_t seed,
+                        const int32_t *counts, const double *uniforms, int capacity, double *tracks, int32_t *offsets);
+
+/* The deposits of the rows offsets[0] .. offsets[nreads]-1 of tracks, in place on reads_e (nreads,nya,nxa) i32 (the output of
+   the apportioning).  A track ends at (clip(i0 + l cos phi, -0.5, nya + 0.5), clip(j0 + l sin phi, -0.5, nxa + 0.5)), l = length /
+   pixel_size; pixel (i,j) is the square [i-0.5,i+0.5) x [j-0.5,j+0.5).  Every pixel of the image that holds a part of the track
+   of length l2 (parts shorter than 1e-10 pixels do not count; a track without such a part deposits once, with its whole length,
+   in the pixel of its middle) receives k ~ Poisson(lambda) electrons, lambda = dEdx * pixel_size / conversion_factor *
+   sqrt((pixel_depth / pixel_size)^2 + l2^2), in the read of its row and every later one (poisson == 0: k = rint(lambda)).
+   first_read (nya,nxa) i32 is WRITTEN by the call: the first read in which a track crossed the pixel, nreads where none did.
+   lam (nya,nxa) f64 or NULL: the sum of lambda per pixel.  Integer adds commute: the same tracks and seed give the same
+   reads_e on every run.  The walk of a track stops after nya + nxa + 2 boundary crossings. */
+int rip_synth_cr_deposit(rip_ctx *ctx, const rip_cr_params *params, int nreads, int nya, int nxa, const double *tracks,
+                         const int32_t *offsets, int poisson, uint64_t seed, int32_t *reads_e, int32_t *first_read, double *lam);
+
 /* ---- diagnostics ------------------------------------------------------------------------- */
 /* floating-point options of a context.  "guard_band": relative half-width of the band around the jump
    threshold inside which the significance is re-evaluated in the reference's exact operation order

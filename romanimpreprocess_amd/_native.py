@@ -85,6 +85,15 @@ class SynthCal(C.Structure):   # rip_synth_cal: DEVICE pointers
     ]
 
 
+class CrParams(C.Structure):   # rip_cr_params: the cosmic-ray model's constants (defaults: romanisim's)
+    _fields_ = [
+        ("flux", C.c_double), ("area", C.c_double), ("conversion_factor", C.c_double), ("pixel_size", C.c_double),
+        ("pixel_depth", C.c_double), ("min_dedx", C.c_double), ("max_dedx", C.c_double), ("moyal_location", C.c_double),
+        ("moyal_scale", C.c_double), ("min_len", C.c_double), ("max_len", C.c_double), ("len_slope", C.c_double),
+        ("grid_size", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+
 class WcsDesc(C.Structure):   # rip_wcs_desc: a FITS zenithal (+SIP) WCS, crpix 0-based, angles in degrees
     _fields_ = [
         ("projection", C.c_int32), ("sip_order", C.c_int32), ("crpix", C.c_double * 2), ("cd", (C.c_double * 2) * 2),
@@ -144,6 +153,8 @@ SYMBOLS = {
     "rip_synth_resultants": (_I, [_VP, C.POINTER(SynthCal), _I, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP]),
     "rip_synth_fill": (_I, [_VP, C.POINTER(SynthCal), _I, _VP, _I, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
     "rip_synth_noise_1f": (_I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint32, _VP]),
+    "rip_synth_cr_tracks": (_I, [_VP, C.POINTER(CrParams), _I, C.c_double, _I, _I, C.c_uint64, _VP, _VP, _I, _VP, _VP]),
+    "rip_synth_cr_deposit": (_I, [_VP, C.POINTER(CrParams), _I, _I, _I, _VP, _VP, _I, C.c_uint64, _VP, _VP, _VP]),
     "rip_synth_extract_ref": (_I, [_VP, _VP, _I, C.c_size_t, _I, _VP]),
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),

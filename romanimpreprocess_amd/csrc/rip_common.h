@@ -136,6 +136,7 @@ enum RipWs {
     RIP_WS_R1_ZERO = 14,    // single-launch pre-pass: control words + histograms + status word (zero between calls)
     RIP_WS_R1_SCRATCH = 15,   // single-launch pre-pass: row / channel scratch
     RIP_WS_DEFER = 16,      // Level-1 synthesis: the apportioning's lists of deferred pixels
+    RIP_WS_CR_TAB = 17,     // Level-1 synthesis: the cosmic-ray model's two inverse-CDF tables
     RIP_WS_COUNT
 };
 
@@ -215,6 +216,8 @@ struct rip_ctx {   // host-only: no kernel reads it
     uint64_t frames_seed = 0;
     int frames_geom[3] = {0, 0, 0};   // rows, channel width, frames
     std::vector<double> share_tab;   // the read-share table whose device copy sits in workspace slot 10
+    rip_cr_params cr_tab_key = {};   // cr.hip: the parameters that shaped the inverse-CDF tables in workspace slot 17 (the others zeroed)
+    bool cr_tab_valid = false;
 };
 
 // ---------------------------------------------------------------- host helpers

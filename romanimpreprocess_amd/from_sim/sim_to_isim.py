@@ -12,15 +12,23 @@ Random numbers: the reference threads a ``galsim.BaseDeviate`` through these fun
 ``numpy.random.Generator`` (one integer is drawn from it per call) and every deviate comes from a counter-based generator
 on the device keyed by (seed, plane, pixel).  The distributions are reproduced, not galsim's or numpy's streams; with
 deviates handed in (``L1Synth`` methods) the arithmetic is bit-identical to the reference's functions (tests/golden/l1sim.npz).
-Cosmic rays and persistence (``romanisim.cr`` / ``romanisim.persistence``, called by romanisim's apportioning loop) are not
-injected: passing ``persistence`` raises.
+
+Cosmic rays (``romanisim.cr``, called by romanisim's apportioning loop): ``crparam`` on ``L1Synth.make`` and ``make_l1_fullcal``,
+romanisim's own switch -- None (the default here) means no hits, a dict means hits with these parameters over romanisim's
+defaults, ``{}`` all defaults.  The reference's ``make_l1_fullcal`` passes ``crparam={}``: its exposures carry about 14 000
+tracks each, and a caller who wants the reference's behaviour passes ``{}`` too.  The default stays None because the existing
+tests pin the hit-free exposure of a seed; the hits draw from Philox tags of their own, so an exposure with hits is the
+hit-free exposure of the same seed plus the hits.  The model is restated from the published algorithm (``from_sim/cr.py``,
+DESIGN.md section 7): romanisim is absent from the reference tree, parity with it is unpinned, every constant is a keyword.
+Persistence (``romanisim.persistence``) is not modelled: passing ``persistence`` raises.
 """
 
 import ctypes as C
 
 import numpy as np
 
-from .. import _native, calio, pars
+from .. import _native, calio, dqflags, pars
+from . import cr
 
 READ_TIME = 3.04   # seconds per read: romanisim.parameters.read_time, which the reference's read_pattern_to_tij uses
 
@@ -186,14 +194,65 @@ class L1Synth:
                                                    self._p(amp33)))
         self._hold3 = (n, f, w)
 
-    def make(self, counts, seed, poisson=False, banding=True):
-        """One exposure: (cube (ngrp, ny, nx), amp33 (ngrp, ny, cw)) int16 device tensors holding the u16 bits."""
+    def cosmic_rays(self, reads_e, seed, crparam=None, tracks=None, poisson=True, want_lambda=False):
+        """Cosmic-ray hits added to ``reads_e`` (nreads, nya, nxa) int32 in place (``from_sim/cr.py``; asynchronous like the other
+        entry points).  ``crparam``: dict of romanisim's keywords over its defaults (None and ``{}``: all defaults).
+        ``tracks``: (n, 6) rows of read index, i0, j0, phi, length [um], dEdx [eV/um] handed in (they are sorted by read) instead
+        of the device's draw; ``poisson=False`` deposits the rounded means.  Returns a dict of device tensors: "first_read"
+        (nya, nxa) int32 -- the first read in which a track crossed the pixel, nreads where none did --, "tracks" (capacity, 6)
+        f64, "offsets" (nreads+1,) int32 (first row of every read; the last entry is the number of rows), and with
+        ``want_lambda`` "lam" (nya, nxa) f64, the summed means of the deposits."""
+        torch = self.torch
+        par = cr.params_from(crparam)
+        if tuple(reads_e.shape) != (self.nreads, self.nya, self.nxa) or reads_e.dtype != torch.int32 or not reads_e.is_contiguous():
+            raise ValueError(f"reads_e must be a contiguous int32 tensor of shape {(self.nreads, self.nya, self.nxa)}")
+        out = {"first_read": torch.empty((self.nya, self.nxa), dtype=torch.int32, device=self.dev)}
+        if want_lambda:
+            out["lam"] = torch.empty((self.nya, self.nxa), dtype=torch.float64, device=self.dev)
+        if tracks is None:
+            cap = cr.capacity_for(par, self.nreads, self.read_time)
+            out["tracks"] = torch.empty((cap, 6), dtype=torch.float64, device=self.dev)
+            out["offsets"] = torch.empty((self.nreads + 1,), dtype=torch.int32, device=self.dev)
+            self.ctx.check(self.ctx.lib.rip_synth_cr_tracks(self.ctx.h, C.byref(par), self.nreads, self.read_time, self.nya, self.nxa,
+                                                            int(seed), None, None, cap, out["tracks"].data_ptr(),
+                                                            out["offsets"].data_ptr()))
+        else:
+            t = np.ascontiguousarray(tracks.cpu().numpy() if torch.is_tensor(tracks) else tracks, dtype=np.float64).reshape(-1, 6)
+            t = t[np.argsort(t[:, 0], kind="stable")]
+            if len(t) and not (t[0, 0] >= 0 and t[-1, 0] < self.nreads):
+                raise ValueError(f"track read indices must lie in 0..{self.nreads - 1}")
+            offsets = np.searchsorted(t[:, 0], np.arange(self.nreads + 1), side="left").astype(np.int32)
+            out["tracks"] = torch.from_numpy(np.concatenate([t, np.zeros((1, 6))])).to(self.dev)   # (never empty)
+            out["offsets"] = torch.from_numpy(offsets).to(self.dev)
+            torch.cuda.current_stream(self.dev).synchronize()   # torch's copies are not on the context's stream
+        self.ctx.check(self.ctx.lib.rip_synth_cr_deposit(self.ctx.h, C.byref(par), self.nreads, self.nya, self.nxa,
+                                                         out["tracks"].data_ptr(), out["offsets"].data_ptr(), int(bool(poisson)),
+                                                         int(seed), reads_e.data_ptr(), out["first_read"].data_ptr(),
+                                                         self._p(out.get("lam"))))
+        self._hold_cr = (out, reads_e)
+        return out
+
+    def resultants_with_hits(self, first_read):
+        """(ngrp, nya, nxa) bool numpy array: the resultants that hold the read ``first_read`` (numpy, (nya, nxa)) or a later one
+        -- where JUMP_DET belongs in the Level-1 dq."""
+        ends = np.cumsum(self.group_count)                       # reads of resultant j: ends[j-1] <= r < ends[j]
+        grp = np.searchsorted(ends, first_read, side="right")    # == ngrp where the pixel was never hit
+        return np.arange(self.ngrp)[:, None, None] >= grp[None]
+
+    def make(self, counts, seed, poisson=False, banding=True, crparam=None):
+        """One exposure: (cube (ngrp, ny, nx), amp33 (ngrp, ny, cw)) int16 device tensors holding the u16 bits.
+        ``crparam``: None = no cosmic rays (the default: existing seeds keep their exposures), a dict = hits with these
+        parameters (``{}``: romanisim's defaults, what the reference's ``make_l1_fullcal`` asks for); ``self.last_first_read``
+        then holds the "first_read" tensor of ``cosmic_rays`` (None without hits)."""
         torch = self.torch
         reads_e = self.apportion(counts, seed, poisson)
         if banding:   # the 1/f frames of this exposure's fill: on the second stream beside the resultants (f64 arithmetic), behind
             # the apportioning (bound by HBM like the transforms)
             self.ctx.check(self.ctx.lib.rip_synth_frames_ahead(self.ctx.h, self.ny, self.cw, self.ngrp * (self.nx // self.cw + 2),
                                                                int(seed)))
+        self.last_first_read = None
+        if crparam is not None:
+            self.last_first_read = self.cosmic_rays(reads_e, seed, crparam)["first_read"]
         cube = self.resultants(reads_e, seed)["cube"]
         amp33 = torch.zeros((self.ngrp, self.ny, self.cw), dtype=torch.int16, device=self.dev)
         torch.cuda.current_stream(self.dev).synchronize()   # torch's zero fill runs on torch's stream, the kernels below on the context's
@@ -210,10 +269,13 @@ class L1Synth:
 
 
 # ---- the reference's function surface (numpy in and out) ---------------------------------------------------------------------
-def make_l1_fullcal(counts, read_pattern, caldir, rng=None, persistence=None, tstart=None, read_time=None, ctx=None):
+def make_l1_fullcal(counts, read_pattern, caldir, rng=None, persistence=None, tstart=None, read_time=None, ctx=None, crparam=None):
     """Resultants (ngrp, na, na) f32 in DN (rounded) and the (ngrp, na, na) u32 dq cube of the linearity file, as the reference's
     ``make_l1_fullcal`` returns them.  ``counts``: (na, na) array of integer electron counts, or an object with ``.array``.
-    ``read_time``: seconds per read (default ``READ_TIME``)."""
+    ``read_time``: seconds per read (default ``READ_TIME``).
+    ``crparam``: None (default) = no cosmic rays; a dict = hits (``from_sim/cr.py``), and JUMP_DET in the dq of the resultant
+    that holds the hit read and of every later one.  The reference's own call corresponds to ``crparam={}`` (the module
+    docstring says why the default here is None)."""
     if persistence is not None:
         raise NotImplementedError("persistence is a romanisim model outside this package")
     arr = np.asarray(getattr(counts, "array", counts), dtype=np.float32)
@@ -222,11 +284,15 @@ def make_l1_fullcal(counts, read_pattern, caldir, rng=None, persistence=None, ts
     cal = caldir_arrays(caldir)
     s = L1Synth(cal, read_pattern, READ_TIME if read_time is None else read_time, ctx=ctx)
     seed = _seed_of(rng)
-    out = s.resultants(s.apportion(arr, seed), seed, want_resultants=True, want_cube=False)
+    reads_e = s.apportion(arr, seed)
+    hits = None if crparam is None else s.cosmic_rays(reads_e, seed, crparam)
+    out = s.resultants(reads_e, seed, want_resultants=True, want_cube=False)
     s.ctx.synchronize()
     nb = s.nb
     dq = np.zeros((s.ngrp, s.nya, s.nxa), dtype=np.uint32)
     dq |= s.lin_dq[None, nb:s.ny - nb, nb:s.nx - nb]
+    if hits is not None:
+        dq[s.resultants_with_hits(hits["first_read"].cpu().numpy())] |= np.uint32(dqflags.pixel.JUMP_DET)
     return out["resultants"].cpu().numpy(), dq
 
 

@@ -78,7 +78,7 @@ def ideal_slope(cal, rate, nb=pars.nborder):
 
 
 def run(calibrator, slot, cal, nseeds=256, seed0=100, read_pattern=None, device=None, reference_alias=True, generator="host",
-        timings=None, rate=None, l1synth=None, stack_capacity=None):
+        timings=None, rate=None, l1synth=None, stack_capacity=None, crparam=None):
     """Generate and calibrate ``nseeds`` realisations (this rank's share of them), exchange, reduce.  Returns the
     (8, ny, nx) f32 planes as a numpy array on rank 0, None on the other ranks.
 
@@ -93,11 +93,16 @@ def run(calibrator, slot, cal, nseeds=256, seed0=100, read_pattern=None, device=
     run with the capacity of the job that follows leaves the 56 GB with torch's caching allocator, and the job does not wait
     0.3-1.9 s for the driver to map them.
     ``l1synth``: generator "hip" -- a ``sim_to_isim.L1Synth`` of this calibration set and read pattern whose arrays are on the
-    device already (the synthesis side's counterpart of ``calibrator.load_caldir``: 1.5 GB of uploads for a full frame)."""
+    device already (the synthesis side's counterpart of ``calibrator.load_caldir``: 1.5 GB of uploads for a full frame).
+    ``crparam``: generator "hip" only -- cosmic-ray hits in every exposure (``L1Synth.make``: None = none, ``{}`` = romanisim's
+    defaults, what the reference's synthesis does); ``timings["cr_hit_pixels"]`` is the number of hit pixels summed over this
+    rank's realisations."""
     import time
 
     import torch
 
+    if crparam is not None and generator != "hip":
+        raise ValueError(f"crparam needs generator 'hip' (generator {generator!r} has its own hits or none)")
     t_start = time.perf_counter()
     device = device or torch.device("cuda", calibrator.ctx.device)
     rp = synth.READ_PATTERN_8 if read_pattern is None else read_pattern
@@ -153,6 +158,7 @@ def run(calibrator, slot, cal, nseeds=256, seed0=100, read_pattern=None, device=
         t_pdq_hip = torch.from_numpy(np.array(cal["mask"]["dq"], dtype=np.uint32).view(np.int32)).to(device)
     elif generator not in ("host", "device"):
         raise ValueError(f"generator {generator!r}: host, device or hip")
+    cr_hit_pixels = 0
     t_gen = t_cal = 0.0
     torch.cuda.synchronize(device)
     t_setup = time.perf_counter() - t_start   # rate image, generator state (the stacks are still being allocated by the helper thread)
@@ -163,7 +169,11 @@ def run(calibrator, slot, cal, nseeds=256, seed0=100, read_pattern=None, device=
             # two contexts (``l1synth`` made on its own) exposure k is calibrated (HBM-bound kernels, 1.6 ms) beside the inverse
             # linearity of exposure k+1 (f64 arithmetic); with one context everything is in stream order as before.  The tensors
             # of exposure k stay referenced until the calibrator has been waited for, an exposure later.
-            cube, a33 = hip_synth.make(counts_mean, sd, poisson=True)   # (returns with the exposure complete)
+            if crparam is None:
+                cube, a33 = hip_synth.make(counts_mean, sd, poisson=True)   # (returns with the exposure complete)
+            else:
+                cube, a33 = hip_synth.make(counts_mean, sd, poisson=True, crparam=crparam)
+                cr_hit_pixels += int((hip_synth.last_first_read < hip_synth.nreads).sum())
             t1 = time.perf_counter()
             calibrator.synchronize()   # calibration + stacking of the exposure before: done beside this make(), or long ago
             held = (cube, a33)         # noqa: F841 -- replaces (frees) the exposure before
@@ -208,5 +218,6 @@ def run(calibrator, slot, cal, nseeds=256, seed0=100, read_pattern=None, device=
     if timings is not None:
         timings.update({"setup_s": t_setup, "generate_s": t_gen, "calibrate_and_stack_s": t_cal - join_wait[0],
                         "stack_allocation_wait_s": join_wait[0],
-                        "exchange_and_reduce_s": time.perf_counter() - t_red, "realisations_on_this_rank": len(seeds)})
+                        "exchange_and_reduce_s": time.perf_counter() - t_red, "realisations_on_this_rank": len(seeds),
+                        "cr_hit_pixels": cr_hit_pixels})
     return None if full is None else full.cpu().numpy()
