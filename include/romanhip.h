@@ -611,6 +611,39 @@ int rip_synth_cr_tracks(rip_ctx *ctx, const rip_cr_params *params, int nreads, d
 int rip_synth_cr_deposit(rip_ctx *ctx, const rip_cr_params *params, int nreads, int nya, int nxa, const double *tracks,
                          const int32_t *offsets, int poisson, uint64_t seed, int32_t *reads_e, int32_t *first_read, double *lam);
 
+/* ---- calibration-file derivation ----------------------------------------------------------- */
+/* What runs/2026_July/postprocess_calfiles.py and makemask.py of the reference compute from a linearitylegendre / dark / gain
+   set.  The array arguments of these four entries are host arrays or device pointers; READS, LPX, LPY and coef are host arrays.
+   Every input plane is a full (ny,nx) frame.  Exact: the reference's numpy operations in its order and dtypes (numpy >= 2). */
+
+/* biascorr (postprocess_calfiles.py:103-140).  reads[2 ngrp]: group j holds the reads reads[2j] .. reads[2j+1]-1 (groups need be
+   neither contiguous nor sorted).  xref = (reads[2 bframe] + reads[2 bframe + 1] - 1) / 2; dark = f32(dark_slope * f32(tframe));
+   per active pixel and group, pred_j = f32(sum over the group's reads x, in read order, of invlinearity(f32(dark * f32(x - xref))))
+   / f32(number of reads), the inverse linearity in f32 as rip_stage_invlinearity evaluates it on coefs (nplanes,ny,nx), smin,
+   smax at the pixel; biascorr_j = dark_data_j - pred_j.  dark_data (ngrp_dark,ny,nx); biascorr and pred (NULL: not wanted) are
+   (ngrp, ny-2nb, nx-2nb) f32; t0 (NULL: not wanted) receives tframe * xref.
+   RIP_EINVAL, before anything is launched: ngrp outside 1..RIP_MAX_GROUPS, a group with reads[2j+1] <= reads[2j] (or more than
+   65536 reads), bframe outside [0, ngrp), ngrp != ngrp_dark, a border that leaves no active pixel, nplanes outside 2..17. */
+int rip_cal_biascorr(rip_ctx *ctx, const float *dark_slope, const float *dark_data, int ngrp_dark, int ny, int nx, int nb, int nplanes,
+                     const float *coefs, const float *smin, const float *smax, const int32_t *reads, int ngrp, double tframe, int bframe,
+                     float *biascorr, float *pred, double *t0);
+
+/* pflat (postprocess_calfiles.py:22-40) from the raw p-flat plane: p = f32(p / f32(model)), the medfit model evaluated as
+   rip_stage_legendre2d does from LPX (order+1,nx), LPY (order+1,ny), coef (sky.medfit rounds it to the plane's dtype, :191);
+   p = f32(p * scale), scale = f32(g_ideal / median(gain)) from the caller; dq = 1 where p < 0.01 or p > 1.99 (f32 compares);
+   data = clip(p, 0.01, 1.99) (NaN stays).  data f32, dq u32, (ny,nx). */
+int rip_cal_pflat(rip_ctx *ctx, const float *pflat, int ny, int nx, int order, const double *LPX, const double *LPY, const double *coef,
+                  float scale, float *data, uint32_t *dq);
+
+/* saturation (postprocess_calfiles.py:69-97): data = f32(clip(Smax, 1, 65535)) - 1, dq = 0 where Smax > Sref, else 1. */
+int rip_cal_saturation(rip_ctx *ctx, const float *smax, const float *sref, int ny, int nx, float *data, uint32_t *dq);
+
+/* mask (makemask.py:12-36): REFERENCE_PIXEL on the nb border rows and columns | lin_dq | LOW_QE where pflat0 / pflat_median
+   < 0.5 (f32; pflat_median = np.median of the plane, from the caller) | HOT where dark_slope > 12.5, else WARM where > 0.25
+   | gain_dq. */
+int rip_cal_mask(rip_ctx *ctx, int ny, int nx, int nb, const uint32_t *lin_dq, const float *pflat0, float pflat_median,
+                 const float *dark_slope, const uint32_t *gain_dq, uint32_t *dq);
+
 /* ---- diagnostics ------------------------------------------------------------------------- */
 /* floating-point options of a context.  "guard_band": relative half-width of the band around the jump
    threshold inside which the significance is re-evaluated in the reference's exact operation order

@@ -156,6 +156,10 @@ SYMBOLS = {
     "rip_synth_cr_tracks": (_I, [_VP, C.POINTER(CrParams), _I, C.c_double, _I, _I, C.c_uint64, _VP, _VP, _I, _VP, _VP]),
     "rip_synth_cr_deposit": (_I, [_VP, C.POINTER(CrParams), _I, _I, _I, _VP, _VP, _I, C.c_uint64, _VP, _VP, _VP]),
     "rip_synth_extract_ref": (_I, [_VP, _VP, _I, C.c_size_t, _I, _VP]),
+    "rip_cal_biascorr": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, C.c_double, _I, _VP, _VP, _VP]),
+    "rip_cal_pflat": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, C.c_float, _VP, _VP]),
+    "rip_cal_saturation": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "rip_cal_mask": (_I, [_VP, _I, _I, _I, _VP, _VP, C.c_float, _VP, _VP, _VP]),
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_last_chain_form": (_I, [_VP]),

@@ -5,8 +5,9 @@
 // Pointer kinds of the ARRAY arguments of the stage-level entry points (include/romanhip.h says the same at each):
 //   host arrays OR device pointers   rip_stage_noise_inject (in-place calls, out == cube, included), rip_stage_poisson_resample,
 //                                    rip_stage_pearson, and the post-path entries of post.hip (rip_stage_build_mask, _endslice,
-//                                    _bin_mean, _select_ranks, _gauss_hist, _legendre2d; rip_stage_pixel_area by out_location).
-//                                    The noise-layer driver (L1_to_L2/gen_noise_image.py) hands them planes that live in HBM.
+//                                    _bin_mean, _select_ranks, _gauss_hist, _legendre2d; rip_stage_pixel_area by out_location),
+//                                    and the calibration-file entries of calfiles.hip (rip_cal_biascorr, _pflat, _saturation,
+//                                    _mask).  The noise-layer driver (L1_to_L2/gen_noise_image.py) hands them planes that live in HBM.
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)

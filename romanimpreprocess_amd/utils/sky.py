@@ -149,6 +149,34 @@ def medfit(arr, N=8, order=2, subtract=False, ctx=None, want_model=True):
         raise ValueError("want_model=False only makes sense with subtract=True")
     a = arr if subtract else _f32(arr)
     ny, nx = a.shape
+    x, LPX, LPY = medfit_tables(a, N, order, ctx)
+    model = np.empty((ny, nx), np.float32) if want_model else None
+    coef = np.ascontiguousarray(x, dtype=np.float64)
+    ctx.check(ctx.lib.rip_stage_legendre2d(ctx.h, a.ctypes.data if subtract else None, ny, nx, int(order), LPX.ctypes.data,
+                                           LPY.ctypes.data, coef.ctypes.data, int(bool(subtract)),
+                                           None if model is None else model.ctypes.data))
+    return x, model
+
+
+def median(arr, ctx=None):
+    """``np.median`` of a float32 plane (host array or ``DevArray``) as a float32: NaN as soon as the plane holds a NaN, else
+    the middle order statistic or the float32 mean of the two middle ones, found exactly on the GPU."""
+    ctx = ctx or _native.default_context()
+    a = _f32(arr)
+    if a.ndim != 2:
+        a = a.reshape(1, -1)
+    ny, nx = a.shape
+    n = int(_select(ctx, a, 0, 0, ny, nx, 1, 1, None)[0][0])
+    if n < a.size:
+        return np.float32(np.nan)
+    vals = _select(ctx, a, 0, 0, ny, nx, 1, 1, np.array([(n - 1) // 2, n // 2], dtype=np.int64))[1][0]
+    return np.mean(vals, dtype=np.float32)
+
+
+def medfit_tables(a, N, order, ctx):
+    """The fit of ``medfit`` without its evaluation: (coef, LPX, LPY), the Legendre tables on the pixel grid as C-contiguous
+    float64 arrays for the kernels that evaluate the model (``rip_stage_legendre2d``, ``rip_cal_pflat``)."""
+    ny, nx = a.shape
     kx, ky = nx // N, ny // N
     px, py = (nx % N) // 2, (ny % N) // 2
     # block centres mapped to [-1, 1) as the reference maps them, medians on the GPU
@@ -176,13 +204,7 @@ def medfit(arr, N=8, order=2, subtract=False, ctx=None, want_model=True):
     # Legendre tables on the pixel grid for the model evaluation on the GPU
     LPX = np.stack([np.reshape(legendre_p(i, np.linspace(-1, 1 - 2 / nx, nx)), nx) for i in range(order + 1)]).astype(np.float64)
     LPY = np.stack([np.reshape(legendre_p(j, np.linspace(-1, 1 - 2 / ny, ny)), ny) for j in range(order + 1)]).astype(np.float64)
-    LPX, LPY = np.ascontiguousarray(LPX), np.ascontiguousarray(LPY)
-    model = np.empty((ny, nx), np.float32) if want_model else None
-    coef = np.ascontiguousarray(x, dtype=np.float64)
-    ctx.check(ctx.lib.rip_stage_legendre2d(ctx.h, a.ctypes.data if subtract else None, ny, nx, int(order), LPX.ctypes.data,
-                                           LPY.ctypes.data, coef.ctypes.data, int(bool(subtract)),
-                                           None if model is None else model.ctypes.data))
-    return x, model
+    return x, np.ascontiguousarray(LPX), np.ascontiguousarray(LPY)
 
 
 def endslice(rdq, nborder, ctx=None):

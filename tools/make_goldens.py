@@ -983,7 +983,133 @@ def case_l1sim():
          im_after=im, amp33_after=amp33, **flat)
 
 
+def case_calfiles():
+    """Calibration-file derivation: the reference's runs/2026_July/postprocess_calfiles.py and makemask.py are EXECUTED as they
+    stand (read from the reference tree at run time) on the small sets of tests/calfiles_cases.py, with sys.argv, the working
+    directory (settings_<name>.yaml, linearity_pars_<sca>.json) and the asdf stand-in (open / AsdfFile(tree).write_to keep the
+    trees in memory) arranged around them.  Three things are changed with `ast` before execution, none of them arithmetic:
+      * postprocess_calfiles.py: the statements from `B = np.zeros((2 * ngrp, 4088, 4088), ...)` to the end (the FITS dump of
+        a hard-coded full-size array, which fails on a small frame after all three trees are written) are dropped;
+      * makemask.py: the literal frame (4096, 4096) becomes the case's;
+      * `from datetime import UTC` needs Python 3.11: on an older interpreter datetime.UTC is set to timezone.utc meanwhile.
+    Before the run, pixels of the p-flat plane outside every medfit block (row 0) are set so that, divided by the reference's own
+    model and scaled, they land exactly on 0.01 and 1.99 and one float32 either side; the fixture keeps that plane and the gain."""
+    import ast
+    import contextlib
+    import datetime as _dt
+    import io
+    import shutil
+    import yaml
+
+    import calfiles_cases as cc
+    from romanimpreprocess import pars as ref_pars
+
+    class _AF:
+        def __init__(self, tr):
+            self.tr = tr
+
+        def write_to(self, path_):
+            _STORE[path_] = self.tr
+
+    sys.modules["asdf"].AsdfFile = _AF
+    runs = os.path.join(os.path.dirname(REF_SRC), "runs", "2026_July") + os.sep
+    post = ast.parse(open(runs + "postprocess_calfiles.py").read())
+    cut = next(i for i, n in enumerate(post.body) if isinstance(n, ast.Assign) and ast.unparse(n.targets[0]) == "B")
+    assert cut == len(post.body) - 4
+    post.body = post.body[:cut]
+    mask_src = open(runs + "makemask.py").read()
+    import tempfile
+
+    tmp = os.path.join(tempfile.mkdtemp(prefix="goldens_calfiles_"), "work")
+    tmp_root = os.path.dirname(tmp)
+    had_utc = hasattr(_dt, "UTC")
+    if not had_utc:
+        _dt.UTC = _dt.timezone.utc
+    cwd, argv = os.getcwd(), sys.argv
+    F = np.float32
+    try:
+        for sca, (name, c) in enumerate(cc.CASES.items(), start=1):
+            a = cc.inputs(name)
+            pflat0, gain = a["pflat"][0], a["gain"]
+            with np.errstate(all="ignore"):
+                s = ref_pars.g_ideal / np.median(gain)
+                _, model = ref_sky.medfit(pflat0.copy(), N=6, order=2)
+            assert model.dtype == np.float32 and np.asarray(s).dtype == np.float32
+            if np.isfinite(s):
+                def result(row, col, w):   # what the script makes of the value w at that pixel
+                    return F(F(w / model[row, col]) * s)
+
+                def landing(row, col, want):   # the float32 values that land exactly on `want` there (the two roundings skip some)
+                    w = F(want / s * model[row, col])
+                    for _ in range(64):
+                        w = np.nextafter(w, F(-1))
+                    hits = []
+                    for _ in range(129):
+                        if result(row, col, w) == want:
+                            hits.append(w)
+                        w = np.nextafter(w, F(9))
+                    return hits
+
+                for row, want, outward in ((0, F(0.01), F(-1)), (cc.NY - 1, F(1.99), F(9))):
+                    cols = [c_ for c_ in range(10, 130) if landing(row, c_, want)][:3]
+                    assert len(cols) == 3, (name, want)
+                    on, out, inside = (landing(row, c_, want) for c_ in cols)
+                    pflat0[row, cols[0]] = on[0]                                                     # exactly on the limit: unflagged
+                    w = out[0] if outward < 0 else out[-1]
+                    while result(row, cols[1], w) == want:
+                        w = np.nextafter(w, outward)
+                    pflat0[row, cols[1]] = w                                                         # one step outside: flagged, clipped
+                    w = inside[-1] if outward < 0 else inside[0]
+                    while result(row, cols[2], w) == want:
+                        w = np.nextafter(w, -outward)
+                    pflat0[row, cols[2]] = w                                                         # one step inside
+            stem = f"/mem/{name}"
+
+            def files():   # fresh copies: the script divides the p-flat plane in place
+                register(stem + "_linearitylegendre_X.asdf", {"data": a["lin_data"].copy(), "Smin": a["Smin"].copy(), "Smax": a["Smax"].copy(),
+                                                              "Sref": a["Sref"].copy(), "dq": a["lin_dq"].copy(), "pflat": a["pflat"].copy()})
+                register(stem + "_gain_X.asdf", {"data": gain.copy(), "dq": a["gain_dq"].copy()})
+                register(stem + "_dark_X.asdf", {"data": a["dark_data"].copy(), "dark_slope": a["dark_slope"].copy()})
+
+            shutil.rmtree(tmp, ignore_errors=True)
+            os.makedirs(tmp)
+            with open(os.path.join(tmp, f"linearity_pars_{sca:02d}.json"), "w") as f:
+                json.dump(c["lpars"], f)
+            with open(os.path.join(tmp, "settings_pattern.yaml"), "w") as f:
+                yaml.safe_dump({"READS": list(c["reads"])}, f)
+            os.chdir(tmp)
+            files()
+            sys.argv = ["postprocess_calfiles.py", stem + "_linearitylegendre_X.asdf", str(sca), "pattern"]
+            ns = {"__name__": "__main__"}
+            with np.errstate(all="ignore"), contextlib.redirect_stdout(io.StringIO()):
+                import warnings
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    exec(compile(post, runs + "postprocess_calfiles.py", "exec"), ns)
+                    files()
+                    sys.argv = ["makemask.py", stem + "_mask_X.asdf", str(sca)]
+                    src = mask_src.replace("(4096, 4096)", f"({cc.NY}, {cc.NX})")
+                    assert src != mask_src
+                    exec(compile(src, runs + "makemask.py", "exec"), {"__name__": "__main__"})
+            os.chdir(cwd)
+            pf, sat = _STORE[stem + "_pflat_X.asdf"]["roman"], _STORE[stem + "_saturation_X.asdf"]["roman"]
+            bc, mk = _STORE[stem + "_biascorr_X.asdf"]["roman"], _STORE[stem + "_mask_X.asdf"]["roman"]
+            tframe, bframe = cc.frame_pars(c["lpars"])
+            save(name, reads=np.array(c["reads"], np.int32), tframe=np.float64(tframe), bframe=np.int32(bframe), sca=np.int32(sca),
+                 g_ideal=np.float64(ref_pars.g_ideal), pflat0=a["pflat"][0], gain=gain,
+                 biascorr=bc["data"], pred=np.array(ns["Sdark_predicted"]), t0=np.float64(bc["t0"]), xref=np.float64(ns["xref"]),
+                 pflat_data=pf["data"], pflat_dq=pf["dq"], pflat_coefs=np.asarray(ns["coefs"], np.float64),
+                 sat_data=sat["data"], sat_dq=sat["dq"], mask_dq=mk["dq"])
+    finally:
+        os.chdir(cwd)
+        sys.argv = argv
+        if not had_utc:
+            del _dt.UTC
+        shutil.rmtree(tmp_root, ignore_errors=True)
+
+
 CASES = {
+    "calfiles": case_calfiles,
     "lin_known_answer": case_lin_known_answer, "multilin": case_multilin, "ipc": case_ipc,
     "weights": case_weights, "rampfit": case_rampfit, "flat": case_flat, "refpix": case_refpix,
     "chain": case_chain, "post": case_post, "harness": case_harness, "il": case_il, "il_example": case_il_example,
