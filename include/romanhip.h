@@ -644,6 +644,41 @@ int rip_cal_saturation(rip_ctx *ctx, const float *smax, const float *sref, int n
 int rip_cal_mask(rip_ctx *ctx, int ny, int nx, int nb, const uint32_t *lin_dq, const float *pflat0, float pflat_median,
                  const float *dark_slope, const uint32_t *gain_dq, uint32_t *dq);
 
+/* ---- dark and read-noise files ------------------------------------------------------------- */
+/* What runs/2026_July/make_dark_file.py of the reference computes from a set of dark exposures and a noise summary.  The ARRAY
+   arguments of these three entries live where `location` says: RIP_HOST (staged through HBM by the call) or RIP_DEVICE (used
+   where they are); READS is a host array.  The calls return when their kernels are done. */
+
+/* Group means of one dark exposure (make_dark_file.py:55-71) into slot j of a stack of such means.  cube (nreads,ny_file,nx_file)
+   u16; the rows y0 .. y0+ny-1 and the columns 0 .. nx-1 of it are used.  reads[2 ng] as for rip_cal_biascorr.  stack
+   (ng,cap,ny,nx) f32, ALWAYS a device pointer: stack[g][j] = np.mean(cube[a:b].astype(f32), axis=0), i.e. the f32 sum of the
+   reads a .. b-1 in read order, divided once in f32 by f32(b - a).  fits_be16 != 0: the samples are FITS storage (big-endian
+   int16, BZERO = 32768), un-swapped and offset by the kernel.  The cube is read once for all groups.
+   RIP_EINVAL, before anything is launched or copied: ng outside 1..RIP_MAX_GROUPS, a group with reads[2g+1] <= reads[2g], a
+   group that starts below 0 or ends beyond nreads, j outside [0, cap), nx > nx_file, rows outside the frame. */
+int rip_cal_group_means(rip_ctx *ctx, const uint16_t *cube, int location, int nreads, int ny_file, int nx_file, int y0, int ny, int nx,
+                        const int32_t *reads, int ng, int fits_be16, float *stack, int cap, int j);
+
+/* mean[p] = np.nanmean(sigma_clip(stack[:, p], sigma, maxiters, cenfunc='median', stdfunc='std', masked=False)) over the n planes
+   stack[s * plane_stride + p] (f32; plane_stride >= npix, in elements), count[p] (i32, NULL: not wanted) the number of values
+   kept.  astropy is not available to this project: the rule below IS the specification, parity with astropy is unpinned.
+   Per pixel: non-finite values are excluded from the start.  Up to maxiters times, over the survivors: c = median (0.5 * (a + b)
+   of the two middle values for an even count), m = mean, s = sqrt(sum((x - m)^2) / count), all three in f64; lo = c -
+   sigma_lower * s, hi = c + sigma_upper * s; a value is removed when (double)x < lo or (double)x > hi (strict: a constant column
+   keeps everything); stop when nothing was removed.  Result: the f64 sum of the survivors in plane order, divided by their
+   count in f64, rounded once to f32; NaN and count 0 where nothing survives.  The f64 sums behind m and s are taken in a
+   fixed order (not plane order): the result is the same on every run.
+   RIP_EINVAL: n outside 1..512, maxiters outside 0..16, a sigma that is negative or not finite, plane_stride < npix. */
+int rip_cal_sigma_clip_mean(rip_ctx *ctx, const float *stack, int location, int n, size_t plane_stride, size_t npix, double sigma_lower,
+                            double sigma_upper, int maxiters, float *mean, int32_t *count);
+
+/* dark_slope = where(dark2 > 200, dark1, dark2), dark_slope_err likewise from the error planes (make_dark_file.py:79-85), and
+   read_noise = f32(f64(cds) / sqrt(2)) (:157; numpy >= 2 divides a float32 array by the float64 scalar np.sqrt(2) in float64).
+   The five inputs are f32 planes of ny rows of row_stride floats (the [:, :nside] crop of wider frames), the outputs (ny,nx). */
+int rip_cal_dark_planes(rip_ctx *ctx, const float *dark1, const float *dark2, const float *dark1_err, const float *dark2_err,
+                        const float *cds, int location, int ny, int nx, size_t row_stride, float *dark_slope, float *dark_slope_err,
+                        float *read_noise);
+
 /* ---- diagnostics ------------------------------------------------------------------------- */
 /* floating-point options of a context.  "guard_band": relative half-width of the band around the jump
    threshold inside which the significance is re-evaluated in the reference's exact operation order

@@ -2,7 +2,9 @@
 ``saturation``, ``biascorr`` (``runs/2026_July/postprocess_calfiles.py``) and ``mask`` (``runs/2026_July/makemask.py``) -- on the
 GPU (``csrc/calfiles.hip``).  The array-level functions below take numpy arrays or ``DevArray`` planes (results then stay in
 HBM as ``DevArray`` too) and reproduce the scripts' numpy arithmetic bit for bit (numpy >= 2 promotion rules, float32 planes);
-``postprocess_calfiles.run`` and ``makemask.run`` are the scripts' file-level drop-ins.
+``postprocess_calfiles.run`` and ``makemask.run`` are the scripts' file-level drop-ins.  The step in front of them, the ``dark`` and
+``read`` files of ``make_dark_file.py``, is ``darkstack.py`` (``DarkStack``, ``sigma_clip_mean``, ``derive_dark_planes``) and the
+drop-in ``make_dark_file.run``.
 """
 
 import numpy as np
@@ -141,3 +143,6 @@ def derive_mask(lin_dq, pflat0, dark_slope, gain_dq, nb=NBORDER, ctx=None):
     ctx.check(ctx.lib.rip_cal_mask(ctx.h, ny, nx, int(nb), l.ctypes.data, p.ctypes.data, float(med), d.ctypes.data, g.ctypes.data,
                                    dq.ctypes.data))
     return dq
+
+
+from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E402, F401

@@ -1,0 +1,141 @@
+"""Drop-in for the reference's ``runs/2026_July/make_dark_file.py``: the ``dark`` and ``read`` (read noise) files of one read
+pattern from a set of dark exposures and the noise summary solid-waffle made of them, computed on the GPU.
+
+    python -m romanimpreprocess_amd.calfiles.make_dark_file <pattern> <first noise file> <noise summary> <sca> <outfile>
+
+Same conventions: ``settings_<pattern>.yaml`` (``READS``) is read from the working directory, the exposures are ``<first noise
+file>`` with its ``001.fits`` counted up until a file is missing (500 at most), the read-noise file's name is ``<outfile>`` with
+``_dark_`` replaced by ``_read_``, and the two trees have the script's layout and keys (``data``, ``dq``, ``dark_slope``,
+``dark_slope_err``; ``data``, ``resetnoise``, ``anc``, ``amp33`` with the script's placeholder where the summary has no ``AMP33``
+extension).  Every exposure is read ONCE (the script opens each once per group): its samples go to the device as stored and
+``DarkStack`` keeps the group means of all exposures in HBM; where they do not fit, the frame is worked in row bands and the
+exposures are read once per band.  The ``_asdf_data.fits`` dumps of the script are NOT written: astropy is not a dependency of
+this package.  The clipped mean follows the rule of ``rip_cal_sigma_clip_mean``; parity with astropy is unpinned.
+"""
+
+import sys
+from datetime import datetime, timezone
+from os.path import exists
+from os.path import split as pathsplit
+
+import numpy as np
+import yaml
+
+from .. import _native, calio
+from .darkstack import DarkStack, derive_dark_planes
+
+NSIDE = 4096   # dimension of H4RG (make_dark_file.py:26)
+
+
+def _meta(pattern, sca, ng, reftype):
+    return {
+        "author": "make_dark_file.py",
+        "description": "make_dark_file.py",
+        "exposure": {"groupgap": 0, "ma_table_name": pattern, "ma_table_number": 1000000, "nframes": 1, "ngroups": ng,
+                     "p_exptype": "WFI_IMAGE|", "type": "WFI_IMAGE"},
+        "instrument": {"detector": f"WFI{sca:02d}", "name": "WFI", "optical_element": "F158"},
+        "origin": "PIT - romanimpreprocess",
+        "date": datetime.now(timezone.utc).isoformat(),
+        "pedigree": "DUMMY",
+        "reftype": reftype,
+        "telescope": "ROMAN",
+        "useafter": "!time/time-1.2.0 2020-01-01T00:00:00.000",
+    }
+
+
+def noise_files(target):
+    """``make_dark_file.py:38-48``: ``target[:-8] + "NNN.fits"`` for NNN = 001, 002, ... while the file exists, 500 at most."""
+    out = []
+    while len(out) < 500:
+        name = target[:-8] + f"{len(out) + 1:03d}.fits"
+        if not exists(name):
+            break
+        out.append(name)
+    return out
+
+
+def _open_dark(path):
+    hdr, data = calio.read_fits_image(path, 0)
+    if data is None or data.ndim != 3 or hdr.get("BITPIX") != 16 or hdr.get("BZERO", 0) != 32768 or hdr.get("BSCALE", 1) != 1:
+        raise ValueError(f"{path}: a cube of unsigned 16-bit samples (BITPIX 16, BZERO 32768) is needed")
+    return data
+
+
+def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None):
+    """The clipped mean of the group means of ``files``, float32 (ng, ny, min(nside, width)): one pass over the files, or one
+    per band of ``band_rows`` rows (default: as many rows as fit into four fifths of the free device memory)."""
+    import torch
+
+    ctx = ctx or _native.default_context()
+    first = _open_dark(files[0])
+    _, ny, width = first.shape
+    nx = min(int(nside), width)
+    ng = len(reads) // 2
+    if band_rows is None:
+        free = int(torch.cuda.mem_get_info(ctx.device)[0])
+        nreads_bytes = first.shape[0] * width * 2   # the staged samples of one exposure, per row
+        band_rows = max(1, min(ny, int(0.8 * free) // (4 * ng * len(files) * nx + nreads_bytes)))
+    del first
+    out = np.empty((ng, ny, nx), np.float32)
+    for y0 in range(0, ny, int(band_rows)):
+        y1 = min(ny, y0 + int(band_rows))
+        stack = DarkStack(reads, ny, nx, len(files), ctx=ctx, rows=(y0, y1))
+        for j, name in enumerate(files):
+            if j % 10 == 0:
+                print("loading groups", y0, j)
+                sys.stdout.flush()
+            stack.add(_open_dark(name), fits_be16=True)
+        out[:, y0:y1, :] = stack.finish(sigma=3)
+        del stack
+    return out
+
+
+def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, band_rows=None, ctx=None):
+    """Write the dark file ``outfile`` and its read-noise sibling; returns their two paths.  ``reads`` (the flat ``READS`` list)
+    replaces the yaml of the working directory; ``nside`` is the script's constant (smaller frames: for tests)."""
+    sca, nside = int(sca), int(nside)
+    if reads is None:
+        with open("settings_" + pattern + ".yaml") as f:
+            reads = yaml.safe_load(f)["READS"]
+    ng = len(reads) // 2
+    print("Read pattern:", [list(range(int(reads[2 * j]), int(reads[2 * j + 1]))) for j in range(ng)])
+    files = noise_files(target)
+    print(files)
+    if not files:
+        raise FileNotFoundError(f"no noise file {target[:-8]}001.fits")
+    darkave = dark_data(files, reads, nside=nside, band_rows=band_rows, ctx=ctx)
+
+    # the dark current maps, read noise and reset noise of the summary
+    header, summary = calio.read_fits_image(noise_out, 1)
+
+    def plane(key):
+        return np.asarray(summary[int(header[key])], dtype=np.float32)
+
+    dark_slope, dark_slope_err, read_noise = derive_dark_planes(plane("DARK1"), plane("DARK2"), plane("DARK1ERR"), plane("DARK2ERR"),
+                                                                plane("CDS"), nside=nside, ctx=ctx)
+    reset_noise = np.ascontiguousarray(plane("RESET")[:, :nside])
+    try:   # AMP33 if it is there
+        h33, d33 = calio.read_fits_image(noise_out, "AMP33")
+        amp33 = {"valid": True, "med": np.array(d33[0], dtype=np.float32), "std": np.array(d33[1], dtype=np.float32),
+                 "M_PINK": float(h33["M_PINK"]), "RU_PINK": float(h33["RU_PINK"])}
+    except (KeyError, ValueError, TypeError):   # placeholders
+        amp33 = {"valid": False, "med": np.zeros((4096, 128), dtype=np.float32), "std": np.zeros((4096, 128), dtype=np.float32),
+                 "M_PINK": 0.0, "RU_PINK": 0.0}
+
+    calio.write_asdf(outfile, {
+        "roman": {"meta": _meta(pattern, sca, ng, "DARK"), "data": darkave, "dq": np.zeros((nside, nside), np.uint32),
+                  "dark_slope": dark_slope, "dark_slope_err": dark_slope_err},
+        "notes": {"noise_header": header.text}})
+    head, tail = pathsplit(outfile)
+    outfile2 = head + "/" + tail.replace("_dark_", "_read_")
+    calio.write_asdf(outfile2, {
+        "roman": {"meta": _meta(pattern, sca, ng, "READNOISE"), "data": read_noise, "resetnoise": reset_noise,
+                  # this information won't be read by romancal, but some simulators may want it
+                  "anc": {"ACN": header["ACN"], "C_PINK": header["C_PINK"], "U_PINK": header["U_PINK"], "UNIT": "DN"},
+                  "amp33": amp33},
+        "notes": {"noise_header": header.text}})
+    return outfile, outfile2
+
+
+if __name__ == "__main__":
+    run(sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4]), sys.argv[5])

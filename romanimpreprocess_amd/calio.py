@@ -10,7 +10,8 @@ same mapping for
     tags with ``source``/``datatype``/``byteorder``/``shape``[/``offset``/``strides``], inline arrays).
 ``write_asdf`` writes such files (uncompressed blocks) so that synthetic CALDIR sets and L2 products
 can be exchanged with the reference tooling.  ``parse_fits_header`` reads the FITS header text of an exposure's WCS
-(``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy.
+(``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy; ``read_fits_image`` maps the image of one HDU of a FITS file
+(the dark exposures and noise summaries of ``calfiles/make_dark_file.py``).
 """
 
 import bz2
@@ -316,3 +317,59 @@ def parse_fits_header(text):
         if key not in out:
             out[key] = _fits_value(key, card[10:])
     return out
+
+
+# ------------------------------------------------------------------------------- FITS images
+_FITS_BLOCK = 2880
+_FITS_DTYPES = {16: ">i2", -32: ">f4", -64: ">f8"}
+
+
+class FitsHeader(dict):
+    """keyword -> value of one HDU (``parse_fits_header``); ``text`` is the header as stored, cards up to and including END"""
+
+    text = ""
+
+
+def read_fits_image(path, hdu=0):
+    """``(header, data)`` of one HDU of a FITS file: the primary HDU (0) or an image extension, by index or by ``EXTNAME``.
+    ``header`` is a dict (``FitsHeader``); ``data`` is a read-only memory map of the samples AS STORED -- big-endian int16,
+    float32 or float64 (BITPIX 16 / -32 / -64), shape (NAXISn, ..., NAXIS1), ``BZERO`` / ``BSCALE`` not applied -- so that a 2 GB
+    cube is not copied on the host; None for an HDU without data.  A last data block that is not padded to 2880 bytes is
+    accepted.  Nothing else of FITS (tables, other BITPIX, compression, checksums) is read."""
+    path = os.fspath(path)
+    size = os.path.getsize(path)
+    want_name = hdu.strip().upper() if isinstance(hdu, str) else None
+    with open(path, "rb") as f:
+        pos, index = 0, 0
+        while pos < size:
+            f.seek(pos)
+            raw = b""
+            while True:
+                block = f.read(_FITS_BLOCK)
+                if len(block) < _FITS_BLOCK:
+                    raise ValueError(f"{path}: the header of HDU {index} has no END card")
+                raw += block
+                cards = [block[i:i + 80] for i in range(0, _FITS_BLOCK, 80)]
+                if any(c[:8] == b"END     " and not c[8:].strip() for c in cards):
+                    break
+            header = FitsHeader(parse_fits_header(raw))
+            header.text = raw[:raw.find(b"END" + b" " * 77) + 80].decode("ascii")
+            start = pos + len(raw)
+            naxis = int(header.get("NAXIS", 0))
+            shape = tuple(int(header[f"NAXIS{i}"]) for i in range(naxis, 0, -1))
+            bitpix = int(header.get("BITPIX", 8))
+            nbytes = abs(bitpix) // 8 * (int(header.get("PCOUNT", 0)) + int(np.prod(shape, dtype=np.int64))) * int(header.get("GCOUNT", 1)) \
+                if naxis else 0
+            if index == hdu if want_name is None else str(header.get("EXTNAME", "")).strip().upper() == want_name:
+                if not naxis or not nbytes:
+                    return header, None
+                if index and header.get("XTENSION", "").strip() != "IMAGE":
+                    raise ValueError(f"{path}: HDU {index} is not an image extension")
+                if bitpix not in _FITS_DTYPES:
+                    raise ValueError(f"{path}: BITPIX {bitpix} of HDU {index} is not supported (16, -32, -64)")
+                if start + nbytes > size:
+                    raise ValueError(f"{path}: HDU {index} needs {nbytes} bytes of data, the file ends after {size - start}")
+                return header, np.memmap(path, dtype=_FITS_DTYPES[bitpix], mode="r", offset=start, shape=shape)
+            pos = start + (nbytes + _FITS_BLOCK - 1) // _FITS_BLOCK * _FITS_BLOCK
+            index += 1
+    raise KeyError(f"{path}: no HDU {hdu!r}")
