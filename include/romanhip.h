@@ -196,10 +196,21 @@ void rip_host_free(rip_ctx *ctx, void *p);
    gen_cal_image.py:217-221 and the flat of flatutils.get_flat) */
 int rip_caldir_upload(rip_ctx *ctx, int sca_slot, const rip_caldir_desc *desc);
 int rip_caldir_drop(rip_ctx *ctx, int sca_slot);
+/* 1: the set in sca_slot passed the screen rip_caldir_upload runs over its device copies -- every plane of dark.data and of
+   biascorr, the Legendre planes, Smin, Smax, Sref, amp33.med finite and within 2^20, Smax - Smin (f32) non-zero, the (f32)
+   gain within 2^-10 .. 2^10 in magnitude, ipc4d within 2^4, slope_ref within 2^10 -- so that group 0 of ANY u16 ramp comes
+   out of the chain finite (the chain of bounds: csrc/caldir.hip) and the fused kernel may skip an excluded first group
+   (option "skip_first").  0: it did not (one NaN anywhere is enough; such a set runs the full kernel form, same results).
+   RIP_EINVAL for an empty slot. */
+int rip_caldir_first_group_safe(rip_ctx *ctx, int sca_slot);
 
 /* plan: replaces meta{ngrp,N,tbar,tau,K,jump_detect_pars} of gen_cal_image.py:123-145,439-444 */
 int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *desc, int *plan_id);
 int rip_plan_destroy(rip_ctx *ctx, int plan_id);
+/* 1: a plan made from desc excludes the first group and gives group 0 the weight zero in the full-ramp weights and in the
+   weights of every truncated variant (what skipping group 0 in the fused kernel rests on; rip_plan_create checks the same of
+   the weights it uploads); 0 otherwise.  Host arithmetic: needs no context and no GPU. */
+int rip_plan_desc_first_weight_zero(const rip_plan_desc *desc);
 
 /* the chain: replaces gen_cal_image.py:531-629 (stages selects a sub-chain).  Asynchronous with
    respect to the host when location == RIP_DEVICE (use rip_synchronize / the stream).
@@ -452,6 +463,11 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
    "chain_reserve" -- (default 8) workgroup slots the 256-column fused kernel's grid leaves free; "chain_quad" -- (default 1) a
                 last strip of at most 64 live columns is covered by workgroups whose 64-column wave columns (four or six) take a row range each
                 (4096 x 4096: 504 workgroups of 139 steps instead of 510 of 143; timing-neutral, profiles/r04_summary.md);
+   "skip_first" -- (default 1) the fused kernel neither loads nor evaluates group 0 of the ramp where the result cannot depend
+                on it: an excluded first group that is the single read 0, weight zero in every fit variant, a u16 cube, no
+                corrected cube asked for, no caller's channel lines on the device, and a CALDIR set that passed the screen of
+                rip_caldir_first_group_safe; the pre-pass then makes the tables of groups 1 .. G-1 only.  0 = every launch takes
+                the full form.  rip_last_chain_first_group tells which form ran;
    "pink_form" -- the complex-to-real transform of the 1/f frames: -1 (default) the library's own two-pass transform for
                 power-of-two frame lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise, 0 hipFFT for every length;
    "overlap" -- run the reference-pixel pre-pass of a ramp on a second stream so that it overlaps the previous ramp's
@@ -461,6 +477,8 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
 /* how the last rip_calibrate ran: 0 = stage kernels, 2 = the fused kernel (1 and 3 were the general and the wave-private fused
    kernels of rounds 1-2) */
 int rip_last_chain_form(rip_ctx *ctx);
+/* 1: the fused launch of the last rip_calibrate skipped group 0 (option "skip_first"); 0: it did not, or the stage kernels ran */
+int rip_last_chain_first_group(rip_ctx *ctx);
 
 /* Is a fused-kernel form compiled for a complete chain with this many Legendre planes, groups and these ipc4d / gain dtypes
    (RIP_F32 / RIP_F64)?  2 = yes (the value rip_last_chain_form reports), 0 = such a ramp takes the stage kernels.  Needs no

@@ -117,8 +117,10 @@ SYMBOLS = {
     "rip_host_free": (None, [_VP, _VP]),
     "rip_caldir_upload": (_I, [_VP, _I, C.POINTER(CaldirDesc)]),
     "rip_caldir_drop": (_I, [_VP, _I]),
+    "rip_caldir_first_group_safe": (_I, [_VP, _I]),
     "rip_plan_create": (_I, [_VP, C.POINTER(PlanDesc), C.POINTER(_I)]),
     "rip_plan_destroy": (_I, [_VP, _I]),
+    "rip_plan_desc_first_weight_zero": (_I, [C.POINTER(PlanDesc)]),
     "rip_calibrate": (_I, [_VP, _I, _I, C.c_uint, C.POINTER(RampDesc), C.POINTER(Outputs)]),
     "rip_calibrate_batch": (_I, [_VP, _I, _I, C.c_uint, _I, C.POINTER(RampDesc), C.POINTER(Outputs)]),
     "rip_calibrate_batch_completed": (_I, [_VP]),
@@ -166,6 +168,7 @@ SYMBOLS = {
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_last_chain_form": (_I, [_VP]),
+    "rip_last_chain_first_group": (_I, [_VP]),
     "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
     "rip_chain_geometry_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "rip_last_chain_geometry": (_I, [_VP, C.POINTER(_I)]),
@@ -311,6 +314,17 @@ class Context:
     def last_chain_form(self):
         """0 = stage kernels, 2 = the fused kernel (last calibrate call; 1 and 3 were the general and wave-private fused kernels of rounds 1-2)."""
         return int(self.lib.rip_last_chain_form(self.h))
+
+    def last_chain_first_group(self):
+        """1 = the fused launch of the last calibrate call skipped group 0 (option "skip_first"), 0 = it did not (or stage kernels)."""
+        return int(self.lib.rip_last_chain_first_group(self.h))
+
+    def caldir_first_group_safe(self, slot):
+        """True where the set in ``slot`` passed the upload screen that lets the fused kernel skip an excluded first group."""
+        rc = int(self.lib.rip_caldir_first_group_safe(self.h, int(slot)))
+        if rc < 0:
+            self.check(rc)
+        return rc == 1
 
     def last_chain_geometry(self):
         """launch geometry of the last calibrate call's fused kernel (keys ``GEOMETRY_FIELDS``); all zeros after a stage-kernel run"""

@@ -164,6 +164,10 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value) {
         ctx->chain_quad = value != 0;
         return RIP_OK;
     }
+    if (name && strcmp(name, "skip_first") == 0) {   // 0: every fused launch loads and evaluates group 0 (A/B timing, tests)
+        ctx->skip_first = value != 0;
+        return RIP_OK;
+    }
     if (name && strcmp(name, "chain_reserve") == 0) {
         ctx->chain_reserve = value < 0 ? 0 : value;
         return RIP_OK;
@@ -237,6 +241,12 @@ int rip_prepass_stamps(rip_ctx *ctx, int nwg, unsigned long long *out) {
 }
 
 int rip_last_chain_form(rip_ctx *ctx) { return ctx ? ctx->last_form : RIP_EINVAL; }
+int rip_last_chain_first_group(rip_ctx *ctx) { return ctx ? (ctx->last_form == 2 ? ctx->last_first_group : 0) : RIP_EINVAL; }
+int rip_caldir_first_group_safe(rip_ctx *ctx, int slot) {
+    if (!ctx) return RIP_EINVAL;
+    if (slot < 0 || slot >= (int)ctx->cals.size() || !ctx->cals[slot].valid) return rip_fail(ctx, RIP_EINVAL, "caldir slot %d is empty", slot);
+    return ctx->cals[slot].first_group_safe ? 1 : 0;
+}
 int rip_last_chain_geometry(rip_ctx *ctx, int out[8]) {
     if (!ctx || !out) return RIP_EINVAL;
     for (int i = 0; i < 8; ++i) out[i] = ctx->last_form == 2 ? ctx->last_geo[i] : 0;

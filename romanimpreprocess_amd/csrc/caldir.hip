@@ -1,4 +1,6 @@
 // The device-resident CALDIR of one SCA (include/romanhip.h: rip_caldir_upload, rip_caldir_drop).  Host code only.
+#include <cmath>
+
 #include "rip_host.h"
 
 namespace {
@@ -9,6 +11,69 @@ int dev_copy_in(rip_ctx *ctx, void **dst, const void *src, size_t bytes) {
     hipError_t e = hipMalloc(dst, bytes);
     if (e != hipSuccess) return rip_fail(ctx, RIP_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     RIP_HIP(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return RIP_OK;
+}
+
+// ---- The screen behind RipCal::first_group_safe.
+// With an excluded first group the fit gives d[0] (group 0 after reference pixels, bias, linearity, IPC and the division by the
+// gain) the weight +-0 and tests no difference on it: d[0] reaches the results only as 0 * d[0] and d[0] - d[1], i.e. only when
+// it is not finite -- or so large that d[0] - d[1] overflows for a finite d[1] (|d[0]| < 2^103 rules that out: half an ulp of the
+// largest f32).  The fused kernel may therefore leave group 0 out (chain2_form.h, "SKIPPED FIRST GROUP") wherever |d[0]| < 2^103
+// is known WITHOUT computing it.  It is, for every u16 ramp, when the arrays of the set that reach group 0 pass these bounds:
+//     V = 2^20 >= |dark.data|, |biascorr| (every plane: which one is "group 0" depends on the ramp), |Legendre planes|,
+//                 |Smin|, |Smax|, |Sref|, |amp33.med|
+//     2^-10 <= |gain| <= 2^10 (f32),   |ipc4d| <= 2^4,   |slope_ref| <= 2^10,   f32(Smax - Smin) != 0,   ny <= 2^16
+// (the values of real and synthetic sets are below 2^17, gains near 1.5, IPC coefficients within [0, 1], the slope of order 1).
+// The chain of bounds, each line one rounded operation of the kernels (rounding adds at most one part in 2^23: every bound below
+// is rounded up generously), S a u16 sample < 2^16:
+//   reference output   amp33 - med                          < 2^21   its medians (mean of two middle elements)      < 2^21
+//                      minus the block's median, row medians < 2^22   minus their median ctr                         < 2^23
+//   row correction     rc = slope_ref * (med - ctr), f64     < 2^33   (0 without a reference output)
+//   v1 = S - dark      < 2^21                                         v2 = f32(f64(v1) - rc)                          < 2^34
+//   channel line       medians b, t of v2 over the reference rows < 2^34;  m = (t - b) / (ny - 4), ny - 4 >= 12      < 2^32
+//                      c = b - 1.5 m < 2^35;  iel = m * y + c, y < 2^16                                             < 2^49
+//                      (a caller's line is checked per call against |m| <= 2^32, |c| <= 2^35: calibrate.hip)
+//   v3 = f32(f64(v2) - iel) < 2^50    S' = v3 + dark - biascorr < 2^52    t = 2 (S' - Smin)                          < 2^54
+//   z = t / span - 1   span is finite and non-zero, t finite: the quotient is finite or +-inf, never NaN (0/0 and non-finite
+//                      operands are the only sources of NaN); through the shared reciprocal (taken when 1e-18 < |span| < 1e18)
+//                      |t * (1/span)| < 2^114 and every fma of the correction steps stays finite.  Group 0 of a plan with
+//                      do_not_flag_first is then CLIPPED to [-1, 1] (inf clips), so |z| <= 1 and no extrapolation branch
+//   Legendre series    p_0 = 1, p_1 = z, p_{L+1} = (c1 z) p_L - c2 p_{L-1} with c1 < 2, c2 < 1: |p_{L+1}| < 2 |p_L| + |p_{L-1}|,
+//                      so |p_L| < 3^L <= 3^10 < 2^16 for the at most 11 planes;  phi = sum of 11 terms cf_L p_L               < 2^40
+//   flagged pixels     S' - Sref < 2^53 in place of phi
+//   x = gain * phi (border pixels: phi)                      < 2^63
+//   first iterate      f = sum of nine k x < 9 * 2^4 * 2^63 < 2^71;   O1 = 2 x - f                                    < 2^72
+//   second iterate     f' = sum of nine k O1 < 2^80;                   O2 = (O1 + x) - f'                              < 2^81
+//   d[0] = O2 / gain   |gain| >= 2^-10                                                                               < 2^91
+// (f64 ipc4d: the iterates and the division are f64 with the same bounds, rounded to f32 at the end.)  So |d[0]| < 2^91: twelve
+// binades below the 2^103 the argument needs, 36 below overflow.  A set that fails takes the full kernel form, call by call
+// (RipCal::has_inf: one with an INFINITE value among these arrays takes the stage kernels).
+constexpr double SCREEN_V = 1048576.0, SCREEN_GAIN = 1024.0, SCREEN_K = 16.0, SCREEN_SLOPE = 1024.0;
+
+int screen_first_group(rip_ctx *ctx, RipCal &c, const rip_caldir_desc *d) {
+    c.first_group_safe = c.has_inf = false;
+    // what the fused chain needs anyway
+    if (!c.dark_data || !c.has_bias || !c.lin_coefs || !c.has_ipc || c.gain_dtype != RIP_F32) return RIP_OK;
+    const size_t npix = (size_t)c.ny * c.nx;
+    DevBuf<uint32_t> bad(ctx);
+    int rc;
+    if ((rc = bad.alloc(1))) return rc;
+    RIP_HIP(ctx, hipMemsetAsync(bad.p, 0, 4, ctx->stream));
+    if ((rc = rip_launch_screen(ctx, c.dark_data, RIP_F32, npix * c.ngrp_dark, 0.0, SCREEN_V, bad.p)) ||
+        (rc = rip_launch_screen(ctx, c.bias, RIP_F32, npix * c.ngrp_bias, 0.0, SCREEN_V, bad.p)) ||
+        // Legendre planes, Smin, Smax, Sref: planes [0, NP + 3) of the slab
+        (rc = rip_launch_screen(ctx, c.slab, RIP_F32, npix * (size_t)(c.lin_nplanes + 3), 0.0, SCREEN_V, bad.p)) ||
+        (rc = rip_launch_screen_span(ctx, c.lin_smin, c.lin_smax, npix, bad.p)) ||
+        (rc = rip_launch_screen(ctx, c.gain, RIP_F32, npix, 1.0 / SCREEN_GAIN, SCREEN_GAIN, bad.p)) ||
+        (rc = rip_launch_screen(ctx, c.ipc, c.ipc_dtype, 9 * npix, 0.0, SCREEN_K, bad.p)) ||
+        (rc = rip_launch_screen(ctx, c.amp33_med, RIP_F32, (size_t)c.ny * RIP_CW, 0.0, SCREEN_V, bad.p)))
+        return rc;
+    uint32_t h_bad = 1;
+    RIP_HIP(ctx, hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const bool scalars_ok = c.ny <= 65536 && (!d->amp33_med || std::fabs(d->refout_slope) <= SCREEN_SLOPE);
+    c.first_group_safe = h_bad == 0 && scalars_ok;
+    c.has_inf = (h_bad & 2u) != 0 || (d->amp33_med && std::isinf(d->refout_slope));
     return RIP_OK;
 }
 
@@ -192,6 +257,7 @@ int rip_caldir_upload(rip_ctx *ctx, int slot, const rip_caldir_desc *d) {
     }
 #undef UP
 #undef UPS
+    if ((rc = screen_first_group(ctx, c, d))) return rc;
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return rip_fail(ctx, RIP_EHIP, "caldir upload: %s", hipGetErrorString(e));
     c.valid = true;

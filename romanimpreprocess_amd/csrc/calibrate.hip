@@ -1,6 +1,8 @@
 // The chain driver (include/romanhip.h: rip_calibrate) and the staging of a ramp handed over in host memory.  Host code only.
 #include <string.h>
 
+#include <cmath>
+
 #include "rip_host.h"
 
 // bytes that take a ramp's inputs: data, amp33, groupdq, pixeldq, area factor, channel lines, each in a 256-byte aligned slot
@@ -104,6 +106,26 @@ struct Calibration {
     const float *cur = nullptr;         // the corrected cube
     const uint32_t *pdq_mid = nullptr;  // pixeldq after the cube stage
     bool ran_fused = false;
+    bool skip0 = false;   // the fused kernel of this call skips group 0, and the pre-pass leaves its tables out
+
+    // ---- May this call's fused kernel skip group 0 (option "skip_first")?  Decided before the pre-pass.  Group 0 must be dead in
+    // the fit (rip_chain_may_skip_first: the plan, and that the fused kernel WILL run) and known to be finite without being
+    // computed: a u16 cube on a CALDIR set that passed the screen at upload (caldir.hip: the chain of bounds), no corrected cube
+    // to write, and channel lines that are either the pre-pass's own or a HOST array whose group-0 entries are within the
+    // bounds that chain assumes of them (|m| <= 2^32, |c| <= 2^35; lines on the device cannot be looked at here).
+    void choose_skip() {
+        skip0 = false;
+        if (!(do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 && !out->cube && c.first_group_safe)) return;
+        const bool with_flat = (stages & RIP_STAGE_FLAT) && c.has_flat;
+        const int merged = c.merged_plane[(with_flat ? 1 : 0) | ((stages & RIP_STAGE_DARK) ? 2 : 0)];   // as fused_chain sets it
+        if (!rip_chain_may_skip_first(ctx, plan, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype, merged, c.nb)) return;
+        if (in->channel_lines) {
+            if (!host) return;
+            for (int ch = 0; ch < nch; ++ch)
+                if (!(std::fabs(in->channel_lines[2 * ch]) <= 4294967296.0 && std::fabs(in->channel_lines[2 * ch + 1]) <= 34359738368.0)) return;
+        }
+        skip0 = true;
+    }
 
     int validate(int slot, int plan_id) {
         if (in->location != out->location) return rip_fail(ctx, RIP_EINVAL, "calibrate: inputs and outputs must share a location");
@@ -164,6 +186,7 @@ struct Calibration {
                   ? (char *)rip_ws(ctx, RIP_WS_TABLES, 2 * tab_bytes + npix * 4 + 512)
                   : nullptr;
         par = ctx->parity;
+        choose_skip();
         // (by situation: where the fused kernel fills the LDS the pre-pass of the next ramp finds no room beside it, runs when it
         // drains, and the single-launch form in front of the own ramp is the shorter way: 1.121 against 1.140 ms per ramp at f64
         // ipc4d x 8 groups, profiles/r04_summary.md)
@@ -191,6 +214,7 @@ struct Calibration {
         lines = rowcorr_t + (size_t)G * ny;
         RefpixArgs ra{d.data, in->data_dtype, c.dark_data, c.has_amp33 ? d.amp33 : nullptr, c.amp33_med, c.refout_slope,
                       d.channel_lines, rowcorr, rowcorr_t, lines, ny, nx, G, overlap ? 1 : 0, pre};
+        ra.g0 = skip0 ? 1 : 0;   // (both forms work group by group: the tables of a skipped group 0 are neither made nor read)
         if (overlap) {
             if (ctx->ev_done_valid[par]) RIP_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_done[par], 0));
             // what the pre-pass stream waits for before it reads the inputs (rip_ramp_desc::inputs_ready / ready_event): the
@@ -263,10 +287,14 @@ struct Calibration {
     // Level-1 (u16) cube; sub-chains and f32 cubes take the stage-by-stage kernels
     int fused_chain() {
         ctx->last_form = 0;
+        ctx->last_first_group = 0;
         memset(ctx->last_geo, 0, sizeof ctx->last_geo);
-        if (!(ctx->use_fused && do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
-              rip_chain_supported(ctx, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype)))
+        if (!(ctx->use_fused && !c.has_inf && do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
+              rip_chain_supported(ctx, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype))) {
+            // (a call planned without group 0 must reach the fused kernel: the stage kernels would read unwritten tables)
+            if (skip0) return rip_fail(ctx, RIP_ESTATE, "calibrate: a call planned without group 0 does not take the fused kernel");
             return RIP_OK;
+        }
         ChainArgs ca;
         memset(&ca, 0, sizeof ca);
         ca.data = d.data;
@@ -308,7 +336,9 @@ struct Calibration {
         ca.merged_dq = c.merged_plane[((flat ? 1 : 0) | ((stages & RIP_STAGE_DARK) ? 2 : 0))];
         ca.dbg = ctx->chain_dbg;
         ca.dbg_buf = ctx->chain_dbg_buf;
-        const int rc = rip_launch_chain(ctx, plan, ca, c.lin_nplanes, c.ipc_dtype);
+        const int rc = rip_launch_chain(ctx, plan, ca, c.lin_nplanes, c.ipc_dtype, skip0);
+        // (choose_skip has asked the launcher's own questions: the stage kernels would find group 0's tables unwritten)
+        if (rc == 1 && skip0) return rip_fail(ctx, RIP_ESTATE, "calibrate: the fused kernel declined a launch planned without group 0");
         // 1: no fused kernel for this plan / CALDIR set (flag words not mergeable, unusual difference mask): stage kernels
         if (rc == 1) return RIP_OK;
         if (rc) return rc;

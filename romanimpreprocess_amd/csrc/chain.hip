@@ -6,9 +6,9 @@
 #include "chain2_form.h"
 
 template <int NP, typename KT, int PART>
-int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
+int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0);
 
-typedef int (*ChainLauncher)(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
+typedef int (*ChainLauncher)(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0);
 
 // part of the group-count list (rip_common.h: RIP_CHAIN_G_PART*) that holds G, -1 when the fused kernel has no form for G
 static int chain_part(int G) {
@@ -115,11 +115,22 @@ bool rip_chain_fills_lds(int G, int k_dtype) {
 }
 
 // returns the launch status, or 1 when no fused kernel fits this plan / CALDIR set (the caller then takes the stage kernels)
-int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype) {
+int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype, bool skip0) {
     const ChainLauncher launch = chain_launcher(nplanes, a.ngrp, k_dtype);
     // (merged_dq < 0: this CALDIR set's flag words cannot be merged, RipCal)
     if (!launch || !ctx->use_chain2 || a.merged_dq < 0) return 1;
-    const int rc = launch(ctx, plan, a);
-    if (rc != 1) ctx->last_form = 2;
+    const int rc = launch(ctx, plan, a, skip0);
+    if (rc != 1) ctx->last_form = 2, ctx->last_first_group = skip0 ? 1 : 0;
     return rc;
+}
+
+// The conditions under which rip_launch_chain above and the launcher (chain2_kernel.h: launch_chain2, launch_chain2_s) run the
+// fused kernel, restated so that a caller can know it BEFORE the pre-pass (which then leaves group 0's tables out), plus what
+// the plan must be for group 0 to be dead in the fit: an excluded first group that is the single read 0 (no linearity flag
+// from it), exactly the full set of tested differences from group 1 on, and the weight zero for group 0 in every variant.
+bool rip_chain_may_skip_first(const rip_ctx *ctx, const RipPlan *plan, int nplanes, int G, int k_dtype, int gain_dtype, int merged_dq,
+                              int nb) {
+    if (!ctx->skip_first || !ctx->use_fused || !ctx->use_chain2 || !plan || merged_dq < 0 || nb < 2) return false;
+    if (!rip_chain_supported(ctx, nplanes, G, k_dtype, gain_dtype)) return false;
+    return plan->h.start == 1 && plan->h.do_not_flag_first && plan->k0_zero && plan->dense.valid == rip_full_valid_of(G, 1);
 }

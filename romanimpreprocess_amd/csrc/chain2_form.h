@@ -48,6 +48,28 @@
 //     and from the flag propagation (propagate_flags_packed<G>: missing groups count as DO_NOT_USE in its all-groups test only).
 // Every `g < G` test is a compile-time constant after unrolling; with even G the guarded code does not exist (if constexpr), so
 // the 6-, 8- and 16-group kernels compile to the instruction streams they had before.
+//
+// SKIPPED FIRST GROUP (template parameter SKIP0 of the kernel, START = 1 only): the mirror image -- the FIRST half of pair 0 is
+// dead.  With an excluded first group the fit gives d[0] the weight +-0 and tests no difference on it, so d[0] reaches the
+// results only as 0 * (d[0] - d[1]) added to a sum that starts at +0: nothing, unless d[0] is not finite (or so large that the
+// difference overflows).  The launcher takes this form only where |d[0]| < 2^103 is known without computing it: a CALDIR set
+// that passed the screen at upload (caldir.hip: the bounds and the chain of bounds), a u16 cube, do_not_flag_first, no cube
+// output, weight zero in every variant (calibrate.hip: choose_skip; chain.hip: rip_chain_may_skip_first).  Everything else
+// runs the SKIP0 = false instantiation, which is the kernel as it was.  The same items as for odd G; group 0 is
+//   - never loaded: cube, dark and biascorr samples, its row corrections (the scalar loads start at group 1) and its channel
+//     lines (the LDS table holds zeros there) -- the pre-pass does not make the tables of group 0 in front of this form, so its
+//     entries are unwritten memory.  Its groupdq BYTE stays live: loaded, packed, propagated and stored exactly as before,
+//   - a copy of its partner inside the linearity block (same z: no exception and no wave vote of its own; the clip of
+//     do_not_flag_first has nothing left to clip), its series is not evaluated, then a ZERO in the x ring; it sets no flag
+//     (it set none before: do_not_flag_first),
+//   - a stored zero in the O1 ring, and whatever the pair arithmetic gives after the second iterate: nobody reads it (the
+//     arithmetic of a dead half has no consumer and is removed by the compiler: the x / O1 ring halves are unread in that sense),
+//     outside the f64 division (not divided, not in its range vote), and the fit role overwrites d[0] with zero before the fit,
+//   - outside the fit: no term in the slope sum of fit_full_pk_a_t (the sum starts with group 1's term added to +0, as it did
+//     after (+0) + (+-0)), none in fit_full_regs / trunc_layers (the two-point weights have K[0] = 0 too), absent from
+//     rip_full_valid<G, 1> as it always was.
+// The pairs keep their positions (d1 = dA[0].y); with odd G both dead halves exist side by side.  Every test on SKIP0 is a
+// compile-time constant, so the SKIP0 = false kernels compile to the instruction streams they had before.
 // Round 3 ran the narrow forms as 128-column workgroups, three (two) per CU: 3 (2) waves per SIMD at <= 168 (256) VGPRs.  What they
 // paid is windows at a 124-column pitch: a window row of a byte plane is one 128-byte line, misaligned it touches two (u16: two ->
 // three, f32: four -> five), and the lines shared with the neighbouring strip have left L2 by the time that strip wants them -- a

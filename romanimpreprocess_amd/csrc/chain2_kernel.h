@@ -134,10 +134,11 @@ __device__ __forceinline__ void c2_ipc9_batch(const VT (&v)[NBB][9], const doubl
 // multiply and two fma: the same operations on the same operands as the expansion, hence the same bits, as long as v_div_scale
 // scales nothing and v_div_fixup has nothing to fix -- which holds for 2^-60 < |b| < 2^60 and every quotient (rounded to f32)
 // finite, non-zero and within 2^-59 .. 2^59 (then 2^-119 < |a| < 2^119: far from every scaling rule of the instruction).  One
-// wave vote checks that; otherwise every lane takes the division operator.
-template <int NG, int NA>
+// wave vote checks that; otherwise every lane takes the division operator.  G0: the first value divided (1 where group 0 is
+// skipped: it is neither divided nor in the vote).
+template <int NG, int NA, int G0 = 0>
 __device__ __forceinline__ void c2_div64_shared(const double (&a)[NA], float bf, bool use, float (&qf)[NA]) {
-    static_assert(NA >= NG, "the first NG of NA values are divided");
+    static_assert(NA >= NG && G0 >= 0 && G0 < NG, "the values G0 .. NG - 1 of NA are divided");
     const double b = (double)bf;
     double y = __builtin_amdgcn_rcp(b);
     double e = __builtin_fma(-b, y, 1.0);
@@ -146,7 +147,7 @@ __device__ __forceinline__ void c2_div64_shared(const double (&a)[NA], float bf,
     y = __builtin_fma(y, e, y);
     float asum = 0.0f, amin = 3.0e38f;   // NaN / Inf show in the sum, zeros and tiny values in the minimum
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
+    for (int g = G0; g < NG; ++g) {
         const double q0 = a[g] * y;
         const double r = __builtin_fma(-b, q0, a[g]);
         qf[g] = (float)__builtin_fma(r, y, q0);
@@ -156,15 +157,18 @@ __device__ __forceinline__ void c2_div64_shared(const double (&a)[NA], float bf,
     const bool ok = rcp_safe(bf) && asum < 5.7e17f && amin > 1.8e-18f;
     if (!__all(ok || !use)) {
 #pragma unroll
-        for (int g = 0; g < NG; ++g) qf[g] = (float)(a[g] / b);
+        for (int g = G0; g < NG; ++g) qf[g] = (float)(a[g] / b);
     }
 }
 
-template <int NP, int G, int START, typename KT>
+template <int NP, int G, int START, typename KT, bool SKIP0 = false>
 __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C2Form<G + (G & 1), sizeof(KT) == 8>::wps)) void chain2_kernel(
     ChainArgs a, const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars, const float *__restrict__ kvals,
     const RipDiff *__restrict__ diffs, double guard) {
     static_assert(G > 4 && G <= 16, "pairs of groups; the groupdq bytes travel packed four to a word");
+    // SKIP0: the first half of pair 0 is DEAD (chain2_form.h, "SKIPPED FIRST GROUP"): the launcher takes this form only where
+    // the fit gives group 0 the weight zero, tests no difference on it, and d[0] is known to be finite without computing it
+    static_assert(!SKIP0 || START == 1, "group 0 can be skipped only where the fit excludes it");
     // odd G: GE = G + 1 register / ring slots, the last one DEAD (see the note above C2Form); g < G guards are compile-time
     constexpr int GE = G + (G & 1);
     using F = C2Form<GE, sizeof(KT) == 8>;
@@ -248,7 +252,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     const int chr = cc / RIP_CW - ch0;
     for (int i = tid; i < NLC * G * 2; i += F::threads) {
         const int ch = i / (G * 2), g = (i / 2) % G, w = i & 1;
-        LN[i] = (ch0 + ch < nch) ? a.lines[(g * nch + ch0 + ch) * 2 + w] : 0.0;
+        LN[i] = (ch0 + ch < nch && !(SKIP0 && g == 0)) ? a.lines[(g * nch + ch0 + ch) * 2 + w] : 0.0;   // (SKIP0: group 0's lines may be unwritten)
     }
     __syncthreads();
 
@@ -371,10 +375,13 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                 if constexpr (GE > G) {
                     if (g >= G) continue;   // the dead half of an odd ramp's last pair is never loaded
                 }
-                rr.S[g] = c2_ld_u16<SA>(rs, cc2, o2);
+                const bool flags_only = SKIP0 && g == 0;   // a skipped first group keeps its flag byte, nothing else is loaded
+                if (!flags_only) rr.S[g] = c2_ld_u16<SA>(rs, cc2, o2);
                 rr.q[g] = c2_ld_u8<F::wring ? SA : 0>(rq, cc1, o1);   // (16 groups: the fit role reads these bytes again)
-                rr.dk[g] = c2_ld_f32<SA>(rd, cc4, o4);
-                rr.bs[g] = c2_ld_f32<SA>(rb, cc4, o4);
+                if (!flags_only) {
+                    rr.dk[g] = c2_ld_f32<SA>(rd, cc4, o4);
+                    rr.bs[g] = c2_ld_f32<SA>(rb, cc4, o4);
+                }
                 o4 += pl4;
                 o2 += pl4 >> 1;
                 o1 += npix;
@@ -415,13 +422,15 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
         constexpr int CO_STEP = (NCO + GP - 1) / GP;  // issued per pair of C
         RowRegs<NP, GE> rr;
         if constexpr (GE > G) rr.S[G] = rr.q[G] = 0u, rr.dk[G] = rr.bs[G] = 0.0f;
+        if constexpr (SKIP0) rr.S[0] = 0u, rr.dk[0] = rr.bs[0] = 0.0f;
         fetch_row(R0 - 2, rr);
         int so_c = (R0 - 5 + 2 + 3000) % 3;  // O1 ring slot of row yc = r + 2
         double rcn[G];  // row corrections of the row the next step ingests
         {
             const RIP_K double *rt = rip_k(kargs->a.rowcorr_t) + (size_t)min(max(R0 - 2, 0), ny - 1) * G;
 #pragma unroll
-            for (int g = 0; g < G; ++g) rcn[g] = rt[g];
+            for (int g = SKIP0 ? 1 : 0; g < G; ++g) rcn[g] = rt[g];   // (SKIP0: group 0's corrections are neither made nor read)
+            if constexpr (SKIP0) rcn[0] = 0.0;
         }
         for (int r = R0 - 5; r <= R0 + rows_wg; ++r, so_c = (so_c == 2) ? 0 : so_c + 1) {
             const RIP_K ChainArgs *ka = &c2_args(kargs)->a;  // S1 copy of the argument block
@@ -436,7 +445,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             {
                 const RIP_K double *rt = rip_k(ka->rowcorr_t) + (size_t)min(max(yi + 1, 0), ny - 1) * G;
 #pragma unroll
-                for (int g = 0; g < G; ++g) rcn[g] = rt[g];
+                for (int g = SKIP0 ? 1 : 0; g < G; ++g) rcn[g] = rt[g];
             }
             const bool a_full = do_a && yi >= 0 && yi < ny;  // wave-uniform
             // A: two pairs of groups at a time -- reference-pixel/bias arithmetic and z of both pairs, then their two
@@ -476,6 +485,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                                     continue;
                                 }
                             }
+                            if constexpr (SKIP0) {
+                                if (g == 0) {   // skipped first group: its flag byte travels on, its value is its partner's (below)
+                                    w[0] |= rr.q[0] & 0xffu;
+                                    continue;
+                                }
+                            }
                             float S = (float)rr.S[g];
                             const float dk = rr.dk[g];
                             float v = S - dk;
@@ -487,6 +502,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                             if (act) S = S - rr.bs[g];
                             Sv[e] = S;
                             w[g / 4] |= (rr.q[g] & 0xffu) << (8 * (g & 3));
+                        }
+                        if constexpr (SKIP0) {
+                            if (p == 0) Sv[0] = Sv[1];   // same z as its partner: no exception and no wave vote of its own
                         }
                         SS[b] = f2{Sv[0], Sv[1]};
                         const f2 t = SS[b] - f2{smin, smin};
@@ -502,7 +520,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
 #pragma unroll
                     for (int b = 0; b < PB; ++b) {
                         f2 z = quo[b] + (-1.0f);
-                        if (pb + b == 0 && a.do_not_flag_first) z.x = clip2<float>(z.x, -1.0f, 1.0f);
+                        if constexpr (!SKIP0) {   // (SKIP0 implies do_not_flag_first; z.x is a copy of z.y there)
+                            if (pb + b == 0 && a.do_not_flag_first) z.x = clip2<float>(z.x, -1.0f, 1.0f);
+                        }
                         zz[b] = z;
                         any_ex = any_ex || (fabsf(z.x) > 1.0f) || (fabsf(z.y) > 1.0f);
                     }
@@ -547,6 +567,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                             float ph[2];
 #pragma unroll
                             for (int e = 0; e < 2; ++e) {
+                                if constexpr (SKIP0) {
+                                    if (pb + b == 0 && e == 0) {   // skipped first group: no series
+                                        ph[0] = 0.0f;
+                                        continue;
+                                    }
+                                }
                                 const float ze = e ? zz[b].y : zz[b].x;
                                 const float az = fabsf(ze);
                                 ex[b][e] = az > 1.0f;
@@ -584,6 +610,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                                     continue;
                                 }
                             }
+                            if constexpr (SKIP0) {
+                                if (g == 0) {   // skipped first group: zero in the ring; it raises no flag (do_not_flag_first)
+                                    vout[e] = 0.0f;
+                                    continue;
+                                }
+                            }
                             vout[e] = ((dq & bad) == 0) ? (e ? phi[b].y : phi[b].x) : (e ? fb.y : fb.x);
                             const bool first = (g == 0) && a.do_not_flag_first;
                             const uint32_t qg = w[g / 4] >> (8 * (g & 3));
@@ -593,6 +625,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                         if (act) xv = xv * rr.gain;
                         if constexpr (GE > G) {
                             if (2 * p + 1 >= G) xv.y = 0.0f;
+                        }
+                        if constexpr (SKIP0) {
+                            if (p == 0) xv.x = 0.0f;
                         }
                         xs[p * XR * COLS] = col_ok ? xv : f2{0.0f, 0.0f};
                     }
@@ -670,7 +705,8 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
 #pragma unroll
                             for (int b = 0; b < 2 * PBC; ++b) {
                                 const float xc = v[b][0];
-                                O1d[((2 * p0 + b) * 3 + so) * COLS + col] = (double)(xc + xc) - f[b];
+                                // (SKIP0: group 0's iterate is a stored zero, its chain above is dead code)
+                                O1d[((2 * p0 + b) * 3 + so) * COLS + col] = (SKIP0 && 2 * p0 + b == 0) ? 0.0 : (double)(xc + xc) - f[b];
                             }
                         }
                     }
@@ -685,7 +721,11 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                         const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
                         f2 f[1], xc[1];
                         fwd_rows_batch<1, true>(xm, x0, xp, col, kC, vC, f, xc);
-                        O12[(p0 * 3 + so) * COLS + col] = (xc[0] + xc[0]) - f[0];
+                        f2 o1v = (xc[0] + xc[0]) - f[0];
+                        if constexpr (SKIP0) {
+                            if (p0 == 0) o1v.x = 0.0f;   // skipped first group: a stored zero, its half of the arithmetic is dead code
+                        }
+                        O12[(p0 * 3 + so) * COLS + col] = o1v;
                     }
                 } else {
 #pragma unroll
@@ -696,7 +736,11 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                             const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
                             f2 f[1], xc[1];
                             fwd_rows_batch<1, false>(xm, x0, xp, col, kC, vC, f, xc);
-                            O12[(p0 * 3 + so) * COLS + col] = (xc[0] + xc[0]) - f[0];
+                            f2 o1v = (xc[0] + xc[0]) - f[0];
+                            if constexpr (SKIP0) {
+                                if (p0 == 0) o1v.x = 0.0f;
+                            }
+                            O12[(p0 * 3 + so) * COLS + col] = o1v;
                         }
                     }
                 }
@@ -828,7 +872,8 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                     }
                     float qf[GE];
                     if constexpr (GE > G) qf[G] = 0.0f;
-                    c2_div64_shared<G>(o2v, e_gain, act, qf);   // (the dead half takes no part in its range vote)
+                    if constexpr (SKIP0) qf[0] = 0.0f;
+                    c2_div64_shared<G, GE, SKIP0 ? 1 : 0>(o2v, e_gain, act, qf);   // (a dead half takes no part in its range vote)
 #pragma unroll
                     for (int g = 0; g < GE; ++g) {
                         const float xc = (g & 1) ? xnext[g / 2].y : xnext[g / 2].x;
@@ -901,10 +946,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                 }
                 // odd G: whatever the pair arithmetic left in the dead half (0 / gain), the fit sees a zero there
                 if constexpr (GE > G) d[G] = 0.0f, dpair[GP - 1].y = 0.0f;
+                // skipped first group: a zero that nothing below reads -- no weight, no tested difference, no refit term
+                if constexpr (SKIP0) d[0] = 0.0f, dpair[0].x = 0.0f;
                 // first half of the ramp fit (registers only): slope, errors, approximate jump significances
                 const bool unsat = ((qw[(G - 1) / 4] >> (8 * ((G - 1) & 3))) & DQ_SATURATED) == 0;
                 if (!(dbg & 4))
-                    fit_full_pk_a<G, rip_full_valid<G, START>()>(dpair, fc0, v0, kf->a.dense, e_gain, e_read, unsat && act, kf->guard, fs);
+                    fit_full_pk_a<G, rip_full_valid<G, START>(), SKIP0>(dpair, fc0, v0, kf->a.dense, e_gain, e_read, unsat && act, kf->guard, fs);
             }
             CH_T(2)
             C2_SYNC();
@@ -920,9 +967,11 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             uint32_t jmask = 0, pdq = 0;
             // second half of the fit: exact pass where needed, jump mask; then the saturated refits
             auto part_fb = [&]() {
-                if (kg->a.cube_out) {
+                if constexpr (!SKIP0) {   // (the launcher never takes SKIP0 for a call that wants the cube)
+                    if (kg->a.cube_out) {
 #pragma unroll
-                    for (int g = 0; g < G; ++g) kg->a.cube_out[(unsigned)g * npix + pe] = d[g];
+                        for (int g = 0; g < G; ++g) kg->a.cube_out[(unsigned)g * npix + pe] = d[g];
+                    }
                 }
                 uint32_t qor = 0;
 #pragma unroll
@@ -939,8 +988,8 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                         uint32_t qe[G];
 #pragma unroll
                         for (int g = 0; g < G; ++g) qe[g] = (qw[g / 4] >> (8 * (g & 3))) & 0xffu;
-                        trunc_layers<G, G - 1>(d, qe, kg->h, kg->vars, kg->kvals, kg->diffs, e_gain, e_read, act, kg->guard, s, er, ep,
-                                               jmask);
+                        trunc_layers<G, G - 1, GE, SKIP0>(d, qe, kg->h, kg->vars, kg->kvals, kg->diffs, e_gain, e_read, act, kg->guard, s, er,
+                                                          ep, jmask);
                     }
                 }
             };
@@ -1052,7 +1101,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
 #endif
 }
 
-template <int NP, int G, int START, typename KT>
+template <int NP, int G, int START, typename KT, bool SKIP0 = false>
 static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
     using F = C2Form<G + (G & 1), sizeof(KT) == 8>;
     const size_t lds = F::lds_bytes;
@@ -1061,11 +1110,11 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
     const long grid = c2_form_geometry<F>(ag, ctx->ncu, ctx->chain_reserve, ctx->chain_quad, ctx->last_geo);
     static bool lds_set[64] = {};   // per device, once per instantiation (contexts are used from one thread each)
     if (lds > 48 * 1024 && !lds_set[ctx->device & 63]) {
-        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT>),
+        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT, SKIP0>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set[ctx->device & 63] = true;
     }
-    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT>), dim3((unsigned)grid), dim3(F::threads), lds, ctx->stream, ag,
+    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT, SKIP0>), dim3((unsigned)grid), dim3(F::threads), lds, ctx->stream, ag,
                        reinterpret_cast<const RipPlanHeader *>(plan->dev), plan->d_variants, plan->d_k, plan->d_diffs,
                        ctx->guard_band);
     RIP_HIP(ctx, hipGetLastError());
@@ -1075,10 +1124,12 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
 // returns the launch status, or 1 when the plan is not one the specialised kernel was compiled for: the dense table the kernel
 // reads (plan.hip builds it from the plan's differences) must test exactly the differences of the compile-time mask -- for odd G
 // too, where no tested difference may touch the dead half of the last pair
+// skip0: take the form that skips group 0 (the caller has established that it may: rip_chain_may_skip_first, chain.hip)
 template <int NP, int G, typename KT>
-static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
-    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return launch_chain2_s<NP, G, 0, KT>(ctx, plan, a);
-    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>()) return launch_chain2_s<NP, G, 1, KT>(ctx, plan, a);
+static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0) {
+    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return skip0 ? 1 : launch_chain2_s<NP, G, 0, KT>(ctx, plan, a);
+    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>())
+        return skip0 ? launch_chain2_s<NP, G, 1, KT, true>(ctx, plan, a) : launch_chain2_s<NP, G, 1, KT>(ctx, plan, a);
     return 1;
 }
 
@@ -1086,10 +1137,10 @@ static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) 
 // (rip_common.h: RIP_CHAIN_G_PART*); chain.hip calls it for the configurations it lists, chain_np*.hip instantiate it.  Returns
 // the launch status, or 1 when no instantiation fits (the caller then takes the stage kernels).
 template <int NP, typename KT, int PART>
-int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
+int rip_launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0) {
     static_assert(PART >= 0 && PART <= 2, "parts of RIP_CHAIN_G_ALL");
 #define C2_CASE(g) \
-    if (a.ngrp == g) return launch_chain2<NP, g, KT>(ctx, plan, a);
+    if (a.ngrp == g) return launch_chain2<NP, g, KT>(ctx, plan, a, skip0);
     if constexpr (PART == 0) {
         RIP_CHAIN_G_PART0(C2_CASE)
     } else if constexpr (PART == 1) {

@@ -4,4 +4,4 @@
 #ifndef C2_PART
 #error "compiled once per part of the group-count list: -DC2_PART=0, 1, 2 (Makefile)"
 #endif
-template int rip_launch_chain2<4, double, C2_PART>(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a);
+template int rip_launch_chain2<4, double, C2_PART>(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0);

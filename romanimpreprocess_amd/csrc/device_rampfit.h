@@ -253,7 +253,9 @@ __device__ __forceinline__ void finish_pixel(bool active, size_t p, const float 
 // re-evaluated in the reference's exact operation order, so the flags are identical.
 //   d[G]    the pixel's ramp
 //   jmask   bit i set <=> JUMP_DET on group i (OR-ed in)
-template <int G>
+// SKIP0 (the fused kernel's form that skips an excluded first group, chain2_form.h): the term of group 0 is left out of the
+// slope sum.  Its weight is zero, so with a finite d[0] the term is +-0 and (+0) + (+-0) = +0: the sum starts from the same +0.
+template <int G, bool SKIP0 = false>
 __device__ __forceinline__ void fit_full_regs(const float (&d)[G], const RipPlanHeader *__restrict__ h,
                                               const RipVariant v, const float *__restrict__ kv,
                                               const RipDiff *__restrict__ df, float gain, float rn, bool flag,
@@ -262,7 +264,7 @@ __device__ __forceinline__ void fit_full_regs(const float (&d)[G], const RipPlan
     const float d1 = d[1];
     float s = 0.0f;
 #pragma unroll
-    for (int t = 0; t < G; ++t) {
+    for (int t = SKIP0 ? 1 : 0; t < G; ++t) {
         const float diff = d[t] - d1;
         const float prod = KLD(kv[t]) * diff;
         s = s + prod;
@@ -360,12 +362,7 @@ __device__ __forceinline__ void rip_load_pair(RipDensePair &r, const RipDense *d
 // the differences the full-ramp fit tests (fitting.py:225-229) as the bit mask RipDense::valid, at compile time
 template <int G, int START>
 constexpr uint32_t rip_full_valid() {
-    uint32_t m = 0;
-    for (int i = START; i < G - 1; ++i) {
-        const int dimax = (i == G - 2 || G - 1 - START == 2) ? 1 : 2;
-        for (int di = 1; di <= dimax; ++di) m |= 1u << (2 * (2 * (i / 2) + (di - 1)) + (i & 1));
-    }
-    return m;
+    return rip_full_valid_of(G, START);   // (rip_common.h: the host asks the same question before it plans a launch)
 }
 
 // state of the packed full-ramp fit between its two halves (registers; the fused kernel puts a barrier between them)
@@ -388,7 +385,7 @@ struct RipDenseK {
 // first half: slope, errors, threshold, approximate significance of every tested difference
 // VALID != 0: the tested differences are known at compile time (no plan-uniform branches: the eight difference
 // slots become one basic block the scheduler can interleave)
-template <int G, uint32_t VALID, typename TAB>
+template <int G, uint32_t VALID, typename TAB, bool SKIP0 = false>
 __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
                                                 const TAB tabsrc, float gain, float rn, bool flag, double guard,
                                                 RipFitState &st) {
@@ -408,6 +405,13 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
 #pragma unroll
     for (int p = 0; p < GP; ++p) {
         const rf2 diff = dA[p] - d11;
+        if constexpr (SKIP0) {   // a skipped first group has the weight zero and adds nothing: the sum starts at d[1]'s term
+            if (p == 0) {
+                const float prod = k2[1] * diff.y;
+                s = s + prod;
+                continue;
+            }
+        }
         if constexpr (G & 1) {   // the dead half of the last pair has no weight and adds nothing (not even a signed zero)
             if (2 * p + 1 >= G) {
                 const float prod = k2[2 * p] * diff.x;
@@ -500,11 +504,11 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
     st.unsure = unsure_mask;
 }
 
-template <int G, uint32_t VALID = 0u>
+template <int G, uint32_t VALID = 0u, bool SKIP0 = false>
 __device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
                                               const RipDense *__restrict__ dn, float gain, float rn, bool flag,
                                               double guard, RipFitState &st) {
-    fit_full_pk_a_t<G, VALID, RipDenseK>(dA, fc, v, RipDenseK{dn}, gain, rn, flag, guard, st);
+    fit_full_pk_a_t<G, VALID, RipDenseK, SKIP0>(dA, fc, v, RipDenseK{dn}, gain, rn, flag, guard, st);
 }
 
 // second half: exact re-evaluation where the approximate significance was not decisive, jump mask
@@ -572,7 +576,7 @@ __device__ __forceinline__ void fit_full_pk(const rf2 (&dA)[(G + 1) / 2], const 
 // truncation length GV = G-1 ... 3 (d may be longer than G: the fused kernel pads an odd ramp to whole pairs).  A layer is evaluated only when some lane of the wave first saturates at
 // group GV (wave-uniform test); results and jump flags replace the running ones for those lanes, in the
 // reference's order (descending GV).
-template <int G, int GV, int GA>
+template <int G, int GV, int GA, bool SKIP0 = false>
 __device__ __forceinline__ void trunc_layers(const float (&d)[GA], const uint32_t (&qe)[G],
                                              const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars,
                                              const float *__restrict__ kvals, const RipDiff *__restrict__ diffs,
@@ -588,7 +592,7 @@ __device__ __forceinline__ void trunc_layers(const float (&d)[GA], const uint32_
                 const RipVariant v = rip_load_variant(vars, G - GV);
                 float s_, er_, ep_;
                 uint32_t jm = 0;
-                fit_full_regs<GV>(dt, h, v, kvals + v.k_ofs, diffs + v.diff_ofs, gain, rn, act, guard, s_, er_, ep_, jm);
+                fit_full_regs<GV, SKIP0>(dt, h, v, kvals + v.k_ofs, diffs + v.diff_ofs, gain, rn, act, guard, s_, er_, ep_, jm);
                 if (layer) {
                     s = s_;
                     er = er_;
@@ -597,7 +601,7 @@ __device__ __forceinline__ void trunc_layers(const float (&d)[GA], const uint32_
                 }
             }
         }
-        trunc_layers<G, GV - 1>(d, qe, h, vars, kvals, diffs, gain, rn, act, guard, s, er, ep, jmask);
+        trunc_layers<G, GV - 1, GA, SKIP0>(d, qe, h, vars, kvals, diffs, gain, rn, act, guard, s, er, ep, jmask);
     }
 }
 

@@ -234,6 +234,48 @@ int rip_launch_satflag(rip_ctx *ctx, const void *data, int data_dtype, const flo
     return RIP_OK;
 }
 
+// the screen of a CALDIR set at upload (caldir.hip): is every value of an array finite and lo <= |v| <= hi (bit 0 of *bad
+// otherwise), and is any of them infinite (bit 1)?
+template <typename T>
+__global__ __launch_bounds__(256) void screen_kernel(const T *__restrict__ p, size_t n, T lo, T hi, uint32_t *__restrict__ bad) {
+    bool b = false, inf = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const T av = p[i] < (T)0 ? -p[i] : p[i];
+        b = b || !(av >= lo && av <= hi);   // (NaN fails both comparisons)
+        inf = inf || av == (T)INFINITY;
+    }
+    if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+    if (__any(inf) && (threadIdx.x & 63) == 0) atomicOr(bad, 2u);
+}
+__global__ __launch_bounds__(256) void screen_span_kernel(const float *__restrict__ smin, const float *__restrict__ smax, size_t n,
+                                                          uint32_t *__restrict__ bad) {
+    bool b = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float span = smax[i] - smin[i];
+        b = b || !(span != 0.0f) || span != span;
+    }
+    if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+}
+static unsigned screen_grid(size_t n) {
+    const size_t g = (n + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+int rip_launch_screen(rip_ctx *ctx, const void *p, int dtype, size_t n, double lo, double hi, uint32_t *d_bad) {
+    if (!p || !n) return RIP_OK;
+    if (dtype == RIP_F64)
+        hipLaunchKernelGGL(screen_kernel<double>, dim3(screen_grid(n)), dim3(256), 0, ctx->stream, (const double *)p, n, lo, hi, d_bad);
+    else
+        hipLaunchKernelGGL(screen_kernel<float>, dim3(screen_grid(n)), dim3(256), 0, ctx->stream, (const float *)p, n, (float)lo,
+                           (float)hi, d_bad);
+    RIP_HIP(ctx, hipGetLastError());
+    return RIP_OK;
+}
+int rip_launch_screen_span(rip_ctx *ctx, const float *smin, const float *smax, size_t n, uint32_t *d_bad) {
+    hipLaunchKernelGGL(screen_span_kernel, dim3(screen_grid(n)), dim3(256), 0, ctx->stream, smin, smax, n, d_bad);
+    RIP_HIP(ctx, hipGetLastError());
+    return RIP_OK;
+}
+
 // bytes[0 .. n) |= bit (the DO_NOT_USE flag of an excluded first group on the library's device copy of groupdq)
 __global__ __launch_bounds__(256) void or_bytes_kernel(uint32_t *__restrict__ w, size_t n4, uint32_t bits) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

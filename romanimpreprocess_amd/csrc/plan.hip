@@ -7,7 +7,31 @@
 
 #include "rip_host.h"
 
+// weights of fit variant v (0: the full ramp, the caller's K; v > 0: the two-point weights of the ramp truncated to g groups,
+// fitting.py:165-169)
+static std::vector<float> variant_weights(const rip_plan_desc *d, int v, int g, int start) {
+    std::vector<float> K(g, 0.0f);
+    if (v == 0) {
+        for (int i = 0; i < g; ++i) K[i] = d->K[i];
+    } else {
+        K[g - 1] = 1.0f / (d->tbar[g - 1] - d->tbar[start]);
+        K[start] = -K[g - 1];
+    }
+    return K;
+}
+
 extern "C" {
+
+// 1: a plan made from `d` excludes the first group and gives group 0 the weight zero (+-0) in the full-ramp weights and in every
+// truncated variant's -- what the fused kernel's form that skips group 0 rests on (rip_plan_create records the same of the
+// weights it uploads); 0 otherwise.  Host arithmetic only.
+int rip_plan_desc_first_weight_zero(const rip_plan_desc *d) {
+    if (!d || !d->exclude_first || d->ngrp < 3 || d->ngrp > RIP_MAX_GROUPS) return 0;
+    const int G = d->ngrp, nvar = 1 + (G - 4 > 0 ? G - 4 : 0);
+    for (int v = 0; v < nvar; ++v)
+        if (variant_weights(d, v, v == 0 ? G : G - v, 1)[0] != 0.0f) return 0;
+    return 1;
+}
 
 int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
     if (!d || !plan_id) return rip_fail(ctx, RIP_EINVAL, "plan: NULL argument");
@@ -41,13 +65,7 @@ int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
         rv.coef = d->variant_coef[v];
         rv.rfac = d->variant_rfac[v];
         rv.k_ofs = (int)p->kvals.size();
-        std::vector<float> K(g, 0.0f);
-        if (v == 0) {
-            for (int i = 0; i < g; ++i) K[i] = d->K[i];
-        } else {  // fitting.py:165-169
-            K[g - 1] = 1.0f / (d->tbar[g - 1] - d->tbar[start]);
-            K[start] = -K[g - 1];
-        }
+        const std::vector<float> K = variant_weights(d, v, g, start);
         p->kvals.insert(p->kvals.end(), K.begin(), K.end());
         rv.diff_ofs = (int)p->diffs.size();
         rv.ndiff = 0;
@@ -124,6 +142,9 @@ int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
                 if (!used) dn.pairs[ps].A[e] = 1.0f;  // keeps the approximate variance positive for unused slots
             }
     }
+    // group 0's weight in every variant: the one question, asked of the description the weights above were made from
+    // (variant_weights serves both)
+    p->k0_zero = rip_plan_desc_first_weight_zero(d) == 1;
     std::vector<char> img(p->bytes, 0);
     memcpy(img.data(), &h, sizeof h);
     memcpy(img.data() + o_var, p->variants.data(), p->variants.size() * sizeof(RipVariant));

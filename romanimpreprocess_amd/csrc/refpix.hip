@@ -51,9 +51,9 @@ __device__ float block_median_sorted(float *vals, int n, int npow2) {
 // bitonic network of cross-lane exchanges; rank 63 ends in (lane 63, slot 0), rank 64 in (lane 0, slot 1)
 __global__ __launch_bounds__(256) void amp33_rows_kernel(const uint16_t *__restrict__ amp33,
                                                          const float *__restrict__ med, float *__restrict__ lohi,
-                                                         int ny, int nrows_total) {
+                                                         int ny, int row_first, int nrows_total) {
     const int lane = threadIdx.x & 63;
-    const int row_id = blockIdx.x * 4 + (threadIdx.x >> 6);  // flattened (g, r)
+    const int row_id = row_first + blockIdx.x * 4 + (threadIdx.x >> 6);  // flattened (g, r), from the first group whose tables are made
     if (row_id >= nrows_total) return;
     const int r = row_id % ny;
     const uint16_t *a = amp33 + (size_t)row_id * RIP_CW;
@@ -90,9 +90,9 @@ struct SelState {
 
 __global__ __launch_bounds__(256) void sel_hist_kernel(const uint16_t *__restrict__ amp33, const float *__restrict__ med,
                                                        const SelState *__restrict__ st, uint32_t *__restrict__ ghist,
-                                                       int ny, int level, int chunk) {
+                                                       int ny, int level, int chunk, int g0) {
     __shared__ uint32_t h[2][SEL_BINS];
-    const int g = blockIdx.y;
+    const int g = g0 + blockIdx.y;
     for (int i = threadIdx.x; i < 2 * SEL_BINS; i += blockDim.x) (&h[0][0])[i] = 0;
     __syncthreads();
     const size_t n = (size_t)ny * RIP_CW;
@@ -117,10 +117,11 @@ __global__ __launch_bounds__(256) void sel_hist_kernel(const uint16_t *__restric
     }
 }
 
-__global__ __launch_bounds__(256) void sel_scan_kernel(SelState *__restrict__ st, uint32_t *__restrict__ ghist, int level, uint32_t n) {
+__global__ __launch_bounds__(256) void sel_scan_kernel(SelState *__restrict__ st, uint32_t *__restrict__ ghist, int level, uint32_t n,
+                                                       int g0) {
     // bin holding the wanted rank: 8 bins per thread
     __shared__ uint32_t part[4];
-    const int g = blockIdx.x, t = blockIdx.y;
+    const int g = g0 + blockIdx.x, t = blockIdx.y;
     uint32_t *h = ghist + ((size_t)g * 2 + t) * SEL_BINS;
     const int per = SEL_BINS / 256;
     const int tid = threadIdx.x;
@@ -173,9 +174,9 @@ __device__ float block_median_select(const float *vals, int n, uint32_t (*h)[SEL
 // ---- 3. per group: global median M, row medians, ctr, rowcorr ------------------------------------
 __global__ __launch_bounds__(1024) void rowcorr_kernel(const SelState *__restrict__ st, const float *__restrict__ lohi,
                                                        double slope, double *__restrict__ rowcorr,
-                                                       double *__restrict__ rowcorr_t, int ny) {
+                                                       double *__restrict__ rowcorr_t, int ny, int G, int g0) {
     extern __shared__ float rm[];  // [ny] row medians
-    const int g = blockIdx.x;
+    const int g = g0 + blockIdx.x;
     const float M = key_median(st[g].prefix[0], st[g].prefix[1]);  // np.median of the block
     auto refmed = [&](int r) {
         const float a = lohi[((size_t)g * ny + r) * 2] - M;
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(1024) void rowcorr_kernel(const SelState *__restric
     for (int r = threadIdx.x; r < ny; r += blockDim.x) {
         const double v = row_corr(slope, refmed(r), ctr);
         rowcorr[(size_t)g * ny + r] = v;
-        if (rowcorr_t) rowcorr_t[(size_t)r * gridDim.x + g] = v;  // [row][group]: one scalar load per row
+        if (rowcorr_t) rowcorr_t[(size_t)r * G + g] = v;  // [row][group]: one scalar load per row
     }
 }
 
@@ -199,9 +200,9 @@ template <typename DT>
 __global__ __launch_bounds__(1024) void chan_kernel(const DT *__restrict__ data, const float *__restrict__ dark,
                                                     const double *__restrict__ rowcorr,
                                                     const double *__restrict__ lines_override,
-                                                    double *__restrict__ lines, int ny, int nx) {
+                                                    double *__restrict__ lines, int ny, int nx, int g0) {
     __shared__ float v[1024];
-    const int ch = blockIdx.x, g = blockIdx.y, nch = gridDim.x;
+    const int ch = blockIdx.x, g = g0 + blockIdx.y, nch = gridDim.x;
     const int e = threadIdx.x & 511, half = threadIdx.x >> 9;
     const int row = (half ? ny - 4 : 0) + e / RIP_CW;
     const size_t idx = ((size_t)g * ny + row) * nx + (size_t)ch * RIP_CW + e % RIP_CW;
@@ -253,6 +254,10 @@ int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a, int form) {
     if (a.nx % RIP_CW) return rip_fail(ctx, RIP_EINVAL, "refpix: nx=%d is not a multiple of 128", a.nx);
     if (a.ny < 8) return rip_fail(ctx, RIP_EINVAL, "refpix: ny=%d too small", a.ny);
     const int G = a.ngrp, ny = a.ny, nch = a.nx / RIP_CW;
+    // tables of groups g0 .. G-1 only (g0 = 1 in front of a fused kernel that skips group 0): every kernel below works group by
+    // group, so the launches simply cover G - g0 groups from g0 on; the entries of the groups before g0 stay unwritten
+    const int g0 = a.g0;
+    if (g0 < 0 || g0 >= G) return rip_fail(ctx, RIP_EINVAL, "refpix: first group %d of %d", g0, G);
     hipStream_t strm = a.stream ? a.stream : ctx->stream;   // (the overlapped pre-pass: the context's second stream)
     if (form == 1) return rip_launch_refpix_one(ctx, a);
     if (a.amp33) {
@@ -271,30 +276,30 @@ int rip_launch_refpix_prepass(rip_ctx *ctx, const RefpixArgs &a, int form) {
         if (!ghist) return RIP_ENOMEM;
         if ((const void *)ghist != had) RIP_HIP(ctx, hipMemsetAsync(ghist, 0, gh_b, strm));
         const uint32_t n = (uint32_t)ny * RIP_CW;
-        hipLaunchKernelGGL(amp33_rows_kernel, dim3((unsigned)((G * ny + 3) / 4)), dim3(256), 0, strm, a.amp33,
-                           a.amp33_med, lohi, ny, G * ny);
+        hipLaunchKernelGGL(amp33_rows_kernel, dim3((unsigned)(((G - g0) * ny + 3) / 4)), dim3(256), 0, strm, a.amp33,
+                           a.amp33_med, lohi, ny, g0 * ny, G * ny);
         const int chunk = 8192;
         const unsigned nblk = (unsigned)((n + chunk - 1) / chunk);
         for (int level = 0; level < 3; ++level) {
-            hipLaunchKernelGGL(sel_hist_kernel, dim3(nblk, G), dim3(256), 0, strm, a.amp33, a.amp33_med, st,
-                               ghist, ny, level, chunk);
-            hipLaunchKernelGGL(sel_scan_kernel, dim3(G, 2), dim3(256), 0, strm, st, ghist, level, n);
+            hipLaunchKernelGGL(sel_hist_kernel, dim3(nblk, G - g0), dim3(256), 0, strm, a.amp33, a.amp33_med, st,
+                               ghist, ny, level, chunk, g0);
+            hipLaunchKernelGGL(sel_scan_kernel, dim3(G - g0, 2), dim3(256), 0, strm, st, ghist, level, n, g0);
         }
         const size_t lds = (size_t)ny * sizeof(float);
         int rc;
         if ((rc = with_lds(ctx, rowcorr_kernel, lds))) return rc;
-        hipLaunchKernelGGL(rowcorr_kernel, dim3(G), dim3(1024), lds, strm, st, lohi, a.slope, a.rowcorr, a.rowcorr_t, ny);
+        hipLaunchKernelGGL(rowcorr_kernel, dim3(G - g0), dim3(1024), lds, strm, st, lohi, a.slope, a.rowcorr, a.rowcorr_t, ny, G, g0);
     } else {
         // no reference output in the read file: the row step is the identity
         RIP_HIP(ctx, hipMemsetAsync(a.rowcorr, 0, (size_t)G * ny * sizeof(double), strm));
         if (a.rowcorr_t) RIP_HIP(ctx, hipMemsetAsync(a.rowcorr_t, 0, (size_t)G * ny * sizeof(double), strm));
     }
     if (a.data_dtype == RIP_U16)
-        hipLaunchKernelGGL(chan_kernel<uint16_t>, dim3(nch, G), dim3(1024), 0, strm, (const uint16_t *)a.data,
-                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx);
+        hipLaunchKernelGGL(chan_kernel<uint16_t>, dim3(nch, G - g0), dim3(1024), 0, strm, (const uint16_t *)a.data,
+                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx, g0);
     else
-        hipLaunchKernelGGL(chan_kernel<float>, dim3(nch, G), dim3(1024), 0, strm, (const float *)a.data,
-                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx);
+        hipLaunchKernelGGL(chan_kernel<float>, dim3(nch, G - g0), dim3(1024), 0, strm, (const float *)a.data,
+                           a.dark_data, a.rowcorr, a.lines_override, a.lines, ny, a.nx, g0);
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;
 }

@@ -17,7 +17,10 @@
 // phases of one group (= one resultant of the ramp) are separated by barriers among the workgroups of THAT group only; groups are
 // independent.  Workgroups are numbered group-major, and a workgroup only ever waits for workgroups of its own group, all of
 // which precede every later group's in each XCD's dispatch queue -- so a partially resident grid (a busy or shared device) cannot
-// deadlock: the lowest unfinished group always becomes resident.
+// deadlock: the lowest unfinished group always becomes resident.  A launch that starts at a later group (RefpixArgs::g0 = 1 in
+// front of a fused kernel that skips group 0) keeps all of this: the numbering stays group-major over the groups g0 .. G-1, a
+// workgroup still waits for workgroups of its own group only, on that group's own counters and histograms, and group 0's are
+// never touched.
 //
 //   phase A   every workgroup: 128 rows of the reference output of its group; a wave sorts a row's 128 values (two registers
 //             per lane, bitonic network on order-preserving integer keys: DPP / swizzle lane exchanges + v_med3_u32) -> the row's
@@ -76,6 +79,7 @@ struct R1Args {
     unsigned long long *stamps;   // diagnostic (tools/gpu_checks/prepass_stamps.py): 16 clock stamps per workgroup, or null
     double slope;
     int ny, nx, G, B;
+    int g0;   // first group whose tables are made: the grid covers groups g0 .. G-1
 };
 
 __device__ __forceinline__ uint32_t ld_sc1(const uint32_t *p) {
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(R1_THREADS) void refpix_one_kernel(R1Args a) {
     __shared__ double rc8[8];
     __shared__ uint32_t flag_s;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int g = (int)blockIdx.x / a.B, b = (int)blockIdx.x % a.B;
+    const int g = a.g0 + (int)blockIdx.x / a.B, b = (int)blockIdx.x % a.B;
     const int ny = a.ny, nx = a.nx, nch = nx / RIP_CW;
     R1Ctrl *ctrl = a.ctrl + g;
     uint32_t *gh = a.ghist + (size_t)g * 3 * 2 * SEL_BINS;
@@ -552,6 +556,7 @@ int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a) {
     if (!rip_refpix_one_supported(a)) return rip_fail(ctx, RIP_EINVAL, "refpix: frame not covered by the single-launch pre-pass");
     const int G = a.ngrp, ny = a.ny, nch = a.nx / RIP_CW;
     const int B = (ny + R1_ROWS - 1) / R1_ROWS;
+    if (a.g0 < 0 || a.g0 >= G) return rip_fail(ctx, RIP_EINVAL, "refpix: first group %d of %d", a.g0, G);
     const void *had = ctx->ws[RIP_WS_R1_ZERO];
     char *z = (char *)rip_ws(ctx, RIP_WS_R1_ZERO, R1_ZERO_BYTES);
     if (!z) return RIP_ENOMEM;
@@ -581,11 +586,12 @@ int rip_launch_refpix_one(rip_ctx *ctx, const RefpixArgs &a) {
     r.nx = a.nx;
     r.G = G;
     r.B = B;
+    r.g0 = a.g0;
     r.stamps = (unsigned long long *)ctx->prepass_stamps;
     if (a.data_dtype == RIP_U16)
-        hipLaunchKernelGGL(refpix_one_kernel<uint16_t>, dim3((unsigned)(G * B)), dim3(R1_THREADS), 0, st, r);
+        hipLaunchKernelGGL(refpix_one_kernel<uint16_t>, dim3((unsigned)((G - a.g0) * B)), dim3(R1_THREADS), 0, st, r);
     else
-        hipLaunchKernelGGL(refpix_one_kernel<float>, dim3((unsigned)(G * B)), dim3(R1_THREADS), 0, st, r);
+        hipLaunchKernelGGL(refpix_one_kernel<float>, dim3((unsigned)((G - a.g0) * B)), dim3(R1_THREADS), 0, st, r);
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;
 }

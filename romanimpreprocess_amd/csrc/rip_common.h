@@ -64,6 +64,16 @@ struct RipDense {
     RipDensePair pairs[RIP_MAX_GROUPS];
 };
 
+// the differences the full-ramp fit of G groups tests from group `start` on (fitting.py:225-229), as the bit mask RipDense::valid
+constexpr uint32_t rip_full_valid_of(int G, int start) {
+    uint32_t m = 0;
+    for (int i = start; i < G - 1; ++i) {
+        const int dimax = (i == G - 2 || G - 1 - start == 2) ? 1 : 2;
+        for (int di = 1; di <= dimax; ++di) m |= 1u << (2 * (2 * (i / 2) + (di - 1)) + (i & 1));
+    }
+    return m;
+}
+
 // layout of the device plan buffer: header | variants[nvariants] | K floats | diffs | dense
 struct RipPlan {
     RipPlanHeader h;
@@ -77,6 +87,9 @@ struct RipPlan {
     const RipDense *d_dense = nullptr;
     RipDense dense;
     size_t bytes = 0;
+    // group 0 has the weight zero (+-0) in the full-ramp weights and in every truncated variant's: with an excluded first group
+    // the slope then does not depend on a FINITE d[0] (the fused kernel's form that skips group 0, chain2_form.h)
+    bool k0_zero = false;
 };
 
 // ---------------------------------------------------------------- device-resident CALDIR of one SCA
@@ -114,6 +127,14 @@ struct RipCal {
     // or -1 where merging would change the linearity test (an added word carries NO_LIN_CORR / REFERENCE_PIXEL: never seen in a
     // reference-written file; the dispatcher then takes another kernel form)
     int merged_plane[4] = {3, -1, -1, -1};
+    // every array that reaches group 0 of the fused chain is finite and within the bounds of the screen at upload (caldir.hip):
+    // d[0] of every pixel is then finite whatever the ramp's u16 data (rip_caldir_first_group_safe)
+    bool first_group_safe = false;
+    // one of those arrays holds an INFINITE value.  The fused kernel's shared-reciprocal divisions (div_rcp2: chain_common.h) are
+    // the division operator's bits for finite numerators; an infinite one gives them NaN where IEEE division gives an infinity
+    // (which the clip of an excluded first group then turns into +-1: the reference's finite result).  Such a set -- never
+    // seen in a written file -- takes the stage kernels, which divide with the operator.
+    bool has_inf = false;
     size_t bytes = 0;
 };
 
@@ -176,6 +197,7 @@ struct rip_ctx {   // host-only: no kernel reads it
     bool use_chain2 = true;  // wave-specialised fused kernel where it applies
     double guard_band = 1e-5;  // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
     bool chain_quad = true;     // a last strip of <= 64 live columns in quad mode (chain2_geometry); false: every strip alike (A/B timing)
+    bool skip_first = true;     // the fused kernel's form that skips an excluded first group, where it applies (option "skip_first")
     int chain_reserve = 8;      // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
     // reference-pixel tables: -1 = by situation (a pre-pass that overlaps the previous ramp's fused kernel: the nine small launches
     // of refpix.hip, which slip into that kernel's tail; a pre-pass in front of its own ramp on the same stream: the single launch
@@ -184,6 +206,7 @@ struct rip_ctx {   // host-only: no kernel reads it
 
     // ---- diagnostics and profiling
     int last_form = 0;       // diagnostic: how the last rip_calibrate ran (0 stage kernels, 2 the fused kernel; 1 and 3 were the general and the wave-private fused kernels of rounds 1-2)
+    int last_first_group = 0;   // diagnostic: 1 = the last fused launch skipped group 0 (rip_last_chain_first_group)
     int last_geo[8] = {};    // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
     int chain_dbg = 0;       // timing experiments only (option "chain_dbg"): the fused kernel skips phases, results invalid
     unsigned long long *chain_dbg_buf = nullptr;  // 4096 waves x 6 phases (diagnostic builds)
@@ -321,7 +344,12 @@ struct ChainArgs {
 #define RIP_CHAIN_G_ALL(X) RIP_CHAIN_G_PART0(X) RIP_CHAIN_G_PART1(X) RIP_CHAIN_G_PART2(X)
 bool rip_chain_supported(const rip_ctx *ctx, int nplanes, int G, int k_dtype, int gain_dtype);
 bool rip_chain_fills_lds(int G, int k_dtype);   // the pre-pass of the next ramp cannot run beside the fused kernel
-int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype);
+// skip0: the form that neither loads nor evaluates group 0; only where rip_chain_may_skip_first said so for this call
+int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int nplanes, int k_dtype, bool skip0 = false);
+// Will rip_launch_chain run the fused kernel for such a call (and not return 1), and may that kernel skip group 0?  The
+// properties of the PLAN and of the launch only; the caller adds those of the CALDIR set and of the ramp (calibrate.hip).
+bool rip_chain_may_skip_first(const rip_ctx *ctx, const RipPlan *plan, int nplanes, int G, int k_dtype, int gain_dtype, int merged_dq,
+                              int nb);
 
 // ipc.hip
 struct IpcArgs {
@@ -352,6 +380,7 @@ struct RefpixArgs {
     int ny, nx, ngrp;
     int background = 0;   // 1: launched beside the previous ramp's fused kernel (second stream)
     hipStream_t stream = nullptr;   // where the launches go (null: the context's main stream)
+    int g0 = 0;   // first group whose tables are made (1: the fused kernel that follows skips group 0; its entries stay unwritten)
 };
 // the form that makes a call's tables (1: refpix_one.hip, 0: refpix.hip) from option = rip_ctx::prepass_form or a stage call's
 int rip_refpix_form(int option, const RefpixArgs &a);
@@ -375,6 +404,10 @@ int rip_launch_flat_area(rip_ctx *ctx, const float *flat_dn, const double *area,
 int rip_launch_merge_dq(rip_ctx *ctx, const uint32_t *lin_dq, const uint32_t *flat_flags, const uint32_t *dark_dq, uint32_t *out, int ny,
                         int nx, int nb, uint32_t *d_clash);
 int rip_launch_or_bytes(rip_ctx *ctx, uint8_t *bytes, size_t n, uint8_t bit, hipStream_t stream = nullptr);
+// *d_bad |= 1 unless lo <= |p[i]| <= hi for every i < n (NaN fails), |= 2 where some p[i] is infinite; p of RIP_F32 / RIP_F64 elements
+int rip_launch_screen(rip_ctx *ctx, const void *p, int dtype, size_t n, double lo, double hi, uint32_t *d_bad);
+// *d_bad |= 1 unless f32(smax[i] - smin[i]) is non-zero and not NaN for every i < n
+int rip_launch_screen_span(rip_ctx *ctx, const float *smin, const float *smax, size_t n, uint32_t *d_bad);
 // dq-init + saturation flagging (misc.hip): gdq_in / pdq_in may be null (= zeros)
 int rip_launch_satflag(rip_ctx *ctx, const void *data, int data_dtype, const float *thr, const uint32_t *sat_dq,
                        const uint8_t *gdq_in, const uint32_t *pdq_in, uint8_t *gdq_out, uint32_t *pdq_out, int G, int ny,
