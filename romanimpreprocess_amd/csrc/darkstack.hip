@@ -8,6 +8,7 @@
 // The stack (groups x exposures x ny x nx f32, 13 GB for 100 darks of the production table) lives in HBM and never moves: the
 // array arguments take a location (RIP_HOST: staged through a scoped device buffer; RIP_DEVICE: used where they are).
 #include "rip_host.h"
+#include "rip_select.h"
 
 namespace {
 
@@ -73,12 +74,6 @@ __global__ __launch_bounds__(256) void group_means_kernel(const uint16_t *__rest
 }
 
 // ------------------------------------------------------------------------------------------ clipped mean over the planes
-__device__ __forceinline__ uint32_t ds_f2key(float v) {   // monotone: key(a) < key(b) <=> a < b, with -0 just below +0
-    const uint32_t b = __float_as_uint(v);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ds_key2f(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
 #define DS_KEY_MIN 0x00800000u   // key(-FLT_MAX): -inf and the NaNs with the sign bit lie below
 #define DS_KEY_MAX 0xFF7FFFFFu   // key(+FLT_MAX): +inf and the other NaNs lie above
 
@@ -86,24 +81,24 @@ __device__ __forceinline__ float ds_key2f(uint32_t k) { return __uint_as_float(k
 // keys, so the neighbour of a float is its key +- 1; the two zeros compare equal and go together.
 __device__ __forceinline__ uint32_t ds_lo_key(double lo) {
     const float f = (float)lo;
-    uint32_t k = ds_f2key(f);
+    uint32_t k = f2key(f);
     if ((double)f < lo) k += 1;
-    return ds_key2f(k) == 0.0f ? 0x7FFFFFFFu : k;
+    return key2f(k) == 0.0f ? 0x7FFFFFFFu : k;
 }
 __device__ __forceinline__ uint32_t ds_hi_key(double hi) {
     const float f = (float)hi;
-    uint32_t k = ds_f2key(f);
+    uint32_t k = f2key(f);
     if ((double)f > hi) k -= 1;
-    return ds_key2f(k) == 0.0f ? 0x80000000u : k;
+    return key2f(k) == 0.0f ? 0x80000000u : k;
 }
 
-// One workgroup of four waves per 64 pixels, the shape of stats.hip's seed_median_kernel: the column of n keys of pixel `lane`
-// sits in LDS as tile[s*64 + lane] (conflict-free), wave w works on the planes s = w (mod 4) -- keys it stored itself -- and the
-// four partial results meet in xch; every wave then takes the same decisions for its 64 pixels.
+// One workgroup of four waves per 64 pixels, the column layout of rip_select.h: the column of n keys of pixel `lane` sits in
+// LDS as tile[s*64 + lane], wave w works on the planes s = w (mod 4) -- keys it stored itself -- and the four partial results
+// meet in xch (ColMeet); every wave then takes the same decisions for its 64 pixels.
 // The survivors of every round are a contiguous range of the sorted column, so the clip is a pair of KEY bounds [klo, khi]
 // (a value is removed when (double)x < lo or (double)x > hi, strictly: ds_lo_key / ds_hi_key); the non-finite values are outside
 // the first pair.  Per round: count and f64 sum -> mean m; f64 sum of (x - m)^2 -> s = sqrt(. / count); median c by radix
-// selection among the survivors, two bits a pass; new bounds c - slo*s, c + shi*s.  A pixel stops when a round removed nothing
+// selection among the survivors (col_select); new bounds c - slo*s, c + shi*s.  A pixel stops when a round removed nothing
 // (its bounds freeze); the workgroup leaves the loop when all 64 have stopped, which every wave finds by itself.  The partial
 // sums are added in the order of the waves: a fixed order.  The result is the f64 sum of the survivors in PLANE order (wave 0
 // walks the column once), divided by the count and rounded once to f32.  All loops are bounded by n, DS_MAX_ITERS and 32 bits.
@@ -116,15 +111,9 @@ __global__ __launch_bounds__(256) void sigma_clip_kernel(const float *__restrict
     const size_t p = (size_t)blockIdx.x * 64 + lane;
     const bool live = p < npix;
     const size_t pp = live ? p : npix - 1;
-    for (int s = w; s < n; s += 4) tile[s * 64 + lane] = ds_f2key(stack[(size_t)s * plane_stride + pp]);
-    int buf = 0;
-    // every wave leaves with the sum over the four waves, added in wave order
-    auto meet = [&](uint4 mine, auto &&add) {
-        xch[buf][w][lane] = mine;
-        __syncthreads();
-        for (int q = 0; q < 4; ++q) add(xch[buf][q][lane]);
-        buf ^= 1;   // the other buffer is free: every wave has passed the barrier after reading it
-    };
+    for (int s = w; s < n; s += 4) tile[s * 64 + lane] = f2key(stack[(size_t)s * plane_stride + pp]);
+    auto key = [&](int s) -> uint32_t { return tile[s * 64 + lane]; };
+    ColMeet meet{xch, w, lane, 0};
     uint32_t klo = DS_KEY_MIN, khi = DS_KEY_MAX;
     int cnt = 0, cnt_prev = -1;
     for (int it = 0; it <= DS_MAX_ITERS; ++it) {
@@ -136,7 +125,7 @@ __global__ __launch_bounds__(256) void sigma_clip_kernel(const float *__restrict
             const uint32_t e = tile[s * 64 + lane];
             if (e >= klo && e <= khi) {
                 c += 1;
-                sum = sum + (double)ds_key2f(e);
+                sum = sum + (double)key2f(e);
             }
         }
         {
@@ -159,7 +148,7 @@ __global__ __launch_bounds__(256) void sigma_clip_kernel(const float *__restrict
         for (int s = w; s < n; s += 4) {
             const uint32_t e = tile[s * 64 + lane];
             if (e >= klo && e <= khi) {
-                const double d = (double)ds_key2f(e) - m;
+                const double d = (double)key2f(e) - m;
                 ssq = ssq + d * d;
             }
         }
@@ -170,54 +159,12 @@ __global__ __launch_bounds__(256) void sigma_clip_kernel(const float *__restrict
             ssq = st;
         }
         const double sd = sqrt(ssq / (double)cnt);
-        // median: the key of rank (cnt-1)/2 among the survivors
-        int k = (cnt - 1) / 2;
-        uint32_t prefix = 0;
-        for (int sh = 30; sh >= 0; sh -= 2) {
-            const uint32_t hi = sh == 30 ? 0u : (0xFFFFFFFFu << (sh + 2));
-            uint32_t c0 = 0, c1 = 0, c2 = 0;
-#pragma unroll 8
-            for (int s = w; s < n; s += 4) {
-                const uint32_t e = tile[s * 64 + lane];
-                const bool in = e >= klo && e <= khi && (e & hi) == prefix;
-                const uint32_t d = (e >> sh) & 3u;
-                c0 += (in && d == 0) ? 1 : 0;
-                c1 += (in && d <= 1) ? 1 : 0;
-                c2 += (in && d <= 2) ? 1 : 0;
-            }
-            uint32_t t0 = 0, t1 = 0, t2 = 0;
-            meet(make_uint4(c0, c1, c2, 0u), [&](const uint4 &v) {
-                t0 += v.x;
-                t1 += v.y;
-                t2 += v.z;
-            });
-            uint32_t d;
-            if (k < (int)t0) d = 0;
-            else if (k < (int)t1) { d = 1; k -= t0; }
-            else if (k < (int)t2) { d = 2; k -= t1; }
-            else { d = 3; k -= t2; }
-            prefix |= d << sh;
-        }
-        // an even count: the other middle value is the median's key again (ties) or the next survivor above it
-        uint32_t le = 0, nxt = 0xFFFFFFFFu;
-#pragma unroll 8
-        for (int s = w; s < n; s += 4) {
-            const uint32_t e = tile[s * 64 + lane];
-            const bool in = e >= klo && e <= khi;
-            le += (in && e <= prefix) ? 1 : 0;
-            if (in && e > prefix && e < nxt) nxt = e;
-        }
-        {
-            uint32_t lt = 0, nt = 0xFFFFFFFFu;
-            meet(make_uint4(le, nxt, 0u, 0u), [&](const uint4 &v) {
-                lt += v.x;
-                nt = min(nt, v.y);
-            });
-            le = lt;
-            nxt = nt;
-        }
-        double cen = (double)ds_key2f(prefix);
-        if ((cnt & 1) == 0) cen = 0.5 * (cen + (double)ds_key2f((int)le >= cnt / 2 + 1 ? prefix : nxt));
+        // median of the survivors; for an even count the mean of the two middle values
+        auto in = [&](uint32_t e) { return e >= klo && e <= khi; };
+        const uint32_t mid = col_select(n, w, (cnt - 1) / 2, key, in, meet);
+        const uint32_t upper = col_select_upper(n, w, cnt, mid, key, in, meet);
+        double cen = (double)key2f(mid);
+        if ((cnt & 1) == 0) cen = 0.5 * (cen + (double)key2f(upper));
         if (!done) {
             klo = max(klo, ds_lo_key(cen - slo * sd));
             khi = min(khi, ds_hi_key(cen + shi * sd));
@@ -227,7 +174,7 @@ __global__ __launch_bounds__(256) void sigma_clip_kernel(const float *__restrict
     double sum = 0.0;
     for (int s = 0; s < n; ++s) {
         const uint32_t e = tile[s * 64 + lane];
-        if (e >= klo && e <= khi) sum = sum + (double)ds_key2f(e);
+        if (e >= klo && e <= khi) sum = sum + (double)key2f(e);
     }
     if (live) {
         mean[p] = cnt > 0 ? (float)(sum / (double)cnt) : __uint_as_float(0x7FC00000u);
@@ -350,8 +297,7 @@ int rip_cal_sigma_clip_mean(rip_ctx *ctx, const float *stack, int location, int 
         (rc = ds_out(dc, count, npix, location, c)))
         return rc;
     const size_t bytes = (size_t)n * 64 * sizeof(uint32_t);
-    if (bytes > 48 * 1024)
-        RIP_HIP(ctx, hipFuncSetAttribute((const void *)sigma_clip_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if ((rc = with_lds(ctx, sigma_clip_kernel, bytes))) return rc;
     hipLaunchKernelGGL(sigma_clip_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), bytes, ctx->stream, s, n, plane_stride, npix,
                        sigma_lower, sigma_upper, maxiters, m, c);
     RIP_HIP(ctx, hipGetLastError());

@@ -8,34 +8,10 @@
 // Border pixels (reference pixels) pass through unchanged.  Arrays in and out are host arrays or device pointers, out == cube
 // (in place) included: rip_host.h.  Exact given the normals.
 #include "rip_host.h"
+#include "rip_rng.h"
 #include <cstring>
 
 namespace {
-
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-}
-__device__ __forceinline__ void philox4x32(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-// one standard normal for (seed, layer, group, pixel): Box-Muller on two uniforms of the Philox block
-__device__ __forceinline__ float device_normal(uint64_t seed, uint32_t layer, uint32_t group, uint32_t pix) {
-    uint32_t c[4] = {pix, group, layer, 0x6e6f6973u};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
-    const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
 
 __global__ __launch_bounds__(256) void noise_inject_kernel(const uint16_t *__restrict__ cube, const float *__restrict__ normals,
                                                            const float *__restrict__ read, const double *__restrict__ rsqn,
@@ -51,7 +27,7 @@ __global__ __launch_bounds__(256) void noise_inject_kernel(const uint16_t *__res
     }
     const int nxa = nx - 2 * nb, nya = ny - 2 * nb;
     const size_t ia = ((size_t)k * nya + (y - nb)) * nxa + (x - nb);
-    const float nrm = normals ? normals[ia] : device_normal(seed, layer, (uint32_t)k, (uint32_t)((y - nb) * nxa + (x - nb)));
+    const float nrm = normals ? normals[ia] : riprng::normal_f32(seed, (uint32_t)((y - nb) * nxa + (x - nb)), (uint32_t)k, layer, 0x6e6f6973u);
     const float im = (float)((double)nrm * ((double)read[(size_t)y * nx + x] / rsqn[k]));
     float r = __fadd_rn((float)v, im);
     r = r < 0.0f ? 0.0f : (r > 65535.0f ? 65535.0f : r);   // np.clip keeps NaN; the cast of NaN is not defined in numpy either
@@ -99,17 +75,12 @@ extern "C" int rip_stage_noise_inject(rip_ctx *ctx, const uint16_t *cube, int ng
 // layer, read, pixel, attempt).  Everything but the deviates is exact.  Host arrays or device pointers, like the injection above.
 namespace {
 
-__device__ __forceinline__ float philox_uniform(uint64_t seed, uint32_t a, uint32_t b, uint32_t c_, uint32_t d, int which) {
-    uint32_t c[4] = {a, b, c_, d};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    return ((float)(c[which] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-}
-
+// Not riprng::poisson_ptrs: this recipe (48-bit uniform, attempt shift 16, lgamma test) gives other deviates; merging is a behaviour change.
 __device__ double device_poisson(double lam, uint64_t seed, uint32_t layer, uint32_t isamp, uint32_t pix) {
     if (!(lam > 0.0)) return 0.0;
     if (lam < 10.0) {   // inversion: sequential search of the cumulative distribution with one uniform (two words: 48 bits)
         uint32_t c[4] = {pix, isamp, layer, 0x706f6973u};
-        philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        riprng::philox(c, seed);
         const double u = ((double)(((uint64_t)c[0] << 16) | (c[1] >> 16)) + 0.5) * (1.0 / 281474976710656.0);
         double p = exp(-lam), cdf = p;
         int k = 0;
@@ -125,7 +96,7 @@ __device__ double device_poisson(double lam, uint64_t seed, uint32_t layer, uint
     const double b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b, inv_alpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
     for (uint32_t attempt = 0; attempt < 64; ++attempt) {
         uint32_t c[4] = {pix, isamp, layer ^ (attempt << 16), 0x70747273u};
-        philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        riprng::philox(c, seed);
         const double u = ((double)c[0] + 0.5) * (1.0 / 4294967296.0) - 0.5;
         const double v = ((double)c[1] + 0.5) * (1.0 / 4294967296.0);
         const double us = 0.5 - fabs(u);

@@ -18,17 +18,9 @@
 // the reference's second sampler for low acceptance is not needed); the normalisation needs Re lgamma(m + i nu/2), evaluated
 // by the recurrence + Stirling series.
 #include "rip_host.h"
+#include "rip_rng.h"
 
 namespace {
-
-__device__ __forceinline__ void px_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-    c[1] = (uint32_t)p1;
-    c[3] = (uint32_t)p0;
-    c[0] = n0;
-    c[2] = n2;
-}
 
 // a stream of uniforms in (0, 1) with 52 random bits each, for one element: counter = (element, stream, block index)
 struct PxRng {
@@ -39,12 +31,7 @@ struct PxRng {
     __device__ PxRng(uint64_t s, uint64_t elem, uint32_t st) : seed(s), elem_lo((uint32_t)elem), elem_hi((uint32_t)(elem >> 32)), stream(st), block(0), have(0) {}
     __device__ void refill() {
         uint32_t c[4] = {elem_lo, elem_hi ^ (stream * 0x9E3779B1u), block++, 0x50656172u};
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-        for (int r = 0; r < 10; ++r) {
-            px_round(c, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
+        riprng::philox(c, seed);
         for (int i = 0; i < 4; ++i) buf[i] = c[i];
         have = 4;
     }

@@ -16,22 +16,9 @@
 
 #include "pink_fft.h"
 #include "rip_host.h"
+#include "rip_rng.h"
 
 namespace {
-
-__device__ __forceinline__ void philox10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (uint32_t)p1;
-        c[3] = (uint32_t)p0;
-        c[0] = n0;
-        c[2] = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 
 // a_k for k = 0 .. L-1, once per frame length (the f64 power is the most expensive operation of the fill, and the same for every
 // frame): signed frequency index as the reference builds it -- linspace(0, 1 - 1/L, L), upper half minus one, times L
@@ -71,7 +58,7 @@ __device__ __forceinline__ void pink_pair(const double *__restrict__ normals, co
         b2 = normals[(size_t)f * 2 * L + L + j2];
     } else {
         uint32_t c[4] = {(uint32_t)j, (uint32_t)(j >> 32) ^ (uint32_t)f, stream_id, 0x70696e6bu};
-        philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        riprng::philox(c, seed);
         box_muller_64(c[0], c[1], a, b);
         box_muller_64(c[2], c[3], a2, b2);
     }

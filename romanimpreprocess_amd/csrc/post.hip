@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "rip_host.h"
+#include "rip_select.h"
 
 namespace {
 
@@ -79,34 +80,23 @@ __global__ __launch_bounds__(256) void bin_mean_kernel(const float *__restrict__
 
 // ------------------------------------------------------------------------------------------ order statistics
 // Blocks: nby x nbx rectangles of ky x kx pixels starting at (y0, x0) of an (ny, nx) f32 image.  NaNs are ignored.
-// Three radix levels (11 + 11 + 10 bits) on the order-preserving integer image of the float.
-#define PS_BINS 2048
+// Three radix levels on the order-preserving key of the float (rip_select.h).
 #define PS_MAX_BLOCKS 65535   // grid.y of the histogram launches
-__device__ __forceinline__ uint32_t ps_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ps_unkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ int ps_shift(int level) { return level == 0 ? 21 : (level == 1 ? 10 : 0); }
-__device__ __forceinline__ int ps_nbits(int level) { return level == 2 ? 10 : 11; }
-
 struct PsGeom {
     int ny, nx, y0, x0, ky, kx, nby, nbx;
 };
 
-// level < 0: count the valid (non-NaN) elements of every block into hist[blk * PS_BINS]
+// level < 0: count the valid (non-NaN) elements of every block into hist[blk * SEL_BINS]
 __global__ __launch_bounds__(256) void ps_hist_kernel(const float *__restrict__ arr, PsGeom g, const uint32_t *__restrict__ prefix,
                                                       uint32_t *__restrict__ hist, int level) {
-    __shared__ uint32_t h[PS_BINS];
+    __shared__ uint32_t h[SEL_BINS];
     const int blk = blockIdx.y, by = blk / g.nbx, bx = blk % g.nbx;
-    for (int i = threadIdx.x; i < PS_BINS; i += blockDim.x) h[i] = 0;
+    for (int i = threadIdx.x; i < SEL_BINS; i += blockDim.x) h[i] = 0;
     __syncthreads();
     const size_t n = (size_t)g.ky * g.kx;
-    const int shift = level >= 0 ? ps_shift(level) : 0;
-    const uint32_t mask = level >= 0 ? (1u << ps_nbits(level)) - 1u : 0u;
-    const int above = level >= 0 ? shift + ps_nbits(level) : 32;
+    const int shift = level >= 0 ? sel_shift(level) : 0;
+    const uint32_t mask = level >= 0 ? (1u << sel_bits(level)) - 1u : 0u;
+    const int above = level >= 0 ? shift + sel_bits(level) : 32;
     const uint32_t pre = (level > 0) ? prefix[blk] : 0u;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int yy = g.y0 + by * g.ky + (int)(i / g.kx), xx = g.x0 + bx * g.kx + (int)(i % g.kx);
@@ -115,14 +105,14 @@ __global__ __launch_bounds__(256) void ps_hist_kernel(const float *__restrict__ 
         if (level < 0) {
             atomicAdd(&h[0], 1u);
         } else {
-            const uint32_t key = ps_key(v);
+            const uint32_t key = f2key(v);
             if (above < 32 && ((key ^ pre) >> above) != 0) continue;
             atomicAdd(&h[(key >> shift) & mask], 1u);
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < PS_BINS; i += blockDim.x)
-        if (h[i]) atomicAdd(&hist[(size_t)blk * PS_BINS + i], h[i]);
+    for (int i = threadIdx.x; i < SEL_BINS; i += blockDim.x)
+        if (h[i]) atomicAdd(&hist[(size_t)blk * SEL_BINS + i], h[i]);
 }
 
 // one thread per block: walk the histogram to the bin holding `rank`, extend the key prefix, rebase the rank
@@ -130,22 +120,22 @@ __global__ void ps_scan_kernel(uint32_t *__restrict__ hist, uint32_t *__restrict
                                int nblk, int level) {
     const int blk = blockIdx.x * blockDim.x + threadIdx.x;
     if (blk >= nblk) return;
-    uint32_t *h = hist + (size_t)blk * PS_BINS;
+    uint32_t *h = hist + (size_t)blk * SEL_BINS;
     unsigned long long r = rank[blk], cum = 0;
-    const int nb = 1 << ps_nbits(level);
+    const int nb = 1 << sel_bits(level);
     int b = 0;
     for (; b < nb - 1; ++b) {
         if (cum + h[b] > r) break;
         cum += h[b];
     }
     rank[blk] = r - cum;
-    prefix[blk] = (level == 0 ? 0u : prefix[blk]) | ((uint32_t)b << ps_shift(level));
-    for (int i = 0; i < PS_BINS; ++i) h[i] = 0;
+    prefix[blk] = (level == 0 ? 0u : prefix[blk]) | ((uint32_t)b << sel_shift(level));
+    for (int i = 0; i < SEL_BINS; ++i) h[i] = 0;
 }
 
 __global__ void ps_finish_kernel(const uint32_t *__restrict__ prefix, float *__restrict__ out, int nblk) {
     const int blk = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blk < nblk) out[blk] = ps_unkey(prefix[blk]);
+    if (blk < nblk) out[blk] = key2f(prefix[blk]);
 }
 
 // ------------------------------------------------------------------------------------------ smoothed histogram
@@ -368,7 +358,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
     DevBuf<uint32_t> hist(ctx), prefix(ctx);
     DevBuf<unsigned long long> rk(ctx);
     int rc;
-    if ((rc = d.upload(arr, n)) || (rc = hist.alloc((size_t)nblk * PS_BINS)) || (rc = prefix.alloc(nblk)) || (rc = rk.alloc(nblk)) ||
+    if ((rc = d.upload(arr, n)) || (rc = hist.alloc((size_t)nblk * SEL_BINS)) || (rc = prefix.alloc(nblk)) || (rc = rk.alloc(nblk)) ||
         (rc = o.alloc(nblk)))
         return rc;
     const PsGeom g{ny, nx, y0, x0, ky, kx, nby, nbx};
@@ -376,13 +366,13 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
     unsigned chunks = (unsigned)((per + 256 * 16 - 1) / (256 * 16));
     if (chunks < 1) chunks = 1;
     if (chunks > 1024) chunks = 1024;
-    RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * PS_BINS * 4, ctx->stream));
+    RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * SEL_BINS * 4, ctx->stream));
     hipLaunchKernelGGL(ps_hist_kernel, dim3(chunks, nblk), dim3(256), 0, ctx->stream, d.p, g, prefix.p, hist.p, -1);
     RIP_HIP(ctx, hipGetLastError());
-    std::vector<uint32_t> hh((size_t)nblk * PS_BINS);
+    std::vector<uint32_t> hh((size_t)nblk * SEL_BINS);
     if ((rc = hist.download(hh.data(), hh.size())) || (rc = dev_sync(ctx))) return rc;
     std::vector<int64_t> cnt(nblk);
-    for (int b = 0; b < nblk; ++b) cnt[b] = hh[(size_t)b * PS_BINS];
+    for (int b = 0; b < nblk; ++b) cnt[b] = hh[(size_t)b * SEL_BINS];
     if (counts)
         for (int b = 0; b < nblk; ++b) counts[b] = cnt[b];
     std::vector<unsigned long long> r(nblk);
@@ -393,7 +383,7 @@ int rip_stage_select_ranks(rip_ctx *ctx, const float *arr, int ny, int nx, int y
             r[b] = (want >= 0 && want < cnt[b]) ? (unsigned long long)want : 0ull;
         }
         if ((rc = rk.copy_in(r.data(), nblk))) return rc;
-        RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * PS_BINS * 4, ctx->stream));
+        RIP_HIP(ctx, hipMemsetAsync(hist.p, 0, (size_t)nblk * SEL_BINS * 4, ctx->stream));
         for (int level = 0; level < 3; ++level) {
             hipLaunchKernelGGL(ps_hist_kernel, dim3(chunks, nblk), dim3(256), 0, ctx->stream, d.p, g, prefix.p, hist.p, level);
             hipLaunchKernelGGL(ps_scan_kernel, dim3((nblk + 63) / 64), dim3(64), 0, ctx->stream, hist.p, prefix.p, rk.p, nblk, level);

@@ -16,9 +16,9 @@
 // All medians are exact selections (np.median: mean of the two middle elements in f32).
 // Arithmetic recipe: oracle/refpix.py.
 //
-// Keys, the selection levels' scan step, the median of a selected pair, the row correction and the channel line come from
-// refpix_shared.h (shared with refpix_one.hip).
-#include "rip_common.h"
+// Keys, the selection levels' scan step and the median of a selected pair come from rip_select.h, the row correction and the
+// channel line from refpix_shared.h (shared with refpix_one.hip).
+#include "rip_host.h"
 #include "refpix_shared.h"
 
 // np.median of vals[0..n) in LDS by an in-place bitonic sort; the buffer must hold npow2 >= n floats
@@ -234,13 +234,6 @@ __global__ __launch_bounds__(1024) void chan_kernel(const DT *__restrict__ data,
         lines[o] = m;
         lines[o + 1] = c;
     }
-}
-
-template <typename K>
-static int with_lds(rip_ctx *ctx, K kernel, size_t lds) {
-    if (lds > 48 * 1024)
-        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return RIP_OK;
 }
 
 // which pre-pass makes the tables: 1 the single launch of refpix_one.hip, 0 the launches below.  option (rip_ctx::prepass_form,

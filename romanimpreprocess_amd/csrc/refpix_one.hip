@@ -38,8 +38,8 @@
 // lines by one wave instruction, each storing wave waits vmcnt(0) before its workgroup's lane 0 arrives on the counter, consumers
 // poll with sc1 loads, pass a workgroup barrier and read with sc1 loads.
 //
-// Keys, the selection levels' digit layout and scan step, the median of a selected pair, the row correction and the channel line
-// come from refpix_shared.h (shared with refpix.hip).
+// Keys, the selection levels' digit layout and scan step and the median of a selected pair come from rip_select.h, the row
+// correction and the channel line from refpix_shared.h (shared with refpix.hip).
 #include "rip_common.h"
 #include "refpix_shared.h"
 #include <string.h>

@@ -63,6 +63,14 @@ inline int dev_sync(rip_ctx *ctx, hipStream_t stream = nullptr) {
     return RIP_OK;
 }
 
+// before a launch with `lds` bytes of dynamic LDS: above the 48 KB a kernel may take by default, its limit has to be raised
+template <typename K>
+inline int with_lds(rip_ctx *ctx, K kernel, size_t lds) {
+    if (lds > 48 * 1024)
+        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return RIP_OK;
+}
+
 // caldir.hip
 RIP_SHARED void free_cal(RipCal &c);
 // plan.hip

@@ -1,6 +1,7 @@
-// Counter-based random deviates for the simulation-side kernels (synth.hip): Philox-4x32-10 keyed by a 64-bit seed, the
-// counter words chosen by the caller (pixel, read / plane, attempt, domain tag), so every deviate is a pure function of its
-// coordinates: reproducible, order-independent, no generator state in memory.
+// Counter-based random deviates of every device generator (synth.hip, cr.hip, noise.hip, pink.hip, pearson.hip): Philox-4x32-10
+// keyed by a 64-bit seed, the counter words chosen by the caller (pixel, read / plane, attempt, domain tag), so every deviate is
+// a pure function of its coordinates: reproducible, order-independent, no generator state in memory.  The counter layouts are
+// listed in DESIGN.md ("Shared device headers").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,13 +29,17 @@ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
     return ((double)(((uint64_t)hi << 21) | (lo >> 11)) + 0.5) * (1.0 / 9007199254740992.0);
 }
 
-// one f32 standard normal for (a, b, tag): Box-Muller on two 24-bit uniforms
-__device__ __forceinline__ float normal_f32(uint64_t seed, uint32_t a, uint32_t b, uint32_t tag) {
-    uint32_t c[4] = {a, b, tag, 0x6c317379u};
+// f32 uniform in (0, 1) from the top 24 bits of a word
+__device__ __forceinline__ float u24(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+
+// Box-Muller on two 24-bit uniforms
+__device__ __forceinline__ float box_muller_f32(uint32_t w0, uint32_t w1) { return sqrtf(-2.0f * logf(u24(w0))) * cospif(2.0f * u24(w1)); }
+
+// one f32 standard normal for the counter (a, b, tag, domain), from words 0 and 1 of its block
+__device__ __forceinline__ float normal_f32(uint64_t seed, uint32_t a, uint32_t b, uint32_t tag, uint32_t domain = 0x6c317379u) {
+    uint32_t c[4] = {a, b, tag, domain};
     philox(c, seed);
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
+    return box_muller_f32(c[0], c[1]);
 }
 
 // log(k!) for integer-valued k >= 0: exact table below 8, Stirling's series above (truncation < 2e-12 at k + 1 = 9): one logarithm

@@ -5,10 +5,10 @@ the reader and the make_dark_file drop-in are tested on."""
 import numpy as np
 
 # ---------------------------------------------------------------------------------------------- clip
-# (planes, pixels): every plane count of the list 1, 2, 3, 4, 63, 64, 65, 257, 512 (one wave's share of the planes is n / 4: empty
-# shares, shares of different length, the largest column that LDS holds) and pixel counts 1, 63, 65 and 64 k + 7
+# (planes, pixels): every plane count of the list 1, 2, 3, 4, 5, 63, 64, 65, 257, 512 (one wave's share of the planes is n / 4:
+# empty shares, shares of different length, the largest column that LDS holds) and pixel counts 1, 63, 65 and 64 k + 7
 CLIP_SHAPES = [(1, 65), (2, 63), (3, 1), (4, 199), (63, 65), (64, 63), (65, 199), (257, 65), (512, 199), (37, 1), (37, 63), (37, 65),
-               (37, 199)]
+               (37, 199), (5, 65)]
 
 
 def noisy(n, npix, seed, centre=1000.0, sd=5.0, frac=0.08):

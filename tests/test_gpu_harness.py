@@ -68,7 +68,7 @@ def test_statistics_match_the_reference_script(name):
     assert_same_bits(img[[0, 1, 3, 4, 5, 6, 7]].cpu().numpy(), out[[0, 1, 3, 4, 5, 6, 7]], "other planes")
 
 
-@pytest.mark.parametrize("nseeds", [1, 2, 255, 256, 300, 600])
+@pytest.mark.parametrize("nseeds", [1, 2, 3, 4, 5, 255, 256, 300, 600])
 def test_medians_for_many_realisations(nseeds):
     """LDS-resident columns (<= 512 realisations) and the re-reading fallback, odd and even counts, ties, signed zeros."""
     rng = np.random.default_rng(nseeds)
