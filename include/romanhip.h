@@ -468,6 +468,11 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
                 corrected cube asked for, no caller's channel lines on the device, and a CALDIR set that passed the screen of
                 rip_caldir_first_group_safe; the pre-pass then makes the tables of groups 1 .. G-1 only.  0 = every launch takes
                 the full form.  rip_last_chain_first_group tells which form ran;
+   "prepass_gate" -- (default 0 = off; measured without a gain, profiles/prepass_gate.txt) N > 0: an overlapped pre-pass whose predecessor call ran the fused kernel starts behind a one-wave
+                gate that waits until every workgroup of that fused launch has started (the workgroups count themselves in), so
+                that the pre-pass's small workgroups do not take pieces of CUs at the kernel boundary; the value is the bound of
+                that wait in microseconds, after which the gate gives up and the pre-pass starts anyway; 0 = no gate and no
+                counting.  rip_last_prepass_gate tells what the last call's gate did;
    "pink_form" -- the complex-to-real transform of the 1/f frames: -1 (default) the library's own two-pass transform for
                 power-of-two frame lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise, 0 hipFFT for every length;
    "overlap" -- run the reference-pixel pre-pass of a ramp on a second stream so that it overlaps the previous ramp's
@@ -479,6 +484,10 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value);
 int rip_last_chain_form(rip_ctx *ctx);
 /* 1: the fused launch of the last rip_calibrate skipped group 0 (option "skip_first"); 0: it did not, or the stage kernels ran */
 int rip_last_chain_first_group(rip_ctx *ctx);
+/* the gate in front of the overlapped pre-pass of the last rip_calibrate (option "prepass_gate"): 0 = none was queued, 1 = the
+   counter released it, 2 = it gave up at its bound; *giveups (may be NULL) receives the give-ups of all gates of this context so
+   far.  Waits for the context's streams.  Negative: an error code. */
+int rip_last_prepass_gate(rip_ctx *ctx, int *giveups);
 
 /* Is a fused-kernel form compiled for a complete chain with this many Legendre planes, groups and these ipc4d / gain dtypes
    (RIP_F32 / RIP_F64)?  2 = yes (the value rip_last_chain_form reports), 0 = such a ramp takes the stage kernels.  Needs no

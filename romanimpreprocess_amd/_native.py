@@ -169,6 +169,7 @@ SYMBOLS = {
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_last_chain_form": (_I, [_VP]),
     "rip_last_chain_first_group": (_I, [_VP]),
+    "rip_last_prepass_gate": (_I, [_VP, C.POINTER(C.c_int)]),
     "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
     "rip_chain_geometry_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "rip_last_chain_geometry": (_I, [_VP, C.POINTER(_I)]),
@@ -318,6 +319,16 @@ class Context:
     def last_chain_first_group(self):
         """1 = the fused launch of the last calibrate call skipped group 0 (option "skip_first"), 0 = it did not (or stage kernels)."""
         return int(self.lib.rip_last_chain_first_group(self.h))
+
+    def last_prepass_gate(self):
+        """(state, give-ups) of the gate in front of the last calibrate call's overlapped pre-pass (option "prepass_gate"): state 0 =
+        none queued, 1 = released by the fused kernel's workgroup count, 2 = gave up at its bound; give-ups of this context so far.
+        Waits for the context's streams."""
+        n = C.c_int(0)
+        rc = int(self.lib.rip_last_prepass_gate(self.h, C.byref(n)))
+        if rc < 0:
+            self.check(rc)
+        return rc, int(n.value)
 
     def caldir_first_group_safe(self, slot):
         """True where the set in ``slot`` passed the upload screen that lets the fused kernel skip an excluded first group."""

@@ -73,6 +73,10 @@ int rip_ctx_create(int device_id, rip_ctx **out) {
     ctx->ncu = prop.multiProcessorCount;
     // (queue priorities -- main stream above the second -- and a raised wave priority of the fused kernel were both tried against
     // the 4 % the overlapped pre-pass costs the fused kernel it runs beside: no effect, profiles/r04_summary.md)
+    // A gate that holds the pre-pass back until the fused grid is resident (option "prepass_gate", calibrate.hip) moves its start
+    // from the kernel boundary to 9 us behind it and gains 0.3-0.6 % of the wall time, inside the benchmark's noise: off by default.
+    // The traces show where the rest goes: the first histogram kernel (16 KB of LDS) finds no room until the fused workgroups
+    // begin to leave, 600 us on, so two thirds of the pre-pass run in the fused kernel's tail either way (profiles/prepass_gate.txt)
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete ctx;
@@ -86,6 +90,14 @@ int rip_ctx_create(int device_id, rip_ctx **out) {
             ctx->use_overlap = false;
         }
     if (!ctx->stream2) ctx->use_overlap = false;
+    // the words of the pre-pass gate (calibrate.hip); without them, or without the clock that bounds its wait, no gate is queued
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0) ctx->wall_khz = khz;
+    if (hipMalloc((void **)&ctx->gate_words, RIP_GATE_WORDS * 4) != hipSuccess) ctx->gate_words = nullptr;
+    if (ctx->gate_words && hipMemset(ctx->gate_words, 0, RIP_GATE_WORDS * 4) != hipSuccess) {
+        (void)hipFree(ctx->gate_words);
+        ctx->gate_words = nullptr;
+    }
     *out = ctx;
     return RIP_OK;
 }
@@ -108,6 +120,7 @@ void rip_ctx_destroy(rip_ctx *ctx) {
         if (p) (void)hipFree(p);
     if (ctx->chain_dbg_buf) (void)hipFree(ctx->chain_dbg_buf);
     if (ctx->prepass_stamps) (void)hipFree(ctx->prepass_stamps);
+    if (ctx->gate_words) (void)hipFree(ctx->gate_words);
     if (ctx->stream3) {
         (void)hipStreamSynchronize(ctx->stream3);
         (void)hipStreamDestroy(ctx->stream3);
@@ -177,6 +190,11 @@ int rip_set_option(rip_ctx *ctx, const char *name, int value) {
         ctx->prepass_form = value;
         return RIP_OK;
     }
+    if (name && strcmp(name, "prepass_gate") == 0) {   // 0: no gate; N > 0: the bound of its wait in microseconds
+        if (value < 0 || value > 1000000) return rip_fail(ctx, RIP_EINVAL, "prepass_gate: 0 (off) or a bound of 1 .. 1000000 microseconds");
+        ctx->prepass_gate = value;
+        return RIP_OK;
+    }
     if (name && strcmp(name, "pink_form") == 0) {
         ctx->pink_form = value;
         return RIP_OK;
@@ -242,6 +260,18 @@ int rip_prepass_stamps(rip_ctx *ctx, int nwg, unsigned long long *out) {
 
 int rip_last_chain_form(rip_ctx *ctx) { return ctx ? ctx->last_form : RIP_EINVAL; }
 int rip_last_chain_first_group(rip_ctx *ctx) { return ctx ? (ctx->last_form == 2 ? ctx->last_first_group : 0) : RIP_EINVAL; }
+// the gate of the last rip_calibrate: 0 none queued, 1 released by the counter, 2 gave up at its bound; *giveups (may be NULL):
+// the give-ups of every gate of this context so far.  Waits for both streams.
+int rip_last_prepass_gate(rip_ctx *ctx, int *giveups) {
+    if (!ctx) return RIP_EINVAL;
+    if (giveups) *giveups = 0;
+    if (!ctx->gate_words) return 0;
+    if (const int rc = rip_synchronize(ctx)) return rc;
+    uint32_t w[2] = {0, 0};
+    RIP_HIP(ctx, hipMemcpy(w, ctx->gate_words + RIP_GATE_GIVEUPS, sizeof w, hipMemcpyDeviceToHost));
+    if (giveups) *giveups = (int)w[0];
+    return ctx->last_gate ? (int)w[1] : 0;
+}
 int rip_caldir_first_group_safe(rip_ctx *ctx, int slot) {
     if (!ctx) return RIP_EINVAL;
     if (slot < 0 || slot >= (int)ctx->cals.size() || !ctx->cals[slot].valid) return rip_fail(ctx, RIP_EINVAL, "caldir slot %d is empty", slot);

@@ -48,7 +48,9 @@ extern "C" int rip_calibrate_batch(rip_ctx *ctx, int slot, int plan_id, unsigned
     BatchSet set[2];
     int rc = RIP_OK;
     ctx->batch_completed = 0;  // ramps whose results have been queued for download in full (valid after an error return too)
+    ctx->in_batch = true;   // the second stream carries the uploads: no pre-pass gate on it (calibrate.hip)
     auto cleanup = [&]() {   // waits for every stream; the device buffers stay with the context
+        ctx->in_batch = false;
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamSynchronize(s_in);
         (void)hipStreamSynchronize(s_out);

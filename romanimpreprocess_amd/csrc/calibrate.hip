@@ -176,8 +176,9 @@ struct Calibration {
     // ---- reference-pixel tables and the saturation pass, then the chain's first mark on the main stream.  With device-resident
     // inputs the pre-pass runs on a second stream so that it overlaps the previous ramp's main kernel; the tables are
     // double-buffered by call parity:
-    //   stream2: wait(main kernels of call n-2 done) -> pre-pass -> ev_tab[p]
+    //   stream2: wait(main kernels of call n-2 done) -> gate -> pre-pass -> ev_tab[p]
     //   stream : wait(ev_tab[p]) -> main kernels -> ev_done[p]
+    // (the gate: prepass_gate below)
     int prepass() {
         // inputs guarded by a caller's event: the kernels on the main stream read them as well
         if (!host && in->ready_event) RIP_HIP(ctx, hipStreamWaitEvent(ctx->stream, (hipEvent_t)in->ready_event, 0));
@@ -186,6 +187,7 @@ struct Calibration {
                   ? (char *)rip_ws(ctx, RIP_WS_TABLES, 2 * tab_bytes + npix * 4 + 512)
                   : nullptr;
         par = ctx->parity;
+        ctx->last_gate = 0;
         choose_skip();
         // (by situation: where the fused kernel fills the LDS the pre-pass of the next ramp finds no room beside it, runs when it
         // drains, and the single-launch form in front of the own ramp is the shorter way: 1.121 against 1.140 ms per ramp at f64
@@ -203,6 +205,26 @@ struct Calibration {
         }
         mark(ctx, ctx->stream);
         return RIP_OK;
+    }
+
+    // ---- The gate in front of an overlapped pre-pass (option "prepass_gate").  What releases pre-pass n on the second stream is
+    // the end of the main kernels of call n-2, and that is the instant at which the fused kernel of call n-1 starts to dispatch:
+    // the pre-pass's small workgroups then take pieces of CUs that the fused workgroups cannot use until they leave, and the fused
+    // kernel ends as late as its last-started workgroup.  An event fires only at a kernel boundary, so the release comes from
+    // inside the running kernel: every fused workgroup counts itself in (ChainArgs::wg_counter), and one wave on the second stream
+    // waits until the count has reached the host's running total after the launch of call n-1.
+    // The gate orders nothing that correctness needs (the event waits in front of it stay as they are), so its wait is bounded
+    // and falling through is always correct.  Queued only where the PREVIOUS call on this context queued a fused launch with the
+    // counter: not on the first call, not after a call that took the stage kernels, not inside rip_calibrate_batch (whose second
+    // stream carries the uploads).
+    // No cycle: fused n-1 waits only for ev_tab of pre-pass n-1 (and the main stream before it), which was recorded on the second
+    // stream BEFORE gate n is queued; gate n waits for fused n-1 to have started; fused n waits for pre-pass n.  Should the
+    // runtime map both streams onto one hardware queue, gate n sits in front of fused n-1 there, and the bound ends the wait: it
+    // is there for that case.
+    int prepass_gate() {
+        if (!(overlap && pre != ctx->stream && ctx->prepass_gate > 0 && ctx->gate_words && ctx->gate_armed && !ctx->in_batch)) return RIP_OK;
+        ctx->last_gate = 1;
+        return rip_launch_prepass_gate(ctx, ctx->gate_words, ctx->gate_total, ctx->prepass_gate, pre);
     }
 
     int refpix_tables() {
@@ -228,8 +250,9 @@ struct Calibration {
                 RIP_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_in, 0));
             }
         }
-        mark(ctx, pre);
         int rc;
+        if ((rc = prepass_gate())) return rc;
+        mark(ctx, pre);
         if ((rc = pre_order()) || (rc = rip_launch_refpix_prepass(ctx, ra, rip_refpix_form(ctx->prepass_form, ra)))) return rc;
         if (do_sat && (rc = sat_pass())) return rc;  // same stream as the pre-pass: overlaps the previous ramp's main kernel
         if ((rc = pre_done())) return rc;
@@ -289,6 +312,7 @@ struct Calibration {
         ctx->last_form = 0;
         ctx->last_first_group = 0;
         memset(ctx->last_geo, 0, sizeof ctx->last_geo);
+        ctx->gate_armed = false;   // (the launcher sets it: the next call's gate waits for a launch that carries the counter)
         if (!(ctx->use_fused && !c.has_inf && do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
               rip_chain_supported(ctx, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype))) {
             // (a call planned without group 0 must reach the fused kernel: the stage kernels would read unwritten tables)
@@ -336,6 +360,7 @@ struct Calibration {
         ca.merged_dq = c.merged_plane[((flat ? 1 : 0) | ((stages & RIP_STAGE_DARK) ? 2 : 0))];
         ca.dbg = ctx->chain_dbg;
         ca.dbg_buf = ctx->chain_dbg_buf;
+        ca.wg_counter = ctx->prepass_gate > 0 ? ctx->gate_words : nullptr;
         const int rc = rip_launch_chain(ctx, plan, ca, c.lin_nplanes, c.ipc_dtype, skip0);
         // (choose_skip has asked the launcher's own questions: the stage kernels would find group 0's tables unwritten)
         if (rc == 1 && skip0) return rip_fail(ctx, RIP_ESTATE, "calibrate: the fused kernel declined a launch planned without group 0");

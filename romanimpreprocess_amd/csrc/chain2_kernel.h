@@ -206,6 +206,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     // ChainArgs is the first kernel argument: it sits at offset 0 of the kernarg segment
     const RIP_K C2KernArgs *kargs = (const RIP_K C2KernArgs *)__builtin_amdgcn_kernarg_segment_ptr();
     const int tid = threadIdx.x;
+    // every workgroup of the launch (the idle ones of the grid's tail too) counts itself in as it starts: the gate in front of the
+    // next call's pre-pass waits until the whole grid has its slots (calibrate.hip).  Relaxed: nothing is published through it.
+    if (a.wg_counter && tid == 0) __hip_atomic_fetch_add(a.wg_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef C2_DBG
     const int dbg = a.dbg;  // timing experiments only (tools/gpu_checks/phase_timing.py): bits switch phases off
 #else
@@ -1118,6 +1121,8 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
                        reinterpret_cast<const RipPlanHeader *>(plan->dev), plan->d_variants, plan->d_k, plan->d_diffs,
                        ctx->guard_band);
     RIP_HIP(ctx, hipGetLastError());
+    // the host's running total of the workgroups that will have counted themselves in (modulo 2^32, like the counter)
+    if (ag.wg_counter) ctx->gate_total += (uint32_t)grid, ctx->gate_armed = true;
     return RIP_OK;
 }
 

@@ -5,6 +5,7 @@
 //                       full-frame coordinates with 16 KiB-aligned rows.
 //   flat_prepare_kernel utils/flatutils.py:46-69 (pad with 1, NO_FLAT_FIELD / NO_GAIN_VALUE flags, clips)
 //   flat_area_kernel    L1_to_L2/gen_cal_image.py:622  flat = f32(flat / AreaFactor)
+//   prepass_gate_kernel one wave that holds an overlapped pre-pass back until the fused grid beside it is resident
 #include "rip_common.h"
 
 template <typename T>
@@ -287,6 +288,31 @@ int rip_launch_or_bytes(rip_ctx *ctx, uint8_t *bytes, size_t n, uint8_t bit, hip
     const uint32_t b = bit;
     hipLaunchKernelGGL(or_bytes_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, (uint32_t *)bytes, n / 4,
                        b | (b << 8) | (b << 16) | (b << 24));
+    RIP_HIP(ctx, hipGetLastError());
+    return RIP_OK;
+}
+
+// The gate in front of an overlapped pre-pass (calibrate.hip).  ONE wave; lane 0 polls the count of started fused workgroups with
+// relaxed agent-scope loads (they read through to the memory side; never an acquire: the gate orders nothing, the pre-pass reads
+// nothing those workgroups write) and sleeps between polls.  The wait is bounded by the constant-rate clock: on the bound the gate
+// falls through, which is always correct, and counts a give-up.  It leaves 1 (released) or 2 (gave up) in the state word.
+__global__ __launch_bounds__(64) void prepass_gate_kernel(uint32_t *__restrict__ words, uint32_t target, unsigned long long bound_ticks) {
+    if (threadIdx.x != 0) return;
+    const unsigned long long t0 = wall_clock64();
+    uint32_t state = 1;
+    while ((int32_t)(__hip_atomic_load(words + RIP_GATE_COUNTER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
+        if (wall_clock64() - t0 >= bound_ticks) {
+            state = 2;
+            __hip_atomic_fetch_add(words + RIP_GATE_GIVEUPS, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(16);   // 16 x 64 cycles, about half a microsecond
+    }
+    __hip_atomic_store(words + RIP_GATE_STATE, state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+int rip_launch_prepass_gate(rip_ctx *ctx, uint32_t *words, uint32_t target, int bound_us, hipStream_t stream) {
+    const unsigned long long ticks = (unsigned long long)bound_us * (unsigned long long)ctx->wall_khz / 1000ull;
+    hipLaunchKernelGGL(prepass_gate_kernel, dim3(1), dim3(64), 0, stream, words, target, ticks);
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;
 }

@@ -161,6 +161,13 @@ enum RipWs {
     RIP_WS_COUNT
 };
 
+// words of rip_ctx::gate_words: the counter has a 128-byte line of its own (every fused workgroup adds to it, one lane polls it)
+enum { RIP_GATE_COUNTER = 0, RIP_GATE_GIVEUPS = 32, RIP_GATE_STATE = 33, RIP_GATE_WORDS = 64 };
+// option "prepass_gate": the bound of the gate's wait in microseconds, 0 = no gate.  Off by default: the gate does what it was built
+// for (the pre-pass starts 9 us after the fused launch instead of with it) and the fused kernel gains 0.4 %, inside the noise of
+// the benchmark (profiles/prepass_gate.txt).  100 is the bound to try it with: the fused grid is resident within 8 to 19 us.
+#define RIP_GATE_DEFAULT_US 0
+
 struct rip_ctx {   // host-only: no kernel reads it
     int device = 0;
     int ncu = 0;             // launch geometry of the fused kernel, per CONTEXT (a second context may sit on another device): CU count
@@ -185,6 +192,17 @@ struct rip_ctx {   // host-only: no kernel reads it
     hipEvent_t ev_pre = nullptr;
     hipStream_t pre_stream = nullptr;
     bool ev_pre_valid = false;
+    // the gate in front of an overlapped pre-pass (calibrate.hip: prepass_gate; option "prepass_gate" = its bound in microseconds,
+    // 0 = off).  gate_words (device, RIP_GATE_*): the monotonic count of fused workgroups that have started, never reset; the
+    // give-ups of all gates; the state the last gate left.  gate_total: the workgroups of every fused launch queued with the
+    // counter so far, modulo 2^32.  gate_armed: the previous rip_calibrate on this context queued such a launch.
+    uint32_t *gate_words = nullptr;
+    uint32_t gate_total = 0;
+    bool gate_armed = false;
+    bool in_batch = false;     // inside rip_calibrate_batch: the second stream carries the uploads, no gate goes on it
+    int prepass_gate = RIP_GATE_DEFAULT_US;
+    int last_gate = 0;         // the last rip_calibrate queued a gate (rip_last_prepass_gate)
+    int wall_khz = 100000;     // rate of wall_clock64(), the clock that bounds the gate's wait
 
     // ---- workspaces (rip_ws: grown on demand, kept between calls)
     void *ws[RIP_WS_COUNT] = {};   // RipWs
@@ -334,6 +352,9 @@ struct ChainArgs {
     // the last strip has at most 64 live columns (nx = 4096: 17th strip of the 256-column form) it is covered by geo_nq workgroups
     // whose COLS / 64 wave columns (four or six) each march down their OWN range of geo_rows_q rows of that strip (0: every strip alike)
     int geo_nr, geo_rows, geo_nq, geo_rows_q;
+    // rip_ctx::gate_words or null: every workgroup of the launch adds 1 to this word as the first thing it does (relaxed, agent
+    // scope; nothing is published through it).  The gate in front of the next call's overlapped pre-pass polls it (calibrate.hip)
+    uint32_t *wg_counter;
 };
 // THE list of the group counts the fused kernel has a form for, in the parts its instantiations are compiled in (one translation
 // unit per part, Legendre order and ipc4d dtype: chain_np*.hip with -DC2_PART).  The launch switch (chain2_kernel.h), the
@@ -404,6 +425,8 @@ int rip_launch_flat_area(rip_ctx *ctx, const float *flat_dn, const double *area,
 int rip_launch_merge_dq(rip_ctx *ctx, const uint32_t *lin_dq, const uint32_t *flat_flags, const uint32_t *dark_dq, uint32_t *out, int ny,
                         int nx, int nb, uint32_t *d_clash);
 int rip_launch_or_bytes(rip_ctx *ctx, uint8_t *bytes, size_t n, uint8_t bit, hipStream_t stream = nullptr);
+// one wave on `stream` that returns once (int32)(words[RIP_GATE_COUNTER] - target) >= 0, or after bound_us microseconds
+int rip_launch_prepass_gate(rip_ctx *ctx, uint32_t *words, uint32_t target, int bound_us, hipStream_t stream);
 // *d_bad |= 1 unless lo <= |p[i]| <= hi for every i < n (NaN fails), |= 2 where some p[i] is infinite; p of RIP_F32 / RIP_F64 elements
 int rip_launch_screen(rip_ctx *ctx, const void *p, int dtype, size_t n, double lo, double hi, uint32_t *d_bad);
 // *d_bad |= 1 unless f32(smax[i] - smin[i]) is non-zero and not NaN for every i < n
