@@ -448,36 +448,32 @@ int rip_stats_reduce(rip_ctx *ctx, int nseeds, const float *diffs, const float *
 int rip_profile_enable(rip_ctx *ctx, int on);
 int rip_profile_read(rip_ctx *ctx, double out_ms[4], int *ncalls);
 
-/* options: "fused" (default 1) -- run the chain as the single fused kernel when the configuration allows it (complete chain on a
-   u16 cube; f32 gain; 4, 9 or 11 Legendre planes; 5 to 16 groups; flag words of the CALDIR set mergeable); 0 forces the
-   stage-by-stage kernels.  Both give identical results. */
+/* ---- options of a context ---------------------------------------------------------------------
+   One table in the library (csrc/api.hip) holds every option's name, default and accepted range; the calls below all read it.
+   Results are identical whatever the integer options hold (chain_dbg excepted): they exist for A/B timing and tests.
+   A value outside [lo, hi], or an unknown name, is RIP_EINVAL and changes nothing.  "any" = every int is taken, 0 = off.
+     name            default  range         meaning
+     "fused"            1     any           the chain as one fused kernel where the configuration allows it (complete chain on a u16 cube; f32 gain; 4, 9 or 11 Legendre planes; 5 to 16 groups; mergeable flag words); 0 = the stage-by-stage kernels
+     "chain2"           1     any           the fused kernel (chain2_kernel.h: f32 or f64 ipc4d, 5 to 16 groups); 0 = the stage kernels where it would run
+     "chain_quad"       1     any           a last strip of at most 64 live columns goes to workgroups whose 64-column wave columns take a row range each (4096 x 4096: 504 workgroups of 139 steps, not 510 of 143; timing-neutral, profiles/r04_summary.md)
+     "skip_first"       1     any           the fused kernel neither loads nor evaluates group 0 where the result cannot depend on it (an excluded first group that is the single read 0, weight zero in every fit variant, a u16 cube, no corrected cube asked for, no caller's channel lines on the device, a set that passed rip_caldir_first_group_safe; the pre-pass then makes the tables of groups 1 .. G-1 only); rip_last_chain_first_group tells which form ran
+     "chain_reserve"    8     0 .. INT_MAX  workgroup slots the 256-column fused kernel's grid leaves free; a negative value is stored as 0
+     "prepass_form"    -1     -1 .. 1       how the reference-pixel tables are made: -1 by situation (a pre-pass that overlaps the previous ramp's fused kernel as the nine small launches of refpix.hip, which slip into that kernel's tail; one in front of its own ramp on the same stream as the single launch of refpix_one.hip, 0.068 against 0.094 ms, where it covers the frame: up to 4096 rows, a reference output); 0 = refpix.hip always; 1 = refpix_one.hip wherever it covers the frame
+     "prepass_gate"     0     0 .. 1000000  N > 0: an overlapped pre-pass whose predecessor call ran the fused kernel starts behind a one-wave gate that waits, for at most N microseconds, until every workgroup of that launch has started (they count themselves in); 0 = no gate, no counting (measured without a gain, profiles/prepass_gate.txt); rip_last_prepass_gate tells what the last gate did
+     "pink_form"       -1     any           the complex-to-real transform of the 1/f frames: the library's own two-pass transform for power-of-two lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise; 0 = hipFFT for every length
+     "overlap"         -1     -1 .. 1       the reference-pixel pre-pass of a ramp on a second stream beside the previous ramp's fused kernel: -1 by situation (wherever that kernel leaves room on the CUs: every form except the f64-ipc4d one of 5 to 8 groups, whose partial coefficient ring fills the LDS), 0 never, 1 always; a context without a second stream never overlaps
+     "chain_dbg"        0     any           timing builds only: the fused kernel skips phases, results invalid
+     "guard_band"    1e-5     0 .. INFINITY (f64: the _f64 calls, and only they, take it) relative half-width of the band around the jump threshold inside which the significance is re-evaluated in the reference's exact operation order; INFINITY = always exact.  Results do not depend on it unless it is set below ~1e-6 */
 int rip_set_option(rip_ctx *ctx, const char *name, int value);
-/* further options (results identical either way; they exist for A/B timing and tests):
-   "chain2"  -- (default 1) the fused kernel (chain2_kernel.h: f32 or f64 ipc4d with 5 to 16 groups); 0 = the stage kernels
-                (rounds 1-2: a general fused kernel, dropped in round 3);
-   "prepass_form" -- how the reference-pixel tables are made: -1 (default) by situation -- a pre-pass that overlaps the previous
-                ramp's fused kernel as the nine small launches of refpix.hip (they slip into that kernel's tail), a pre-pass in
-                front of its own ramp on the same stream as the single launch of refpix_one.hip (0.068 against 0.094 ms) where
-                it covers the frame (up to 4096 rows, a reference output); 0 = refpix.hip always; 1 = refpix_one.hip wherever
-                it covers the frame;
-   "chain_reserve" -- (default 8) workgroup slots the 256-column fused kernel's grid leaves free; "chain_quad" -- (default 1) a
-                last strip of at most 64 live columns is covered by workgroups whose 64-column wave columns (four or six) take a row range each
-                (4096 x 4096: 504 workgroups of 139 steps instead of 510 of 143; timing-neutral, profiles/r04_summary.md);
-   "skip_first" -- (default 1) the fused kernel neither loads nor evaluates group 0 of the ramp where the result cannot depend
-                on it: an excluded first group that is the single read 0, weight zero in every fit variant, a u16 cube, no
-                corrected cube asked for, no caller's channel lines on the device, and a CALDIR set that passed the screen of
-                rip_caldir_first_group_safe; the pre-pass then makes the tables of groups 1 .. G-1 only.  0 = every launch takes
-                the full form.  rip_last_chain_first_group tells which form ran;
-   "prepass_gate" -- (default 0 = off; measured without a gain, profiles/prepass_gate.txt) N > 0: an overlapped pre-pass whose predecessor call ran the fused kernel starts behind a one-wave
-                gate that waits until every workgroup of that fused launch has started (the workgroups count themselves in), so
-                that the pre-pass's small workgroups do not take pieces of CUs at the kernel boundary; the value is the bound of
-                that wait in microseconds, after which the gate gives up and the pre-pass starts anyway; 0 = no gate and no
-                counting.  rip_last_prepass_gate tells what the last call's gate did;
-   "pink_form" -- the complex-to-real transform of the 1/f frames: -1 (default) the library's own two-pass transform for
-                power-of-two frame lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise, 0 hipFFT for every length;
-   "overlap" -- run the reference-pixel pre-pass of a ramp on a second stream so that it overlaps the previous ramp's
-                fused kernel: -1 (default) by situation -- wherever the fused kernel leaves room on the CUs (every form except the
-                f64-ipc4d one of 5 to 8 groups, whose partial coefficient ring fills the LDS), 0 never, 1 always. */
+int rip_set_option_f64(rip_ctx *ctx, const char *name, double value);
+/* the value as it was set (what rip_set_option stored: "overlap" reads -1, 0 or 1 whatever the context can do) */
+int rip_get_option(rip_ctx *ctx, const char *name, int *value);
+int rip_get_option_f64(rip_ctx *ctx, const char *name, double *value);
+/* every option, the f64 one included, back to its default: the state of a new context */
+int rip_reset_options(rip_ctx *ctx);
+/* row `index` of the table: 1 for an integer option, 2 for the f64 one (def / lo / hi then hold its values cut to int: the
+   default reads 0), 0 past the last row.  Any of the four pointers may be NULL.  Needs no context and no GPU. */
+int rip_option_info(int index, const char **name, int *def, int *lo, int *hi);
 
 /* how the last rip_calibrate ran: 0 = stage kernels, 2 = the fused kernel (1 and 3 were the general and the wave-private fused
    kernels of rounds 1-2) */
@@ -705,13 +701,6 @@ int rip_cal_sigma_clip_mean(rip_ctx *ctx, const float *stack, int location, int 
 int rip_cal_dark_planes(rip_ctx *ctx, const float *dark1, const float *dark2, const float *dark1_err, const float *dark2_err,
                         const float *cds, int location, int ny, int nx, size_t row_stride, float *dark_slope, float *dark_slope_err,
                         float *read_noise);
-
-/* ---- diagnostics ------------------------------------------------------------------------- */
-/* floating-point options of a context.  "guard_band": relative half-width of the band around the jump
-   threshold inside which the significance is re-evaluated in the reference's exact operation order
-   (default 1e-5; INFINITY = always exact).  Results do not depend on it unless it is set below ~1e-6; it
-   exists so that tests can force either path.  Per context (round 1 had a process-wide setter). */
-int rip_set_option_f64(rip_ctx *ctx, const char *name, double value);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ This is the only door between the Python host code and the HIP kernels.  There i
 fallback: if the library is missing or no MI355X is visible, the calls raise.
 """
 
+import contextlib
 import ctypes as C
 import os
 
@@ -167,6 +168,10 @@ SYMBOLS = {
     "rip_cal_dark_planes": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_size_t, _VP, _VP, _VP]),
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
+    "rip_get_option": (_I, [_VP, C.c_char_p, C.POINTER(_I)]),
+    "rip_get_option_f64": (_I, [_VP, C.c_char_p, c_double_p]),
+    "rip_reset_options": (_I, [_VP]),
+    "rip_option_info": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "rip_last_chain_form": (_I, [_VP]),
     "rip_last_chain_first_group": (_I, [_VP]),
     "rip_last_prepass_gate": (_I, [_VP, C.POINTER(C.c_int)]),
@@ -218,13 +223,26 @@ def chain_form_for(lin_nplanes, ngroups, ipc_dtype=RIP_F32, gain_dtype=RIP_F32):
     return int(load_library().rip_chain_form_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype)))
 
 
+def option_table():
+    """The library's option table (``rip_option_info``) as name -> (default, lowest, highest accepted value); the one f64 option,
+    "guard_band", appears with its values cut to int.  Needs no GPU."""
+    lib, table = load_library(), {}
+    name, d, lo, hi = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+    while lib.rip_option_info(len(table), C.byref(name), C.byref(d), C.byref(lo), C.byref(hi)):
+        table[name.value.decode()] = (d.value, lo.value, hi.value)
+    return table
+
+
 GEOMETRY_FIELDS = ("cols", "nstrips", "live_last", "nr", "rows", "nq", "rows_q", "grid")
 
 
-def chain_geometry_for(lin_nplanes, ngroups, ipc_dtype, ny, nx, ncu, reserve=8, quad_ok=True, gain_dtype=RIP_F32):
+def chain_geometry_for(lin_nplanes, ngroups, ipc_dtype, ny, nx, ncu, reserve=None, quad_ok=True, gain_dtype=RIP_F32):
     """The fused kernel's launch geometry for such a ramp on an (ny, nx) frame and a device of ``ncu`` compute units, as a dict
     with the keys ``GEOMETRY_FIELDS`` (``rip_chain_geometry_for``: ``nq`` > 0 means quad mode), or None where the stage kernels
-    run.  Needs no GPU; ``Context.last_chain_geometry`` tells what a call really used."""
+    run.  ``reserve`` None: the default of the option "chain_reserve".  Needs no GPU; ``Context.last_chain_geometry`` tells
+    what a call really used."""
+    if reserve is None:
+        reserve = option_table()["chain_reserve"][0]
     out = (C.c_int * 8)()
     rc = load_library().rip_chain_geometry_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype), int(ny), int(nx),
                                                int(ncu), int(reserve), int(bool(quad_ok)), out)
@@ -311,6 +329,38 @@ class Context:
     def set_option_f64(self, name, value):
         """floating-point options of this context ("guard_band")"""
         self.check(self.lib.rip_set_option_f64(self.h, name.encode(), float(value)))
+
+    def get_option(self, name):
+        v = C.c_int()
+        self.check(self.lib.rip_get_option(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    def get_option_f64(self, name):
+        v = C.c_double()
+        self.check(self.lib.rip_get_option_f64(self.h, name.encode(), C.byref(v)))
+        return v.value
+
+    def reset_options(self):
+        """every option back to the library's default (``option_table``)"""
+        self.check(self.lib.rip_reset_options(self.h))
+
+    @contextlib.contextmanager
+    def options(self, **values):
+        """``with ctx.options(fused=0, guard_band=float("inf")):`` sets these options for the block and puts back, in reverse
+        order and on an exception too, what they held before.  float values are the f64 options."""
+        calls = {name: ((self.get_option_f64, self.set_option_f64) if isinstance(v, float) else (self.get_option, self.set_option))
+                 for name, v in values.items()}
+        old = []
+        try:
+            for name, v in values.items():
+                get, set_ = calls[name]
+                before = get(name)
+                set_(name, v)
+                old.append((set_, name, before))
+            yield self
+        finally:
+            for set_, name, before in reversed(old):
+                set_(name, before)
 
     def last_chain_form(self):
         """0 = stage kernels, 2 = the fused kernel (last calibrate call; 1 and 3 were the general and wave-private fused kernels of rounds 1-2)."""

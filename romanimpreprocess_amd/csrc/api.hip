@@ -1,6 +1,8 @@
 // C-ABI of libromanhip.so (include/romanhip.h): error text, workspaces, context and options, diagnostics and profiling.
 // Host code only.  The device-resident CALDIR is in caldir.hip, the ramp-fit plans in plan.hip, the chain driver in
 // calibrate.hip and the stage-level entry points in stage.hip; kernels live in the other translation units.
+#include <limits.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -42,6 +44,54 @@ void *rip_ws(rip_ctx *ctx, RipWs slot, size_t bytes) {
     return p;
 }
 
+// ---- the options of a context: one row each.  rip_set_option / rip_get_option (_f64 for the f64 row), rip_reset_options (the
+// values a new context starts with) and rip_option_info all read this table; include/romanhip.h documents the rows.
+struct RipOption {
+    const char *name;
+    double def, lo, hi;      // accepted: lo <= value <= hi (never NaN), anything else is RIP_EINVAL ...
+    bool clamp_lo;           // ... except that a value below lo is stored as lo
+    int rip_ctx::*i;         // where the value lives: an int member,
+    double rip_ctx::*f64;    // or the f64 one
+};
+static const double ANY_LO = INT_MIN, ANY_HI = INT_MAX;   // unchecked
+static const RipOption k_options[] = {
+    {"fused", 1, ANY_LO, ANY_HI, false, &rip_ctx::use_fused, nullptr},
+    {"chain2", 1, ANY_LO, ANY_HI, false, &rip_ctx::use_chain2, nullptr},
+    {"chain_quad", 1, ANY_LO, ANY_HI, false, &rip_ctx::chain_quad, nullptr},
+    {"skip_first", 1, ANY_LO, ANY_HI, false, &rip_ctx::skip_first, nullptr},
+    {"chain_reserve", 8, 0, ANY_HI, true, &rip_ctx::chain_reserve, nullptr},
+    {"prepass_form", -1, -1, 1, false, &rip_ctx::prepass_form, nullptr},
+    {"prepass_gate", 0, 0, 1000000, false, &rip_ctx::prepass_gate, nullptr},
+    {"pink_form", -1, ANY_LO, ANY_HI, false, &rip_ctx::pink_form, nullptr},
+    {"overlap", -1, -1, 1, false, &rip_ctx::overlap_mode, nullptr},
+    {"chain_dbg", 0, ANY_LO, ANY_HI, false, &rip_ctx::chain_dbg, nullptr},
+    {"guard_band", 1e-5, 0, INFINITY, false, nullptr, &rip_ctx::guard_band},
+};
+
+// the row of this name among the int or the f64 options; nullptr (error recorded): no such option there
+static const RipOption *find_option(rip_ctx *ctx, const char *name, bool f64) {
+    for (const RipOption &o : k_options)
+        if (name && (o.f64 != nullptr) == f64 && strcmp(name, o.name) == 0) return &o;
+    (void)rip_fail(ctx, RIP_EINVAL, "unknown option %s", name ? name : "(null)");
+    return nullptr;
+}
+
+static void store_option(rip_ctx *ctx, const RipOption &o, double v) {
+    if (o.f64)
+        ctx->*o.f64 = v;
+    else
+        ctx->*o.i = (int)v;
+}
+
+static int set_option(rip_ctx *ctx, const char *name, bool f64, double value) {
+    const RipOption *o = find_option(ctx, name, f64);
+    if (!o) return RIP_EINVAL;
+    if (o->clamp_lo && value < o->lo) value = o->lo;
+    if (!(value >= o->lo && value <= o->hi)) return rip_fail(ctx, RIP_EINVAL, "%s must be in %g .. %g", o->name, o->lo, o->hi);
+    store_option(ctx, *o, value);
+    return RIP_OK;
+}
+
 extern "C" {
 
 #ifdef RIP_TIMING_BUILD
@@ -69,6 +119,7 @@ int rip_ctx_create(int device_id, rip_ctx **out) {
         return rip_fail(nullptr, RIP_EHIP, "device %d is %s; this library is built for gfx950 (MI355X) only", device_id,
                         prop.gcnArchName);
     rip_ctx *ctx = new rip_ctx();
+    rip_reset_options(ctx);
     ctx->device = device_id;
     ctx->ncu = prop.multiProcessorCount;
     // (queue priorities -- main stream above the second -- and a raised wave priority of the fused kernel were both tried against
@@ -84,12 +135,12 @@ int rip_ctx_create(int device_id, rip_ctx **out) {
     }
     if (hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) != hipSuccess) ctx->stream2 = nullptr;
     if (hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking) != hipSuccess) ctx->stream3 = nullptr;
+    ctx->can_overlap = ctx->stream2 != nullptr;
     for (int i = 0; i < 2 && ctx->stream2; ++i)
         if (hipEventCreateWithFlags(&ctx->ev_tab[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&ctx->ev_done[i], hipEventDisableTiming) != hipSuccess) {
-            ctx->use_overlap = false;
+            ctx->can_overlap = false;
         }
-    if (!ctx->stream2) ctx->use_overlap = false;
     // the words of the pre-pass gate (calibrate.hip); without them, or without the clock that bounds its wait, no gate is queued
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0) ctx->wall_khz = khz;
@@ -155,61 +206,34 @@ void rip_host_free(rip_ctx *ctx, void *p) {
     if (p) (void)hipHostFree(p);
 }
 
-int rip_set_option_f64(rip_ctx *ctx, const char *name, double value) {
-    if (name && strcmp(name, "guard_band") == 0) {
-        if (!(value >= 0.0)) return rip_fail(ctx, RIP_EINVAL, "guard_band must be >= 0 (INFINITY = exact path everywhere)");
-        ctx->guard_band = value;
-        return RIP_OK;
-    }
-    return rip_fail(ctx, RIP_EINVAL, "unknown option %s", name ? name : "(null)");
+int rip_option_info(int index, const char **name, int *def, int *lo, int *hi) {
+    if (index < 0 || index >= (int)(sizeof k_options / sizeof k_options[0])) return 0;
+    const RipOption &o = k_options[index];
+    const auto as_int = [](double v) { return v <= INT_MIN ? INT_MIN : v >= INT_MAX ? INT_MAX : (int)v; };
+    if (name) *name = o.name;
+    if (def) *def = as_int(o.def);
+    if (lo) *lo = as_int(o.lo);
+    if (hi) *hi = as_int(o.hi);
+    return o.f64 ? 2 : 1;
 }
 
-int rip_set_option(rip_ctx *ctx, const char *name, int value) {
-    if (name && strcmp(name, "fused") == 0) {
-        ctx->use_fused = value != 0;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "chain2") == 0) {
-        ctx->use_chain2 = value != 0;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "chain_quad") == 0) {
-        ctx->chain_quad = value != 0;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "skip_first") == 0) {   // 0: every fused launch loads and evaluates group 0 (A/B timing, tests)
-        ctx->skip_first = value != 0;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "chain_reserve") == 0) {
-        ctx->chain_reserve = value < 0 ? 0 : value;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "prepass_form") == 0) {
-        if (value < -1 || value > 1) return rip_fail(ctx, RIP_EINVAL, "prepass_form: -1 (by situation), 0 or 1");
-        ctx->prepass_form = value;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "prepass_gate") == 0) {   // 0: no gate; N > 0: the bound of its wait in microseconds
-        if (value < 0 || value > 1000000) return rip_fail(ctx, RIP_EINVAL, "prepass_gate: 0 (off) or a bound of 1 .. 1000000 microseconds");
-        ctx->prepass_gate = value;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "pink_form") == 0) {
-        ctx->pink_form = value;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "overlap") == 0) {
-        if (value < -1 || value > 1) return rip_fail(ctx, RIP_EINVAL, "overlap: -1 (by situation), 0 or 1");
-        ctx->use_overlap = value != 0 && ctx->stream2 != nullptr;
-        ctx->overlap_mode = value;
-        return RIP_OK;
-    }
-    if (name && strcmp(name, "chain_dbg") == 0) {
-        ctx->chain_dbg = value;
-        return RIP_OK;
-    }
-    return rip_fail(ctx, RIP_EINVAL, "unknown option %s", name ? name : "(null)");
+int rip_reset_options(rip_ctx *ctx) {
+    for (const RipOption &o : k_options) store_option(ctx, o, o.def);
+    return RIP_OK;
+}
+
+int rip_set_option(rip_ctx *ctx, const char *name, int value) { return set_option(ctx, name, false, value); }
+int rip_set_option_f64(rip_ctx *ctx, const char *name, double value) { return set_option(ctx, name, true, value); }
+
+int rip_get_option(rip_ctx *ctx, const char *name, int *value) {
+    const RipOption *o = find_option(ctx, name, false);
+    if (o) *value = ctx->*o->i;
+    return o ? RIP_OK : RIP_EINVAL;
+}
+int rip_get_option_f64(rip_ctx *ctx, const char *name, double *value) {
+    const RipOption *o = find_option(ctx, name, true);
+    if (o) *value = ctx->*o->f64;
+    return o ? RIP_OK : RIP_EINVAL;
 }
 
 // diagnostic builds (-DCH_STAMP): per-phase cycle sums of the fused kernel, summed over waves; clears the buffer

@@ -193,7 +193,7 @@ struct Calibration {
         // drains, and the single-launch form in front of the own ramp is the shorter way: 1.121 against 1.140 ms per ramp at f64
         // ipc4d x 8 groups, profiles/r04_summary.md)
         const bool lds_full = rip_chain_fills_lds(G, c.ipc_dtype) && ctx->use_fused && in->data_dtype == RIP_U16;
-        overlap = do_ref && !host && ctx->use_overlap && (ctx->overlap_mode == 1 || !lds_full);
+        overlap = do_ref && !host && ctx->can_overlap && ctx->overlap_mode != 0 && (ctx->overlap_mode == 1 || !lds_full);
         pre = overlap ? ctx->stream2 : ctx->stream;
         int rc;
         if (do_ref) {

@@ -166,7 +166,6 @@ enum { RIP_GATE_COUNTER = 0, RIP_GATE_GIVEUPS = 32, RIP_GATE_STATE = 33, RIP_GAT
 // option "prepass_gate": the bound of the gate's wait in microseconds, 0 = no gate.  Off by default: the gate does what it was built
 // for (the pre-pass starts 9 us after the fused launch instead of with it) and the fused kernel gains 0.4 %, inside the noise of
 // the benchmark (profiles/prepass_gate.txt).  100 is the bound to try it with: the fused grid is resident within 8 to 19 us.
-#define RIP_GATE_DEFAULT_US 0
 
 struct rip_ctx {   // host-only: no kernel reads it
     int device = 0;
@@ -200,7 +199,7 @@ struct rip_ctx {   // host-only: no kernel reads it
     uint32_t gate_total = 0;
     bool gate_armed = false;
     bool in_batch = false;     // inside rip_calibrate_batch: the second stream carries the uploads, no gate goes on it
-    int prepass_gate = RIP_GATE_DEFAULT_US;
+    int prepass_gate;          // option
     int last_gate = 0;         // the last rip_calibrate queued a gate (rip_last_prepass_gate)
     int wall_khz = 100000;     // rate of wall_clock64(), the clock that bounds the gate's wait
 
@@ -208,25 +207,26 @@ struct rip_ctx {   // host-only: no kernel reads it
     void *ws[RIP_WS_COUNT] = {};   // RipWs
     size_t ws_bytes[RIP_WS_COUNT] = {};
 
-    // ---- options (rip_set_option, rip_set_option_f64)
-    bool use_overlap = true;
-    int overlap_mode = -1;   // -1: by situation (see rip_calibrate), 1: wherever possible
-    bool use_fused = true;   // rip_set_option("fused", 0) forces the stage-by-stage kernels
-    bool use_chain2 = true;  // wave-specialised fused kernel where it applies
-    double guard_band = 1e-5;  // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
-    bool chain_quad = true;     // a last strip of <= 64 live columns in quad mode (chain2_geometry); false: every strip alike (A/B timing)
-    bool skip_first = true;     // the fused kernel's form that skips an excluded first group, where it applies (option "skip_first")
-    int chain_reserve = 8;      // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
+    // ---- options: the values as set, nothing derived.  Names, defaults and ranges are the rows of k_options (api.hip), which
+    // rip_ctx_create applies through rip_reset_options; prepass_gate (above), chain_dbg and pink_form (below) are options too
+    bool can_overlap = false;  // NOT an option: the second stream and its events exist (rip_ctx_create); the overlap needs it
+    int overlap_mode;        // -1: by situation (see rip_calibrate), 0: never, 1: wherever possible
+    int use_fused;           // 0 forces the stage-by-stage kernels
+    int use_chain2;          // wave-specialised fused kernel where it applies
+    double guard_band;       // relative half-width of the exact-order re-evaluation band of the jump test (rip_set_option_f64)
+    int chain_quad;          // a last strip of <= 64 live columns in quad mode (chain2_geometry); 0: every strip alike (A/B timing)
+    int skip_first;          // the fused kernel's form that skips an excluded first group, where it applies
+    int chain_reserve;       // workgroup slots the 256-column fused kernel leaves free (the next ramp's pre-pass runs in them)
     // reference-pixel tables: -1 = by situation (a pre-pass that overlaps the previous ramp's fused kernel: the nine small launches
     // of refpix.hip, which slip into that kernel's tail; a pre-pass in front of its own ramp on the same stream: the single launch
     // of refpix_one.hip where it covers the frame); 0 = refpix.hip always, 1 = refpix_one.hip wherever it covers the frame
-    int prepass_form = -1;
+    int prepass_form;
 
     // ---- diagnostics and profiling
     int last_form = 0;       // diagnostic: how the last rip_calibrate ran (0 stage kernels, 2 the fused kernel; 1 and 3 were the general and the wave-private fused kernels of rounds 1-2)
     int last_first_group = 0;   // diagnostic: 1 = the last fused launch skipped group 0 (rip_last_chain_first_group)
     int last_geo[8] = {};    // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
-    int chain_dbg = 0;       // timing experiments only (option "chain_dbg"): the fused kernel skips phases, results invalid
+    int chain_dbg;           // timing experiments only (option "chain_dbg"): the fused kernel skips phases, results invalid
     unsigned long long *chain_dbg_buf = nullptr;  // 4096 waves x 6 phases (diagnostic builds)
     void *prepass_stamps = nullptr;   // diagnostic: device buffer of 16 clock stamps per workgroup of the single-launch pre-pass
     // per-stage device timing (HIP events on `stream`), see rip_profile_enable / rip_profile_read
@@ -242,7 +242,7 @@ struct rip_ctx {   // host-only: no kernel reads it
     // ---- 1/f frames (pink.hip): transform plan and buffers of the last (length, batch) kept between calls
     void *pink_plan = nullptr, *pink_z = nullptr, *pink_s = nullptr, *pink_tab = nullptr;   // (library plan OR own tables: pink_own)
     bool pink_own = false;
-    int pink_form = -1;   // option "pink_form": 0 = the library's transform for every frame length
+    int pink_form;        // option "pink_form": 0 = the library's transform for every frame length
     hipEvent_t ev_pink = nullptr;   // end of the last 1/f call, on pink_stream: the next call on the OTHER stream waits for it
     hipStream_t pink_stream = nullptr;
     bool ev_pink_valid = false;

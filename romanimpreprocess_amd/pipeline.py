@@ -76,6 +76,12 @@ class Calibrator:
         self.ctx.__dict__.setdefault("_caldir_owner", {})[slot] = owner
         return self.shapes[slot]
 
+    def drop_caldir(self, slot):
+        """Free ``slot`` on the device and forget its frame shape and owner: a later call on it raises KeyError."""
+        self.ctx.drop_caldir(slot)
+        self.shapes.pop(slot, None)
+        self.ctx.__dict__.get("_caldir_owner", {}).pop(slot, None)
+
     def slot_owner(self, slot):
         return self.ctx.__dict__.get("_caldir_owner", {}).get(slot)
 
@@ -88,10 +94,10 @@ class Calibrator:
         nplanes, ipc_dtype, gain_dtype = self.ctx.caldir_dtypes[int(slot)]
         return _native.chain_form_for(nplanes, ngroups, ipc_dtype, gain_dtype)
 
-    def chain_geometry_for(self, slot, ngroups, ncu, reserve=8, quad_ok=True):
+    def chain_geometry_for(self, slot, ngroups, ncu, reserve=None, quad_ok=True):
         """Launch geometry of the fused kernel (``_native.chain_geometry_for``) for a ramp of ``ngroups`` groups on the CALDIR set
         of ``slot`` -- its frame shape and dtypes -- on a device of ``ncu`` compute units; None where the stage kernels run.
-        ``Context.last_chain_geometry`` tells what a call really used."""
+        ``reserve`` None: the default of the option "chain_reserve".  ``Context.last_chain_geometry`` tells what a call really used."""
         if int(slot) not in self.ctx.caldir_dtypes:
             raise ValueError(f"chain_geometry_for: no CALDIR set is loaded in slot {slot}")
         nplanes, ipc_dtype, gain_dtype = self.ctx.caldir_dtypes[int(slot)]

@@ -1,8 +1,12 @@
 """The whole chain (rip_calibrate) on the GPU vs the CPU oracle on seeded synthetic ramps."""
 
+import contextlib
+
 import numpy as np
 import pytest
 import torch  # before libromanhip is loaded: torch brings its own copy of the HIP runtime, and the first one loaded must be the one both use
+from chain_support import (OUT, assert_equal_outputs, assert_oracle, calibrate_resident, chain_context, device_outputs, loaded,
+                           oracle_lines, outputs_to_numpy, to_dev)
 from conftest import assert_same_bits, gpu_context
 
 import oracle
@@ -19,50 +23,35 @@ CASES = [
 ]
 
 
-def _oracle_lines(out, G, nch):
-    """(G, nch, 2) LAPACK (m, c) the oracle used for the science channels."""
-    lines = np.zeros((G, nch, 2))
-    for g in range(G):
-        lines[g] = out["refpix_diag"][g]["channels"][:nch, 2:4]
-    return lines
-
-
 @pytest.mark.parametrize("fused", [1, 0])
 @pytest.mark.parametrize("name,shape,rp,p,gdt,kdt", CASES)
 def test_chain_vs_oracle(name, shape, rp, p, gdt, kdt, fused):
     """fused = 1: the single fused kernel (chain.hip) where the configuration allows it; 0: stage kernels."""
     ny, nx = shape
-    gpu_context().set_option("fused", fused)
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=p, seed=77, gain_dtype=gdt, ipc_dtype=kdt,
                             bias_amplitude=2.0, bad_lin_frac=0.01)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=78, cr_frac=0.02)
     area = 1.0 + 0.01 * np.cos(np.arange(ny * nx, dtype=np.float64).reshape(ny, nx) / 50.0)
     ref = oracle.calibrate_arrays(ramp, cal, area_factor=area)
 
-    cb = pipeline.Calibrator(ctx=gpu_context())
-    cb.load_caldir(3, cal)
-    # (1) with LAPACK's channel lines handed in: everything bit-identical to the oracle
-    lines = _oracle_lines(ref, len(rp), nx // 128)
-    got = cb.calibrate(3, ramp, area_factor=area, want_cube=True, channel_lines=lines)
-    assert_same_bits(got["K"], ref["K"], "K")
-    assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-    assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
-    assert np.count_nonzero(got["pixeldq"] & 4) > 5 and np.count_nonzero(got["pixeldq"] & 2) > 5
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 3, cal) as cb, ctx.options(fused=fused):
+        # (1) with LAPACK's channel lines handed in: everything bit-identical to the oracle
+        lines = oracle_lines(ref, len(rp), nx // 128)
+        got = cb.calibrate(3, ramp, area_factor=area, want_cube=True, channel_lines=lines)
+        assert_same_bits(got["K"], ref["K"], "K")
+        assert_oracle(got, ref, "oracle's lines", cube=True)
+        assert np.count_nonzero(got["pixeldq"] & 4) > 5 and np.count_nonzero(got["pixeldq"] & 2) > 5
 
-    # (2) channel lines fitted on the device: DQ identical, floats within the north-star tolerance
-    got2 = cb.calibrate(3, ramp, area_factor=area)
-    assert_same_bits(got2["groupdq"], ref["groupdq"], "groupdq (device lines)")
-    assert_same_bits(got2["pixeldq"], ref["pixeldq"], "pixeldq (device lines)")
-    # tolerance: 1e-5 relative on the slope (BASELINE.json north star), errors relative to the total error
-    np.testing.assert_allclose(got2["slope"], ref["slope"], rtol=1e-5, atol=1e-7)
-    tot = np.hypot(ref["err_read"], ref["err_poisson"])
-    assert np.all(np.abs(got2["err_read"] - ref["err_read"]) <= 1e-5 * tot + 1e-12)
-    assert np.all(np.abs(got2["err_poisson"] - ref["err_poisson"]) <= 1e-5 * tot + 1e-12)
-    cb.ctx.drop_caldir(3)
-    gpu_context().set_option("fused", 1)
+        # (2) channel lines fitted on the device: DQ identical, floats within the north-star tolerance
+        got2 = cb.calibrate(3, ramp, area_factor=area)
+        assert_same_bits(got2["groupdq"], ref["groupdq"], "groupdq (device lines)")
+        assert_same_bits(got2["pixeldq"], ref["pixeldq"], "pixeldq (device lines)")
+        # tolerance: 1e-5 relative on the slope (BASELINE.json north star), errors relative to the total error
+        np.testing.assert_allclose(got2["slope"], ref["slope"], rtol=1e-5, atol=1e-7)
+        tot = np.hypot(ref["err_read"], ref["err_poisson"])
+        assert np.all(np.abs(got2["err_read"] - ref["err_read"]) <= 1e-5 * tot + 1e-12)
+        assert np.all(np.abs(got2["err_poisson"] - ref["err_poisson"]) <= 1e-5 * tot + 1e-12)
 
 
 def test_stage_subsets_and_f32_input():
@@ -82,39 +71,37 @@ def test_stage_subsets_and_f32_input():
     dark_rate = finish.dark_rate_deconvolved(cal["dark"]["dark_slope"], cal["ipc4d"]["data"], cal["gain"]["data"])
     s, er, ep = finish.finish(s, er, ep, pdq, 4, dark_rate, None, None, None)
 
-    cb = pipeline.Calibrator(ctx=gpu_context())
-    cb.load_caldir(0, cal)
-    r2 = dict(ramp)
-    r2["data"] = full["data"]  # f32 cube, already corrected
-    got = cb.calibrate(0, r2, stages=pipeline.STAGE_RAMPFIT | pipeline.STAGE_DARK)
-    assert_same_bits(got["pixeldq"], pdq, "pixeldq")
-    assert_same_bits(got["groupdq"], rdq, "groupdq")
-    assert_same_bits(got["slope"], s, "slope", zero_sign_ok=True)
-    assert_same_bits(got["err_read"], er, "err_read", zero_sign_ok=True)
-    assert_same_bits(got["err_poisson"], ep, "err_poisson", zero_sign_ok=True)
-    # cube-only sub-chain: refpix + bias + linearity, no fit
-    lines = _oracle_lines(full, len(rp), nx // 128)
-    part = cb.calibrate(0, ramp, stages=pipeline.STAGE_REFPIX | pipeline.STAGE_BIAS | pipeline.STAGE_LIN, want_cube=True,
-                        channel_lines=lines)
-    assert "slope" not in part
-    ref_lin = oracle.calibrate_arrays(ramp, {k: v for k, v in cal.items() if k != "ipc4d"})
-    assert_same_bits(part["cube"], ref_lin["data"], "cube after linearity", zero_sign_ok=True)
+    with loaded(pipeline.Calibrator(ctx=chain_context()), 0, cal) as cb:
+        r2 = dict(ramp)
+        r2["data"] = full["data"]  # f32 cube, already corrected
+        got = cb.calibrate(0, r2, stages=pipeline.STAGE_RAMPFIT | pipeline.STAGE_DARK)
+        assert_same_bits(got["pixeldq"], pdq, "pixeldq")
+        assert_same_bits(got["groupdq"], rdq, "groupdq")
+        assert_same_bits(got["slope"], s, "slope", zero_sign_ok=True)
+        assert_same_bits(got["err_read"], er, "err_read", zero_sign_ok=True)
+        assert_same_bits(got["err_poisson"], ep, "err_poisson", zero_sign_ok=True)
+        # cube-only sub-chain: refpix + bias + linearity, no fit
+        lines = oracle_lines(full, len(rp), nx // 128)
+        part = cb.calibrate(0, ramp, stages=pipeline.STAGE_REFPIX | pipeline.STAGE_BIAS | pipeline.STAGE_LIN, want_cube=True,
+                            channel_lines=lines)
+        assert "slope" not in part
+        ref_lin = oracle.calibrate_arrays(ramp, {k: v for k, v in cal.items() if k != "ipc4d"})
+        assert_same_bits(part["cube"], ref_lin["data"], "cube after linearity", zero_sign_ok=True)
 
 
 def test_bad_arguments():
-    cb = pipeline.Calibrator(ctx=gpu_context())
     rp = synth.READ_PATTERN_6
     cal = synth.make_caldir(32, 128, read_pattern=rp, p_order=3, seed=1)
-    cb.load_caldir(1, cal)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=2)
-    bad = dict(ramp)
-    bad["data"] = ramp["data"][:, :, :64]
-    with pytest.raises(ValueError):
-        cb.calibrate(1, bad)
-    with pytest.raises(ValueError):
-        cb.ctx.drop_caldir(9)
-    with pytest.raises(KeyError):
-        cb.calibrate(7, ramp)  # never loaded
+    with loaded(pipeline.Calibrator(ctx=chain_context()), 1, cal) as cb:
+        bad = dict(ramp)
+        bad["data"] = ramp["data"][:, :, :64]
+        with pytest.raises(ValueError):
+            cb.calibrate(1, bad)
+        with pytest.raises(ValueError):
+            cb.ctx.drop_caldir(9)
+        with pytest.raises(KeyError):
+            cb.calibrate(7, ramp)  # never loaded
 
 
 def test_fused_exact_everywhere_gives_same_flags():
@@ -123,19 +110,13 @@ def test_fused_exact_everywhere_gives_same_flags():
     rp = synth.READ_PATTERN_8
     cal = synth.make_caldir(64, 256, read_pattern=rp, p_order=8, seed=21, bias_amplitude=2.0)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=22, cr_frac=0.05)
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(2, cal)
-    a = cb.calibrate(2, ramp)
-    ctx.set_option_f64("guard_band", float("inf"))
-    try:
-        b = cb.calibrate(2, ramp)
-    finally:
-        ctx.set_option_f64("guard_band", 1e-5)
-    for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-        assert_same_bits(a[k], b[k], k)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 2, cal) as cb:
+        a = cb.calibrate(2, ramp)
+        with ctx.options(guard_band=float("inf")):
+            b = cb.calibrate(2, ramp)
+    assert_equal_outputs(a, b, "approximate + band against exact everywhere")
     assert np.count_nonzero(a["pixeldq"] & 4) > 100
-    cb.ctx.drop_caldir(2)
 
 
 def test_calibrateimage_files_end_to_end(tmp_path):
@@ -163,7 +144,7 @@ def test_calibrateimage_files_end_to_end(tmp_path):
     calio.write_asdf(str(tmp_path / "l1.asdf"), l1)
     config = {"IN": str(tmp_path / "l1.asdf"), "OUT": str(tmp_path / "l2.asdf"), "CALDIR": caldir,
               "JUMP_DETECT_PARS": {"SthreshA": 5.0, "IthreshB": 800.0}, "SLICEOUT": True}
-    cb_files = pipeline.Calibrator(ctx=gpu_context())
+    cb_files = pipeline.Calibrator(ctx=chain_context())
     gen_cal_image.calibrateimage(config, verbose=False, calibrator=cb_files)
     out = calio.read_asdf(config["OUT"])
 
@@ -208,16 +189,9 @@ def test_calibrateimage_files_end_to_end(tmp_path):
 # seams between their column strips / row ranges
 
 
-def _set_form(ctx, form):
-    """2: the fused kernel, 0: stage kernels"""
-    ctx.set_option("fused", 1 if form else 0)
-    ctx.set_option("chain2", 1 if form >= 2 else 0)
-
-
-def _default_form(ctx):
-    """the library's defaults: fused, the specialised kernels where they apply"""
-    ctx.set_option("fused", 1)
-    ctx.set_option("chain2", 1)
+def form_options(form):
+    """the options that ask for kernel form 2 (the fused kernel) or 0 (stage kernels): ``with ctx.options(**form_options(form))``"""
+    return dict(fused=1 if form else 0, chain2=1 if form >= 2 else 0)
 
 
 SPECIALISED = [
@@ -244,8 +218,7 @@ SPECIALISED = [
 def test_specialised_kernel_vs_oracle(name, shape, rp, p, exclude_first, kdt):
     ny, nx = shape
     form = 2
-    ctx = gpu_context()
-    _set_form(ctx, 2)
+    ctx = chain_context()
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=p, seed=91, bias_amplitude=2.0, bad_lin_frac=0.01,
                             ipc_dtype=kdt)
     # degenerate gains: the waves holding them leave the shared-reciprocal division for the division operator
@@ -255,19 +228,12 @@ def test_specialised_kernel_vs_oracle(name, shape, rp, p, exclude_first, kdt):
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=92, cr_frac=0.03)
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal, exclude_first=exclude_first)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(4, cal)
-    lines = _oracle_lines(ref, len(rp), nx // 128)
-    got = cb.calibrate(4, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=lines)
-    assert ctx.last_chain_form() == form, "the requested fused kernel did not run"
-    _default_form(ctx)
-    assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-    assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
+    with loaded(pipeline.Calibrator(ctx=ctx), 4, cal) as cb, ctx.options(**form_options(form)):
+        lines = oracle_lines(ref, len(rp), nx // 128)
+        got = cb.calibrate(4, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=lines)
+        assert ctx.last_chain_form() == form, "the requested fused kernel did not run"
+    assert_oracle(got, ref, "fused kernel", cube=True)
     assert np.count_nonzero(got["pixeldq"] & 4) > 5
-    cb.ctx.drop_caldir(4)
 
 
 @pytest.mark.parametrize("rp,kdt", [(synth.READ_PATTERN_8, np.float32), (synth.READ_PATTERN_8, np.float64),
@@ -281,22 +247,15 @@ def test_fused_forms_agree_across_seams(rp, kdt):
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=31, bias_amplitude=2.0, bad_lin_frac=0.005,
                             ipc_dtype=kdt)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=32, cr_frac=0.02)
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(5, cal)
+    ctx = chain_context()
     outs = []
-    try:
+    with loaded(pipeline.Calibrator(ctx=ctx), 5, cal) as cb:
         for form in (2, 0):
-            _set_form(ctx, form)
-            outs.append(cb.calibrate(5, ramp, want_cube=True))
-            assert ctx.last_chain_form() == form
-    finally:
-        _default_form(ctx)
-    for other, label in ((outs[1], "stage kernels"),):
-        for k in ("cube", "slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-            assert_same_bits(outs[0][k], other[k], f"{k}: wave-specialised vs {label}")
+            with ctx.options(**form_options(form)):
+                outs.append(cb.calibrate(5, ramp, want_cube=True))
+                assert ctx.last_chain_form() == form
+    assert_equal_outputs(outs[0], outs[1], "wave-specialised vs stage kernels", keys=("cube",) + OUT)
     assert np.count_nonzero(outs[0]["pixeldq"] & 4) > 1000 and np.count_nonzero(outs[0]["pixeldq"] & 2) > 100
-    cb.ctx.drop_caldir(5)
 
 
 def test_saturation_flagging_on_device_matches_host_restatement():
@@ -324,25 +283,21 @@ def test_saturation_flagging_on_device_matches_host_restatement():
         h = {"data": ramp["data"], "groupdq": np.zeros(ramp["data"].shape, np.uint8), "pixeldq": mask.copy()}
         saturation.flag_saturation(h, thr, backup=backup, skip_firstn=1, n_pix_grow_sat=1, sat_dq=sdq)
         assert 50 < np.count_nonzero(h["groupdq"][-1] & 2) < 0.5 * ny * nx
-        cb = pipeline.Calibrator(ctx=gpu_context())
-        cb.load_caldir(6, cal)
         r_host = dict(ramp, groupdq=h["groupdq"], pixeldq=h["pixeldq"])
-        a = cb.calibrate(6, r_host)
         r_dev = dict(ramp, groupdq=None, pixeldq=mask)
-        b = cb.calibrate(6, r_dev, flag_saturation=True, saturation_backup=backup)
-        for k in ("groupdq", "pixeldq", "slope", "err_read", "err_poisson"):
-            assert_same_bits(a[k], b[k], f"{k} (backup {backup})")
         # read-pattern rule (groups averaging several reads are compared with threshold * mean(reads) / last read): groups whose
         # later reads alone saturate sit between the diluted and the full threshold -- flagged only with the rule on
         h2 = {"data": ramp["data"], "groupdq": np.zeros(ramp["data"].shape, np.uint8), "pixeldq": mask.copy()}
         saturation.flag_saturation(h2, thr, backup=backup, skip_firstn=1, n_pix_grow_sat=1, sat_dq=sdq, read_pattern=rp)
         more = np.count_nonzero(h2["groupdq"] & 2) - np.count_nonzero(h["groupdq"] & 2)
         assert more > 20, "the synthetic thresholds do not exercise partially saturated groups"
-        c = cb.calibrate(6, r_dev, flag_saturation=True, saturation_backup=backup, saturation_read_pattern=True)
-        d = cb.calibrate(6, dict(ramp, groupdq=h2["groupdq"], pixeldq=h2["pixeldq"]))
-        for k in ("groupdq", "pixeldq", "slope", "err_read", "err_poisson"):
-            assert_same_bits(c[k], d[k], f"{k} (backup {backup}, read-pattern rule)")
-        cb.ctx.drop_caldir(6)
+        with loaded(pipeline.Calibrator(ctx=chain_context()), 6, cal) as cb:
+            a = cb.calibrate(6, r_host)
+            b = cb.calibrate(6, r_dev, flag_saturation=True, saturation_backup=backup)
+            assert_equal_outputs(a, b, f"backup {backup}")
+            c = cb.calibrate(6, r_dev, flag_saturation=True, saturation_backup=backup, saturation_read_pattern=True)
+            d = cb.calibrate(6, dict(ramp, groupdq=h2["groupdq"], pixeldq=h2["pixeldq"]))
+            assert_equal_outputs(c, d, f"backup {backup}, read-pattern rule")
 
 
 FULL_FRAME = [
@@ -366,34 +321,26 @@ def test_full_frame_4096x4096_vs_oracle_and_between_forms(name, rp, kdt, p, orac
     from romanimpreprocess_amd import synth_gpu
 
     n = 4096
-    ctx = gpu_context()
+    ctx = chain_context()
     cb = pipeline.Calibrator(ctx=ctx)
     if oracle_rows < n:
         cal_s = synth_gpu.make_caldir(oracle_rows, n, read_pattern=rp, p_order=p, seed=1002, ipc_dtype=kdt)
         ramp_s = synth_gpu.make_ramp(cal_s, read_pattern=rp, seed=2, cr_frac=0.01)
         ref_s = oracle.calibrate_arrays(ramp_s, cal_s)
-        cb.load_caldir(6, cal_s)
-        _default_form(ctx)
-        got_s = cb.calibrate(6, ramp_s, channel_lines=_oracle_lines(ref_s, len(rp), n // 128))
-        assert ctx.last_chain_form() == 2
-        for k in ("groupdq", "pixeldq", "slope", "err_read", "err_poisson"):
-            assert_same_bits(got_s[k], ref_s[k], f"{k} ({oracle_rows}-row frame)", zero_sign_ok=True)
+        with loaded(cb, 6, cal_s):
+            got_s = cb.calibrate(6, ramp_s, channel_lines=oracle_lines(ref_s, len(rp), n // 128))
+            assert ctx.last_chain_form() == 2
+        assert_oracle(got_s, ref_s, f"{oracle_rows}-row frame")
         assert np.count_nonzero(got_s["pixeldq"] & 4) > 1000
-        cb.ctx.drop_caldir(6)
         del cal_s, ramp_s, ref_s, got_s
     cal = synth_gpu.make_caldir(n, n, read_pattern=rp, p_order=p, seed=1001, ipc_dtype=kdt)
     ramp = synth_gpu.make_ramp(cal, read_pattern=rp, seed=1)
-    cb.load_caldir(6, cal)
-    try:
-        _default_form(ctx)
+    with loaded(cb, 6, cal):
         if oracle_rows == n:
             ref = oracle.calibrate_arrays(ramp, cal)
-            got = cb.calibrate(6, ramp, channel_lines=_oracle_lines(ref, len(rp), n // 128))
+            got = cb.calibrate(6, ramp, channel_lines=oracle_lines(ref, len(rp), n // 128))
             assert ctx.last_chain_form() == 2   # (f64 ipc4d too: with its f64 chains batched the wave-specialised kernel is the faster one)
-            assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-            assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-            for k in ("slope", "err_read", "err_poisson"):
-                assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
+            assert_oracle(got, ref, "full frame")
             del ref
         else:
             got = cb.calibrate(6, ramp)
@@ -403,18 +350,13 @@ def test_full_frame_4096x4096_vs_oracle_and_between_forms(name, rp, kdt, p, orac
         assert np.count_nonzero(ramp["rate"][4:-4, 4:-4] > 100.0) > 200
         outs = []
         for form in (2, 0):
-            _set_form(ctx, form)
-            outs.append(cb.calibrate(6, ramp))
-            assert ctx.last_chain_form() == form
-        for other, label in ((outs[1], "stage kernels"),):
-            for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-                assert_same_bits(outs[0][k], other[k], f"{k}: wave-specialised vs {label}")
+            with ctx.options(**form_options(form)):
+                outs.append(cb.calibrate(6, ramp))
+                assert ctx.last_chain_form() == form
+        assert_equal_outputs(outs[0], outs[1], "wave-specialised vs stage kernels")
         # device-fitted lines against LAPACK's: flags identical, slopes within the north-star tolerance
         assert_same_bits(outs[0]["pixeldq"], got["pixeldq"], "pixeldq (device lines)")
         np.testing.assert_allclose(outs[0]["slope"], got["slope"], rtol=1e-5, atol=1e-7)
-    finally:
-        _default_form(ctx)
-        cb.ctx.drop_caldir(6)
 
 
 def test_preallocated_and_page_locked_host_arrays():
@@ -423,27 +365,25 @@ def test_preallocated_and_page_locked_host_arrays():
     ny, nx = 40, 256
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=3, seed=3)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=4, cr_frac=0.02)
-    cb = pipeline.Calibrator(ctx=gpu_context())
-    cb.load_caldir(7, cal)
-    ref = cb.calibrate(7, ramp)
-    pinned = {k: cb.pinned_empty(v.shape, v.dtype) for k, v in ramp.items() if isinstance(v, np.ndarray)}
-    for k, v in pinned.items():
-        v[...] = ramp[k]
-    out = {k: cb.pinned_empty(ref[k].shape, ref[k].dtype) for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq")}
-    got = cb.calibrate(7, dict(ramp, **pinned), out=out)
-    for k in out:
-        assert got[k] is out[k]
-        assert_same_bits(out[k], ref[k], k)
-    # a groupdq without DO_NOT_USE on the first group: the library sets it on its own copy, the caller's array stays
-    bare = ramp["groupdq"].copy()
-    bare[0] &= np.uint8(0xFE)
-    keep = bare.copy()
-    got2 = cb.calibrate(7, dict(ramp, groupdq=bare))
-    assert np.array_equal(bare, keep)
-    assert_same_bits(got2["slope"], ref["slope"], "slope (first group flagged by the library)")
-    with pytest.raises(ValueError):
-        cb.calibrate(7, ramp, out={"slope": np.empty((ny, nx), np.float64)})
-    cb.ctx.drop_caldir(7)
+    with loaded(pipeline.Calibrator(ctx=chain_context()), 7, cal) as cb:
+        ref = cb.calibrate(7, ramp)
+        pinned = {k: cb.pinned_empty(v.shape, v.dtype) for k, v in ramp.items() if isinstance(v, np.ndarray)}
+        for k, v in pinned.items():
+            v[...] = ramp[k]
+        out = {k: cb.pinned_empty(ref[k].shape, ref[k].dtype) for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq")}
+        got = cb.calibrate(7, dict(ramp, **pinned), out=out)
+        for k in out:
+            assert got[k] is out[k]
+            assert_same_bits(out[k], ref[k], k)
+        # a groupdq without DO_NOT_USE on the first group: the library sets it on its own copy, the caller's array stays
+        bare = ramp["groupdq"].copy()
+        bare[0] &= np.uint8(0xFE)
+        keep = bare.copy()
+        got2 = cb.calibrate(7, dict(ramp, groupdq=bare))
+        assert np.array_equal(bare, keep)
+        assert_same_bits(got2["slope"], ref["slope"], "slope (first group flagged by the library)")
+        with pytest.raises(ValueError):
+            cb.calibrate(7, ramp, out={"slope": np.empty((ny, nx), np.float64)})
 
 
 UNUSUAL = [
@@ -464,17 +404,9 @@ def test_unusual_group_counts_vs_oracle(name, rp, exclude_first):
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=3, seed=61, bias_amplitude=1.0)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=62, cr_frac=0.03)
     ref = oracle.calibrate_arrays(ramp, cal, exclude_first=exclude_first)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(8, cal)
-    got = cb.calibrate(8, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=_oracle_lines(ref, len(rp), nx // 128))
-    assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-    assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
-    cb.ctx.drop_caldir(8)
+    with loaded(pipeline.Calibrator(ctx=chain_context()), 8, cal) as cb:
+        got = cb.calibrate(8, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=oracle_lines(ref, len(rp), nx // 128))
+    assert_oracle(got, ref, "stage kernels", cube=True)
 
 
 @pytest.mark.parametrize("flag_sat", [False, True])
@@ -484,30 +416,27 @@ def test_batch_of_host_ramps_equals_single_calls(flag_sat):
     rp = synth.READ_PATTERN_8
     ny, nx = 72, 256
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=41, bias_amplitude=2.0)
-    cb = pipeline.Calibrator(ctx=gpu_context())
-    cb.load_caldir(2, cal)
-    ramps = []
-    for i in range(5):
-        r = synth.make_ramp(cal, read_pattern=rp, seed=50 + i, cr_frac=0.02)
-        if flag_sat:
-            r["groupdq"] = None
-            r["pixeldq"] = cal["mask"]["dq"].copy()
-        ramps.append(r)
-    kept = {}
-    for rule in ((False, True) if flag_sat else (False,)):
-        singles = [cb.calibrate(2, r, flag_saturation=flag_sat, saturation_read_pattern=rule) for r in ramps]
-        pinned_out = [{k: cb.pinned_empty((ny, nx), np.float32) for k in ("slope", "err_read", "err_poisson")} for _ in ramps]
-        many = cb.calibrate_many(2, ramps, want_groupdq=True, flag_saturation=flag_sat, out=pinned_out, saturation_read_pattern=rule)
-        assert len(many) == len(ramps)
-        for i, (a, b) in enumerate(zip(many, singles)):
-            assert a["slope"] is pinned_out[i]["slope"]
-            for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-                assert_same_bits(a[k], b[k], f"ramp {i}: {k} (read-pattern rule {rule})")
-        kept[rule] = many[0]["groupdq"].copy()
-    if flag_sat:   # the rule does act on these ramps
-        assert np.count_nonzero(kept[False] != kept[True]) > 100
-    assert cb.calibrate_many(2, []) == []
-    cb.ctx.drop_caldir(2)
+    with loaded(pipeline.Calibrator(ctx=chain_context()), 2, cal) as cb:
+        ramps = []
+        for i in range(5):
+            r = synth.make_ramp(cal, read_pattern=rp, seed=50 + i, cr_frac=0.02)
+            if flag_sat:
+                r["groupdq"] = None
+                r["pixeldq"] = cal["mask"]["dq"].copy()
+            ramps.append(r)
+        kept = {}
+        for rule in ((False, True) if flag_sat else (False,)):
+            singles = [cb.calibrate(2, r, flag_saturation=flag_sat, saturation_read_pattern=rule) for r in ramps]
+            pinned_out = [{k: cb.pinned_empty((ny, nx), np.float32) for k in ("slope", "err_read", "err_poisson")} for _ in ramps]
+            many = cb.calibrate_many(2, ramps, want_groupdq=True, flag_saturation=flag_sat, out=pinned_out, saturation_read_pattern=rule)
+            assert len(many) == len(ramps)
+            for i, (a, b) in enumerate(zip(many, singles)):
+                assert a["slope"] is pinned_out[i]["slope"]
+                assert_equal_outputs(a, b, f"ramp {i} (read-pattern rule {rule})")
+            kept[rule] = many[0]["groupdq"].copy()
+        if flag_sat:   # the rule does act on these ramps
+            assert np.count_nonzero(kept[False] != kept[True]) > 100
+        assert cb.calibrate_many(2, []) == []
 
 
 @pytest.mark.parametrize("inputs_complete", [True, False])
@@ -516,24 +445,14 @@ def test_back_to_back_device_calls_without_sync(flag_sat, inputs_complete):
     """Different device-resident ramps issued back to back with no synchronisation in between (the reference-pixel pre-pass and
     the saturation pass of call n+1 run ahead on the second stream while the chain of call n is still reading ITS tables and
     flag copies: they are double-buffered by call parity, calibrate.hip): results must equal those of synchronised single calls."""
-    dev = torch.device("cuda", 0)
     rp = synth.READ_PATTERN_8
     ny, nx = 1024, 1024
     cal, _ = synth.make_tiled_inputs(ny, nx, read_pattern=rp, p_order=8, seed=3, strip_rows=64)
     cal = dict(cal)
     thr = np.full((ny, nx), 50000.0, np.float32)
     cal["saturation"] = {"data": thr, "dq": np.zeros((ny, nx), np.uint32)}
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(9, cal)
+    cb = pipeline.Calibrator(ctx=chain_context())
     pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-    def to_dev(a):
-        a = np.ascontiguousarray(a)
-        view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-        return torch.from_numpy(a.view(view) if view else a).to(dev)
-
     n = 5
     ramps = []
     for i in range(n):
@@ -543,18 +462,13 @@ def test_back_to_back_device_calls_without_sync(flag_sat, inputs_complete):
         # distinct reference-output levels: the row corrections of consecutive ramps differ by much more than rounding
         a33 = (r["amp33"].astype(np.int32) + 40 * i * (np.arange(ny)[None, :, None] % 7)).astype(np.uint16)
         ramps.append([to_dev(r["data"]), to_dev(a33), None if flag_sat else to_dev(g), to_dev(r["pixeldq"])])
-    outs = [[torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] +
-            [torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((8, ny, nx), dtype=torch.uint8, device=dev)]
-            for _ in range(2 * n)]
+    outs = [device_outputs(8, ny, nx) for _ in range(2 * n)]
     torch.cuda.synchronize()
 
     def call(i, o):
-        t = ramps[i]
-        cb.calibrate_device(9, pid, 8, t[0].data_ptr(), True, t[1].data_ptr(), None if t[2] is None else t[2].data_ptr(),
-                            t[3].data_ptr(), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(),
-                            flag_saturation=flag_sat, inputs_complete=inputs_complete)   # True: the pre-pass runs ahead
+        calibrate_resident(cb, 9, pid, 8, ramps[i], o, flag_saturation=flag_sat, inputs_complete=inputs_complete)   # True: the pre-pass runs ahead
 
-    try:
+    with loaded(cb, 9, cal):
         for i in range(n):          # reference: one call at a time
             call(i, outs[i])
             cb.synchronize()
@@ -567,29 +481,18 @@ def test_back_to_back_device_calls_without_sync(flag_sat, inputs_complete):
                     assert torch.equal(outs[i][k], outs[n + i][k]), f"ramp {i} {name}: queued call differs (repeat {rep})"
         # the ramps do differ from one another (otherwise the test could not see a stale table)
         assert not torch.equal(outs[0][0], outs[1][0])
-    finally:
-        cb.ctx.drop_caldir(9)
 
 
+@contextlib.contextmanager
 def _small_resident_set(slot, n, ny=512, nx=512, sat=True):
-    """a CALDIR set in `slot` and n different device-resident ramps (tensors: data, amp33, groupdq, pixeldq)"""
-    dev = torch.device("cuda", 0)
+    """a CALDIR set in `slot` (dropped on the way out) and n different device-resident ramps (tensors: data, amp33, groupdq, pixeldq)"""
     rp = synth.READ_PATTERN_8
     cal, _ = synth.make_tiled_inputs(ny, nx, read_pattern=rp, p_order=8, seed=3, strip_rows=64)
     cal = dict(cal)
     if sat:
         cal["saturation"] = {"data": np.full((ny, nx), 50000.0, np.float32), "dq": np.zeros((ny, nx), np.uint32)}
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(slot, cal)
+    cb = pipeline.Calibrator(ctx=chain_context())
     pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-    def to_dev(a):
-        a = np.ascontiguousarray(a)
-        view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-        return torch.from_numpy(a.view(view) if view else a).to(dev)
-
     ramps = []
     for i in range(n):
         _, r = synth.make_tiled_inputs(ny, nx, read_pattern=rp, p_order=8, seed=3, strip_rows=64, ramp_seed=200 + i)
@@ -598,12 +501,9 @@ def _small_resident_set(slot, n, ny=512, nx=512, sat=True):
         a33 = (r["amp33"].astype(np.int32) + 40 * i * (np.arange(ny)[None, :, None] % 7)).astype(np.uint16)
         ramps.append([to_dev(r["data"]), to_dev(a33), to_dev(g), to_dev(r["pixeldq"])])
 
-    def outputs():
-        return [torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] + [
-            torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((8, ny, nx), dtype=torch.uint8, device=dev)]
-
     torch.cuda.synchronize()
-    return cb, pid, ramps, outputs
+    with loaded(cb, slot, cal):
+        yield cb, pid, ramps, lambda: device_outputs(8, ny, nx)
 
 
 def test_mixed_overlap_modes_back_to_back():
@@ -612,23 +512,21 @@ def test_mixed_overlap_modes_back_to_back():
     double-buffered tables and flag copies and leaves its completion event, so a following overlapped call can neither reuse
     nor overwrite buffers a queued kernel still reads (round-2 advisor finding on calibrate.hip)."""
     n = 6
-    cb, pid, ramps, outputs = _small_resident_set(9, n)
     no_ref = pipeline.STAGE_ALL & ~pipeline.STAGE_REFPIX
     # (overlap option, stage mask, flag saturation on the device) per call
     modes = [(1, pipeline.STAGE_ALL, True), (0, pipeline.STAGE_ALL, True), (1, pipeline.STAGE_ALL, True),
              (1, no_ref, True), (1, pipeline.STAGE_ALL, True), (0, no_ref, False)]
 
-    def call(i, o):
-        t = ramps[i]
-        ov, stages, fs = modes[i]
-        cb.ctx.set_option("overlap", ov)
-        cb.calibrate_device(9, pid, 8, t[0].data_ptr(), True, t[1].data_ptr(), None if fs else t[2].data_ptr(), t[3].data_ptr(),
-                            o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), stages=stages,
-                            flag_saturation=fs, inputs_complete=True)
+    with _small_resident_set(9, n) as (cb, pid, ramps, outputs):
+        def call(i, o):
+            t = ramps[i]
+            ov, stages, fs = modes[i]
+            with cb.ctx.options(overlap=ov):
+                calibrate_resident(cb, 9, pid, 8, t[:2] + [None if fs else t[2], t[3]], o, stages=stages, flag_saturation=fs,
+                                   inputs_complete=True)
 
-    ref = [outputs() for _ in range(n)]
-    got = [outputs() for _ in range(n)]
-    try:
+        ref = [outputs() for _ in range(n)]
+        got = [outputs() for _ in range(n)]
         for i in range(n):
             call(i, ref[i])
             cb.synchronize()
@@ -640,9 +538,6 @@ def test_mixed_overlap_modes_back_to_back():
                 for k, name in enumerate(("slope", "err_read", "err_poisson", "pixeldq", "groupdq")):
                     assert torch.equal(ref[i][k], got[i][k]), f"call {i} {modes[i]} {name}: queued call differs (repeat {rep})"
         assert not torch.equal(ref[0][0], ref[2][0])
-    finally:
-        cb.ctx.set_option("overlap", 1)
-        cb.ctx.drop_caldir(9)
 
 
 @pytest.mark.parametrize("producer", ["side_stream_event", "library_stream_default"])
@@ -651,16 +546,15 @@ def test_inputs_written_by_queued_work_no_sync(producer):
     on a torch side stream, guarded by rip_ramp_desc::ready_event, or on rip_stream() itself with the default
     (stream-ordered) contract.  No host synchronisation anywhere; the result must be that of the synchronised call -- the
     second-stream pre-pass would otherwise read the stale previous contents and produce other row corrections."""
-    cb, pid, ramps, outputs = _small_resident_set(9, 3, sat=False)
     dev = torch.device("cuda", 0)
-    ref, got = outputs(), outputs()
-    stale, fresh = ramps[0], ramps[1]
-    work = [torch.empty_like(stale[0]), torch.empty_like(stale[1])]   # the buffers the calls read
-    junk = torch.empty((4096, 4096), dtype=torch.float32, device=dev)
-    try:
+    with _small_resident_set(9, 3, sat=False) as (cb, pid, ramps, outputs):
+        ref, got = outputs(), outputs()
+        stale, fresh = ramps[0], ramps[1]
+        work = [torch.empty_like(stale[0]), torch.empty_like(stale[1])]   # the buffers the calls read
+        junk = torch.empty((4096, 4096), dtype=torch.float32, device=dev)
+
         def call(o, **kw):
-            cb.calibrate_device(9, pid, 8, work[0].data_ptr(), True, work[1].data_ptr(), fresh[2].data_ptr(), fresh[3].data_ptr(),
-                                o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr(), **kw)
+            calibrate_resident(cb, 9, pid, 8, work + fresh[2:], o, **kw)
 
         work[0].copy_(fresh[0]); work[1].copy_(fresh[1])
         torch.cuda.synchronize()
@@ -690,32 +584,20 @@ def test_inputs_written_by_queued_work_no_sync(producer):
             torch.cuda.synchronize()
             for k, name in enumerate(("slope", "err_read", "err_poisson", "pixeldq", "groupdq")):
                 assert torch.equal(ref[k], got[k]), f"{name}: inputs written by queued work were read too early (repeat {rep})"
-    finally:
-        cb.ctx.drop_caldir(9)
 
 
 def test_several_caldir_slots_resident_and_interleaved():
     """BASELINE config 4 in small: several CALDIR sets (SCAs) resident at once, ramps of different (filter, SCA) items issued
     interleaved and back to back, every result checked against the oracle run with that item's own calibration set."""
-    dev = torch.device("cuda", 0)
     rp = synth.READ_PATTERN_8
     ny, nx = 64, 256
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
+    cb = pipeline.Calibrator(ctx=chain_context())
     scas = (3, 7, 12, 18)
     cals = {}
     for sca in scas:
         kdt = np.float64 if sca == 12 else np.float32   # one production-style set with f64 ipc4d among them
         cals[sca] = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=5000 + sca, ipc_dtype=kdt, bias_amplitude=1.0)
-        cb.load_caldir(sca, cals[sca])
     pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-    def to_dev(a):
-        a = np.ascontiguousarray(a)
-        view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-        return torch.from_numpy(a.view(view) if view else a).to(dev)
-
     items = [(f, s) for f in range(3) for s in scas]    # (filter, SCA), seed 1000 * filter + sca (SURVEY 8d)
     order = [items[i] for i in (0, 5, 10, 3, 4, 9, 2, 7, 8, 1, 6, 11)]   # never the same slot twice in a row
     refs, ins, outs = {}, {}, {}
@@ -725,29 +607,25 @@ def test_several_caldir_slots_resident_and_interleaved():
         g = r["groupdq"].copy()
         g[0] |= 1
         ins[(f, s)] = [to_dev(r["data"]), to_dev(r["amp33"]), to_dev(g), to_dev(r["pixeldq"])]
-        outs[(f, s)] = [torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] + [
-            torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((8, ny, nx), dtype=torch.uint8, device=dev)]
+        outs[(f, s)] = device_outputs(8, ny, nx)
     torch.cuda.synchronize()
-    try:
+    with contextlib.ExitStack() as slots:
+        for sca in scas:
+            slots.enter_context(loaded(cb, sca, cals[sca]))
         for f, s in order:      # all queued, one synchronisation at the end
-            t, o = ins[(f, s)], outs[(f, s)]
-            cb.calibrate_device(s, pid, 8, t[0].data_ptr(), True, t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr())
+            calibrate_resident(cb, s, pid, 8, ins[(f, s)], outs[(f, s)])
         cb.synchronize()
         for key in items:
-            ref, o = refs[key], outs[key]
+            ref, o = refs[key], outputs_to_numpy(outs[key])
             # channel lines are fitted on the device here: flags identical, floats within the north-star tolerance
-            assert_same_bits(o[3].cpu().numpy().view(np.uint32), ref["pixeldq"], f"pixeldq of item {key}")
-            assert_same_bits(o[4].cpu().numpy(), ref["groupdq"], f"groupdq of item {key}")
-            np.testing.assert_allclose(o[0].cpu().numpy(), ref["slope"], rtol=1e-5, atol=1e-7)
+            assert_same_bits(o["pixeldq"], ref["pixeldq"], f"pixeldq of item {key}")
+            assert_same_bits(o["groupdq"], ref["groupdq"], f"groupdq of item {key}")
+            np.testing.assert_allclose(o["slope"], ref["slope"], rtol=1e-5, atol=1e-7)
             tot = np.hypot(ref["err_read"], ref["err_poisson"])
-            assert np.all(np.abs(o[1].cpu().numpy() - ref["err_read"]) <= 1e-5 * tot + 1e-12)
-            assert np.all(np.abs(o[2].cpu().numpy() - ref["err_poisson"]) <= 1e-5 * tot + 1e-12)
+            assert np.all(np.abs(o["err_read"] - ref["err_read"]) <= 1e-5 * tot + 1e-12)
+            assert np.all(np.abs(o["err_poisson"] - ref["err_poisson"]) <= 1e-5 * tot + 1e-12)
         # the items do differ (a result computed against the wrong slot would not pass the checks above)
         assert not np.array_equal(refs[(0, 3)]["slope"], refs[(0, 7)]["slope"])
-    finally:
-        for sca in scas:
-            cb.ctx.drop_caldir(sca)
 
 
 @pytest.mark.parametrize("form", [2, 0])
@@ -770,19 +648,13 @@ def test_read_file_without_reference_output(form):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")  # numpy's RankWarning of the degenerate fit
             ref = oracle.calibrate_arrays(ramp, cal)
-    ctx = gpu_context()
-    _set_form(ctx, form)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(10, cal)
-    try:
-        got = cb.calibrate(10, ramp, want_cube=True, channel_lines=_oracle_lines(ref, len(rp), nx // 128))
-        assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-        assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-        for k in ("slope", "err_read", "err_poisson"):
-            assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
-    finally:
-        _default_form(ctx)
-        cb.ctx.drop_caldir(10)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 10, cal) as cb, ctx.options(**form_options(form)):
+        got = cb.calibrate(10, ramp, want_cube=True, channel_lines=oracle_lines(ref, len(rp), nx // 128))
+    assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
+    assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
+    for k in ("slope", "err_read", "err_poisson"):
+        assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
 
 
 @pytest.mark.parametrize("clash", [False, True])
@@ -809,27 +681,19 @@ def test_flat_flags_and_dark_dq_reach_pixeldq_through_the_merged_flag_word(clash
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=93, cr_frac=0.02)
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(11, cal)
-    try:
-        got = cb.calibrate(11, ramp, channel_lines=_oracle_lines(ref, len(rp), nx // 128))
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 11, cal) as cb:
+        got = cb.calibrate(11, ramp, channel_lines=oracle_lines(ref, len(rp), nx // 128))
         form = ctx.last_chain_form()
         assert (form != 2) if clash else (form == 2), form
-        assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-        assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-        for k in ("slope", "err_read", "err_poisson"):
-            assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
+        assert_oracle(got, ref, "merged flag word")
         # the flags are there: dark dq on active pixels only, flat and gain flags
         assert (got["pixeldq"][4:-4, 4:-4] & ddq[4:-4, 4:-4] == ddq[4:-4, 4:-4]).all() and not (got["pixeldq"][0, 0] & (1 << 9))
         assert got["pixeldq"][10, 10] & (1 << 18) and got["pixeldq"][12, 12] & (1 << 19)
         # a sub-chain without the flat stage: the flat flags must not appear (another merged word, or none)
-        no_flat = cb.calibrate(11, ramp, stages=pipeline.STAGE_ALL & ~pipeline.STAGE_FLAT, channel_lines=_oracle_lines(ref, len(rp), nx // 128))
+        no_flat = cb.calibrate(11, ramp, stages=pipeline.STAGE_ALL & ~pipeline.STAGE_FLAT, channel_lines=oracle_lines(ref, len(rp), nx // 128))
         assert not (no_flat["pixeldq"][10, 10] & (1 << 18)) and (no_flat["pixeldq"][4:-4, 4:-4] & ddq[4:-4, 4:-4] == ddq[4:-4, 4:-4]).all()
-        no_dark = cb.calibrate(11, ramp, stages=pipeline.STAGE_ALL & ~pipeline.STAGE_DARK, channel_lines=_oracle_lines(ref, len(rp), nx // 128))
+        no_dark = cb.calibrate(11, ramp, stages=pipeline.STAGE_ALL & ~pipeline.STAGE_DARK, channel_lines=oracle_lines(ref, len(rp), nx // 128))
         assert no_dark["pixeldq"][10, 10] & (1 << 18)
         sel = (ddq[4:-4, 4:-4] != 0) & ((ref["pixeldq"][4:-4, 4:-4] & ~ddq[4:-4, 4:-4]) == (no_dark["pixeldq"][4:-4, 4:-4]))
         assert sel.sum() > 10     # pixels whose only extra flags were the dark's: gone without the dark stage
-    finally:
-        cb.ctx.drop_caldir(11)

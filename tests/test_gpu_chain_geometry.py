@@ -14,40 +14,18 @@ At 512 / 768 columns the quad strip emits two science columns and the four refer
 saturate: a band of bright rates over the last science columns (200 .. 60000 DN/s down the rows) and a cosmic-ray fraction of 5 %
 put jumps and first saturations at every group there, and every case checks the ORACLE's output for them before any GPU call."""
 
-from functools import lru_cache
-
 import numpy as np
 import pytest
 import torch  # before libromanhip is loaded: torch brings its own copy of the HIP runtime, and the first one loaded must be the one both use
-from conftest import assert_same_bits, gpu_context
-from test_gpu_chain_groups import _oracle_lines, read_pattern
+from chain_support import (F32, F64, assert_equal_outputs, assert_oracle, band_conditions, calibrate_resident, chain_context, device_cus,
+                           device_outputs, find_height, geometry, inputs, is_quad, loaded, make_band_ramp, outputs_to_numpy,
+                           quad_columns, ramp_to_dev)
 
-import oracle
 from romanimpreprocess_amd import _native, pipeline, synth
 
 pytestmark = pytest.mark.gpu
 
-JUMP, SAT = 4, 2
-F32, F64 = np.float32, np.float64
-MAX_NY = 1600
-DEFAULT_RESERVE = 8
 SLOT = 7
-
-
-def device_cus():
-    return int(torch.cuda.get_device_properties(0).multi_processor_count)
-
-
-def geometry(G, kdt, ny, nx, ncu, reserve=DEFAULT_RESERVE, quad_ok=True):
-    return _native.chain_geometry_for(9, G, _native.RIP_F64 if kdt == F64 else _native.RIP_F32, ny, nx, ncu, reserve, quad_ok)
-
-
-def find_height(ny0, step, has_property, what, lo=16):
-    """ny0 where it has the property (the shapes are designed for 256 CUs), else the first height of the search that has it"""
-    for ny in [ny0] + list(range(lo, MAX_NY + 1, step)):
-        if has_property(ny):
-            return ny
-    raise AssertionError(f"no height up to {MAX_NY} rows gives {what} on this device ({device_cus()} CUs)")
 
 
 def last_rows(ny, rows):
@@ -55,101 +33,44 @@ def last_rows(ny, rows):
     return ny - (-(-ny // rows) - 1) * rows
 
 
-def quad_columns(g, nx):
-    """the science columns the quad workgroups emit: lanes 2 .. live-3 of the last strip's window, short of the 4 reference columns"""
-    return slice((g["nstrips"] - 1) * (g["cols"] - 4) + 2, nx - 4)
-
-
-# ---- inputs: built once per (G, dtype, shape, order, start), shared by the cases that use the same
-@lru_cache(maxsize=2)
-def inputs(G, k64, ny, nx, p, exclude_first, seed=31):
-    rp = read_pattern(G)
-    cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=p, seed=seed, bias_amplitude=2.0, bad_lin_frac=0.005,
-                            ipc_dtype=F64 if k64 else F32)
-    ramp = make_band_ramp(cal, rp, ny, nx, seed + 1)
-    with np.errstate(all="ignore"):
-        ref = oracle.calibrate_arrays(ramp, cal, exclude_first=exclude_first)
-    return rp, cal, ramp, ref, _oracle_lines(ref, G, nx // 128)
-
-
-def make_band_ramp(cal, rp, ny, nx, seed):
-    """sources as everywhere, plus the bright band over the last 24 science columns"""
-    rate = synth.make_rate_image(ny, nx, seed)
-    band = 200.0 * 300.0 ** ((np.arange(ny) % 97) / 96.0)
-    rate[4:ny - 4, nx - 28:nx - 4] += band[4:ny - 4, None]
-    return synth.make_ramp(cal, read_pattern=rp, seed=seed, cr_frac=0.05, saturation_backup=0, rate=rate)
-
-
-def band_conditions(ref, G, cols):
-    """the oracle's own output, on the science columns `cols`: jumps, and first saturations at every group"""
-    q = ref["groupdq"][:, :, cols]
-    njump = np.count_nonzero(ref["pixeldq"][:, cols] & JUMP)
-    assert njump >= 10, f"{njump} jump pixels in the oracle's output on columns {cols}"
-    for g in range(1, G):
-        n = np.count_nonzero((q[g] & SAT) & ~(q[g - 1] & SAT))
-        assert n >= 10, f"{n} pixels first saturate at group {g} in the oracle's output on columns {cols}"
-
-
 # ---- one case: (a) the branch, (b) the oracle, (c) stage kernels and the uniform grid
 KEYS = ("cube", "groupdq", "pixeldq", "slope", "err_read", "err_poisson")
 
 
-def set_defaults(ctx):
-    ctx.set_option("fused", 1)
-    ctx.set_option("chain2", 1)
-    ctx.set_option("chain_quad", 1)
-    ctx.set_option("chain_reserve", DEFAULT_RESERVE)
-
-
-def assert_oracle_bits(got, ref, what):
-    assert_same_bits(got["cube"], ref["data"], f"{what}: corrected cube", zero_sign_ok=True)
-    assert_same_bits(got["groupdq"], ref["groupdq"], f"{what}: groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], f"{what}: pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], f"{what}: {k}", zero_sign_ok=True)
-
-
-def run_case(G, kdt, ny, nx, p, exclude_first, want, want_uniform=None, reserves=(DEFAULT_RESERVE,)):
-    """`want(g)` / `want_uniform(g)`: the property the geometry of the default / the chain_quad = 0 launch must have"""
+def run_case(G, kdt, ny, nx, p, exclude_first, want, want_uniform=None, reserves=None):
+    """`want(g)` / `want_uniform(g)`: the property the geometry of the default / the chain_quad = 0 launch must have;
+    `reserves`: the values of "chain_reserve" the fused kernel runs with (None: the library's default alone)"""
     ncu = device_cus()
     rp, cal, ramp, ref, lines = inputs(G, kdt == F64, ny, nx, p, exclude_first)
     g0 = geometry(G, kdt, ny, nx, ncu)
     band_conditions(ref, G, quad_columns(g0, nx) if g0["nq"] else slice(nx - 28, nx - 4))
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
+    ctx = chain_context()
+    reserves = reserves or (ctx.get_option("chain_reserve"),)
     kw = dict(exclude_first=exclude_first, want_cube=True, channel_lines=lines)
-    try:
-        set_defaults(ctx)
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         seen = []
         for reserve in reserves:
-            ctx.set_option("chain_reserve", reserve)
-            fused = cb.calibrate(SLOT, ramp, **kw)
+            with ctx.options(chain_reserve=reserve):
+                fused = cb.calibrate(SLOT, ramp, **kw)
             assert ctx.last_chain_form() == 2, "the fused kernel did not run"
             g = ctx.last_chain_geometry()
             assert g == geometry(G, kdt, ny, nx, ncu, reserve), "the launch and the query disagree"
             assert g == cb.chain_geometry_for(SLOT, G, ncu, reserve)
             assert want(g), f"not the intended branch: {g}"
             seen.append(g)
-            assert_oracle_bits(fused, ref, f"reserve {reserve}")
-        set_defaults(ctx)
-        ctx.set_option("chain_quad", 0)
-        uniform = cb.calibrate(SLOT, ramp, **kw)
+            assert_oracle(fused, ref, f"reserve {reserve}", cube=True)
+        with ctx.options(chain_quad=0):
+            uniform = cb.calibrate(SLOT, ramp, **kw)
         assert ctx.last_chain_form() == 2
         u = ctx.last_chain_geometry()
         assert u == geometry(G, kdt, ny, nx, ncu, quad_ok=False) and u["nq"] == 0 and u["rows_q"] == 0, u
         assert want_uniform is None or want_uniform(u), f"not the intended uniform grid: {u}"
-        set_defaults(ctx)
-        ctx.set_option("chain2", 0)
-        stages = cb.calibrate(SLOT, ramp, **kw)
+        with ctx.options(chain2=0):
+            stages = cb.calibrate(SLOT, ramp, **kw)
         assert ctx.last_chain_form() == 0
         assert ctx.last_chain_geometry() == dict.fromkeys(_native.GEOMETRY_FIELDS, 0)
-    finally:
-        set_defaults(ctx)
-        cb.ctx.drop_caldir(SLOT)
-    for k in KEYS:
-        assert_same_bits(fused[k], stages[k], f"{k}: fused vs stage kernels")
-        assert_same_bits(fused[k], uniform[k], f"{k}: fused vs fused on the uniform grid")
+    assert_equal_outputs(fused, stages, "fused vs stage kernels", keys=KEYS)
+    assert_equal_outputs(fused, uniform, "fused vs fused on the uniform grid", keys=KEYS)
     return seen
 
 
@@ -178,10 +99,6 @@ def _quad_cases():
             for i, (G, kdt, ny, nx, live) in enumerate(QUAD)]
 
 
-def is_quad(g, live=None):
-    return g is not None and g["nq"] > 0 and g["rows_q"] > 0 and (live is None or g["live_last"] == live)
-
-
 @pytest.mark.parametrize("G,kdt,ny0,nx,live,p,exclude_first", _quad_cases())
 def test_quad_mode_on_every_form(G, kdt, ny0, nx, live, p, exclude_first):
     ncu = device_cus()
@@ -200,13 +117,14 @@ def test_reserve_changes_the_geometry_not_the_bits():
     G, kdt, nx = 8, F32, 512
     ncu = device_cus()
     slots = 2 * ncu
-    reserves = (0, DEFAULT_RESERVE, slots - 12, slots + 5)
+    default_reserve = _native.option_table()["chain_reserve"][0]
+    reserves = (0, default_reserve, slots - 12, slots + 5)
     ny = find_height(1376, 8, lambda ny: all(is_quad(geometry(G, kdt, ny, nx, ncu, r), 8) for r in reserves), "quad mode at every reserve")
     p, exclude_first = _quad_cases()[-1].values[5:]   # (the inputs of the case above)
     seen = run_case(G, kdt, ny, nx, p, exclude_first, lambda g: is_quad(g, 8), reserves=reserves)
     assert seen[3] == seen[0], "the second pass searches without the reserve"
     assert seen[2] != seen[0] and seen[2]["grid"] <= 12 and seen[2]["rows"] > seen[0]["rows"] and seen[2]["rows_q"] > seen[0]["rows_q"]
-    assert seen[1]["grid"] <= slots - DEFAULT_RESERVE
+    assert seen[1]["grid"] <= slots - default_reserve
 
 
 # ---- 3. ragged rows: heights that are no multiple of the range length
@@ -274,58 +192,32 @@ def _entry_inputs():
 def test_batch_equals_single_calls_in_quad_mode():
     G, ny, nx, rp, cal, ramp = _entry_inputs()
     ramps = [ramp, make_band_ramp(cal, rp, ny, nx, 57)]
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
-    try:
-        set_defaults(ctx)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         singles = []
         for r in ramps:
             singles.append(cb.calibrate(SLOT, r))
             assert ctx.last_chain_form() == 2 and is_quad(ctx.last_chain_geometry(), 8)
         many = cb.calibrate_many(SLOT, ramps, want_groupdq=True)
         assert ctx.last_chain_form() == 2 and is_quad(ctx.last_chain_geometry(), 8)
-    finally:
-        set_defaults(ctx)
-        cb.ctx.drop_caldir(SLOT)
     assert len(many) == 2
     for i, (a, b) in enumerate(zip(many, singles)):
-        for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-            assert_same_bits(a[k], b[k], f"ramp {i}: {k}")
+        assert_equal_outputs(a, b, f"ramp {i}")
     assert not np.array_equal(singles[0]["slope"], singles[1]["slope"])
 
 
 def test_device_resident_calls_equal_host_call_in_quad_mode():
-    dev = torch.device("cuda", 0)
     G, ny, nx, rp, cal, ramp = _entry_inputs()
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
-    try:
-        set_defaults(ctx)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         host = cb.calibrate(SLOT, ramp)
         assert ctx.last_chain_form() == 2 and is_quad(ctx.last_chain_geometry(), 8)
         pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-        def to_dev(a):
-            a = np.ascontiguousarray(a)
-            view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-            return torch.from_numpy(a.view(view) if view else a).to(dev)
-
-        t = [to_dev(ramp[k]) for k in ("data", "amp33", "groupdq", "pixeldq")]
-        o = [torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] + \
-            [torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((G, ny, nx), dtype=torch.uint8, device=dev)]
+        t, o = ramp_to_dev(ramp), device_outputs(G, ny, nx)
         torch.cuda.synchronize()
         for _ in range(2):   # back to back: the second call's pre-pass is queued while the first call's kernel runs
-            cb.calibrate_device(SLOT, pid, G, t[0].data_ptr(), True, t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr())
+            calibrate_resident(cb, SLOT, pid, G, t, o)
         cb.synchronize()
         assert ctx.last_chain_form() == 2 and is_quad(ctx.last_chain_geometry(), 8)
-        got = [x.cpu().numpy() for x in o]
-    finally:
-        set_defaults(ctx)
-        cb.ctx.drop_caldir(SLOT)
-    for k, name in enumerate(("slope", "err_read", "err_poisson")):
-        assert_same_bits(got[k], host[name], name)
-    assert_same_bits(got[3].view(np.uint32), host["pixeldq"], "pixeldq")
-    assert_same_bits(got[4], host["groupdq"], "groupdq")
+        got = outputs_to_numpy(o)
+    assert_equal_outputs(got, host, "device-resident against host call")

@@ -9,7 +9,8 @@ groups i and j > i on group i, so a jump into the last group G-1 shows as JUMP_D
 import numpy as np
 import pytest
 import torch  # before libromanhip is loaded: torch brings its own copy of the HIP runtime, and the first one loaded must be the one both use
-from conftest import assert_same_bits, gpu_context
+from chain_support import (JUMP, OUT, SAT, assert_equal_outputs, assert_oracle, calibrate_resident, chain_context, device_outputs, loaded,
+                           oracle_lines, outputs_to_numpy, ramp_to_dev, read_pattern)
 
 import oracle
 from romanimpreprocess_amd import pipeline, synth
@@ -17,37 +18,6 @@ from romanimpreprocess_amd import pipeline, synth
 pytestmark = pytest.mark.gpu
 
 NEW_COUNTS = (5, 7, 9, 10, 11, 12, 13, 14, 15)
-JUMP, SAT = 4, 2
-
-
-def _set_form(ctx, form):
-    """2: the fused kernel, 0: stage kernels"""
-    ctx.set_option("fused", 1 if form else 0)
-    ctx.set_option("chain2", 1 if form >= 2 else 0)
-
-
-def _default_form(ctx):
-    """the library's defaults: fused, the specialised kernels where they apply"""
-    ctx.set_option("fused", 1)
-    ctx.set_option("chain2", 1)
-
-
-def read_pattern(G):
-    """G groups of uneven lengths (1, 1, 2, 3, 5, 2, 1, 4, ... reads), consecutive reads, the first group the single read 0"""
-    lens = [1, 1, 2, 3, 5, 2, 1, 4, 2, 3, 1, 2, 6, 1, 2, 1]
-    rp, at = [], 0
-    for g in range(G):
-        rp.append(list(range(at, at + lens[g])))
-        at += lens[g]
-    return rp
-
-
-def _oracle_lines(out, G, nch):
-    """(G, nch, 2) LAPACK (m, c) the oracle used for the science channels."""
-    lines = np.zeros((G, nch, 2))
-    for g in range(G):
-        lines[g] = out["refpix_diag"][g]["channels"][:nch, 2:4]
-    return lines
 
 
 def _odd_conditions(ref, G):
@@ -102,21 +72,12 @@ def test_new_forms_vs_oracle(G, shape, p, exclude_first, kdt, seed):
     ny, nx = shape
     rp, cal, ramp, ref = small_inputs(G, shape, p, exclude_first, kdt, seed)
     small_conditions(ref, G)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(4, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 4, cal) as cb:
         assert cb.chain_form_for(4, G) == 2
-        got = cb.calibrate(4, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=_oracle_lines(ref, G, nx // 128))
+        got = cb.calibrate(4, ramp, exclude_first=exclude_first, want_cube=True, channel_lines=oracle_lines(ref, G, nx // 128))
         assert ctx.last_chain_form() == 2, "the fused kernel did not run"
-        assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-        assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-        assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-        for k in ("slope", "err_read", "err_poisson"):
-            assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
-    finally:
-        cb.ctx.drop_caldir(4)
+        assert_oracle(got, ref, "fused kernel", cube=True)
 
 
 # ---- 2. seams: several column strips and row ranges, fused against stage kernels
@@ -138,15 +99,11 @@ def big_conditions(ref, G):
 
 def _fused_vs_stages(cb, ctx, slot, ramp, G):
     outs = []
-    try:
-        for form in (2, 0):
-            _set_form(ctx, form)
+    for form in (2, 0):   # 2: the fused kernel, 0: stage kernels
+        with ctx.options(fused=1 if form else 0, chain2=1 if form else 0):
             outs.append(cb.calibrate(slot, ramp, want_cube=True))
             assert ctx.last_chain_form() == form
-    finally:
-        _default_form(ctx)
-    for k in ("cube", "slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-        assert_same_bits(outs[0][k], outs[1][k], f"{k}: fused vs stage kernels")
+    assert_equal_outputs(outs[0], outs[1], "fused vs stage kernels", keys=("cube",) + OUT)
 
 
 @pytest.mark.parametrize("G,kdt", SEAMS, ids=[f"g{g}_{'k64' if k == np.float64 else 'f32'}" for g, k in SEAMS])
@@ -155,13 +112,9 @@ def test_new_forms_agree_with_stage_kernels_across_seams(G, kdt):
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal)
     big_conditions(ref, G)
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(5, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 5, cal) as cb:
         _fused_vs_stages(cb, ctx, 5, ramp, G)
-    finally:
-        cb.ctx.drop_caldir(5)
 
 
 # ---- 3. full width: 33 (17) strips, frame-edge lanes emitting
@@ -182,21 +135,12 @@ def test_new_forms_full_width_vs_oracle_and_stage_kernels(G, kdt):
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal)
     big_conditions(ref, G)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(6, cal)
-    try:
-        got = cb.calibrate(6, ramp, want_cube=True, channel_lines=_oracle_lines(ref, G, 4096 // 128))
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 6, cal) as cb:
+        got = cb.calibrate(6, ramp, want_cube=True, channel_lines=oracle_lines(ref, G, 4096 // 128))
         assert ctx.last_chain_form() == 2
-        assert_same_bits(got["cube"], ref["data"], "corrected cube", zero_sign_ok=True)
-        assert_same_bits(got["groupdq"], ref["groupdq"], "groupdq")
-        assert_same_bits(got["pixeldq"], ref["pixeldq"], "pixeldq")
-        for k in ("slope", "err_read", "err_poisson"):
-            assert_same_bits(got[k], ref[k], k, zero_sign_ok=True)
+        assert_oracle(got, ref, "fused kernel", cube=True)
         _fused_vs_stages(cb, ctx, 6, ramp, G)
-    finally:
-        cb.ctx.drop_caldir(6)
 
 
 # ---- 5. the batch and the device-resident entry points
@@ -205,11 +149,8 @@ def test_batch_of_host_ramps_equals_single_calls(G):
     rp = read_pattern(G)
     ny, nx = 72, 256
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=41, bias_amplitude=2.0)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(2, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 2, cal) as cb:
         ramps = [synth.make_ramp(cal, read_pattern=rp, seed=50 + i, cr_frac=0.02, saturation_backup=0) for i in range(4)]
         singles = []
         for r in ramps:
@@ -219,48 +160,27 @@ def test_batch_of_host_ramps_equals_single_calls(G):
         assert ctx.last_chain_form() == 2
         assert len(many) == len(ramps)
         for i, (a, b) in enumerate(zip(many, singles)):
-            for k in ("slope", "err_read", "err_poisson", "pixeldq", "groupdq"):
-                assert_same_bits(a[k], b[k], f"ramp {i}: {k}")
+            assert_equal_outputs(a, b, f"ramp {i}")
         assert np.count_nonzero(singles[0]["pixeldq"] & JUMP) > 5
         assert not np.array_equal(singles[0]["slope"], singles[1]["slope"])
-    finally:
-        cb.ctx.drop_caldir(2)
 
 
 @pytest.mark.parametrize("G", [7, 12])
 def test_device_resident_call_equals_host_call(G):
-    dev = torch.device("cuda", 0)
     rp = read_pattern(G)
     ny, nx = 136, 512
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=43, bias_amplitude=2.0)
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=44, cr_frac=0.02, saturation_backup=0)
-    ctx = gpu_context()
-    _default_form(ctx)
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(9, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 9, cal) as cb:
         host = cb.calibrate(9, ramp)
         assert ctx.last_chain_form() == 2
         pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-        def to_dev(a):
-            a = np.ascontiguousarray(a)
-            view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-            return torch.from_numpy(a.view(view) if view else a).to(dev)
-
-        t = [to_dev(ramp[k]) for k in ("data", "amp33", "groupdq", "pixeldq")]
-        o = [torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] + \
-            [torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((G, ny, nx), dtype=torch.uint8, device=dev)]
+        t, o = ramp_to_dev(ramp), device_outputs(G, ny, nx)
         torch.cuda.synchronize()
         for _ in range(2):   # twice: the second call's pre-pass runs ahead of the first call's kernel
-            cb.calibrate_device(9, pid, G, t[0].data_ptr(), True, t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), o[4].data_ptr())
+            calibrate_resident(cb, 9, pid, G, t, o)
         cb.synchronize()
         assert ctx.last_chain_form() == 2
-        for k, name in enumerate(("slope", "err_read", "err_poisson")):
-            assert_same_bits(o[k].cpu().numpy(), host[name], name)
-        assert_same_bits(o[3].cpu().numpy().view(np.uint32), host["pixeldq"], "pixeldq")
-        assert_same_bits(o[4].cpu().numpy(), host["groupdq"], "groupdq")
+        assert_equal_outputs(outputs_to_numpy(o), host, "device-resident against host call")
         assert np.count_nonzero(host["pixeldq"] & JUMP) > 5
-    finally:
-        cb.ctx.drop_caldir(9)

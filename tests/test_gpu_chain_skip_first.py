@@ -14,22 +14,15 @@ from functools import lru_cache
 import numpy as np
 import pytest
 import torch  # before libromanhip is loaded: torch brings its own copy of the HIP runtime, and the first one loaded must be the one both use
-from conftest import assert_same_bits, gpu_context
-from test_gpu_chain_groups import _oracle_lines, read_pattern
+from chain_support import (F32, F64, JUMP, SAT, assert_equal_outputs, assert_oracle, band_conditions, calibrate_resident, chain_context,
+                           device_cus, device_outputs, find_height, geometry, inputs, is_quad, loaded, oracle_lines, outputs_to_numpy,
+                           quad_columns, ramp_to_dev, read_pattern)
 
 import oracle
 from romanimpreprocess_amd import _native, pipeline, plan as planmod, synth
 
-JUMP, SAT = 4, 2
-F32, F64 = np.float32, np.float64
 SLOT = 12
-OUT = ("slope", "err_read", "err_poisson", "pixeldq", "groupdq")
 gpu = pytest.mark.gpu
-
-
-def set_defaults(ctx):
-    for name, value in (("fused", 1), ("chain2", 1), ("chain_quad", 1), ("chain_reserve", 8), ("skip_first", 1)):
-        ctx.set_option(name, value)
 
 
 @lru_cache(maxsize=4)
@@ -43,7 +36,7 @@ def clean_inputs(G, shape, p, k64, seed):
     ramp = synth.make_ramp(cal, read_pattern=rp, seed=seed + 1, cr_frac=0.03, saturation_backup=0)
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal)
-    return rp, cal, ramp, ref, _oracle_lines(ref, G, nx // 128)
+    return rp, cal, ramp, ref, oracle_lines(ref, G, nx // 128)
 
 
 def oracle_conditions(ref, G, start=1):
@@ -52,18 +45,6 @@ def oracle_conditions(ref, G, start=1):
     assert np.count_nonzero(ref["pixeldq"] & JUMP) > 5, "no jump flags in the oracle's output"
     refits = sum(np.count_nonzero((q[g] & SAT) & ~(q[g - 1] & SAT)) for g in range(3 + start, G))
     assert refits > 0, "no truncated refit in the oracle's output"
-
-
-def assert_oracle(got, ref, what):
-    assert_same_bits(got["groupdq"], ref["groupdq"], f"{what}: groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], f"{what}: pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], f"{what}: {k}", zero_sign_ok=True)
-
-
-def assert_equal_outputs(a, b, what, keys=OUT):
-    for k in keys:
-        assert_same_bits(a[k], b[k], f"{what}: {k}")
 
 
 def run(cb, ctx, ramp, skipped, form=2, **kw):
@@ -76,11 +57,9 @@ def run(cb, ctx, ramp, skipped, form=2, **kw):
 
 def skip_and_full(cb, ctx, ramp, **kw):
     """the same call with the option on and off"""
-    set_defaults(ctx)
     skip = run(cb, ctx, ramp, True, **kw)
-    ctx.set_option("skip_first", 0)
-    full = run(cb, ctx, ramp, False, **kw)
-    set_defaults(ctx)
+    with ctx.options(skip_first=0):
+        full = run(cb, ctx, ramp, False, **kw)
     return skip, full
 
 
@@ -100,18 +79,13 @@ CASES = [
 def test_skip_vs_full_and_oracle(G, shape, k64, p):
     rp, cal, ramp, ref, lines = clean_inputs(G, shape, p, k64, 300 + G)
     oracle_conditions(ref, G)
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         assert ctx.caldir_first_group_safe(SLOT), "a clean CALDIR set did not pass the screen"
         skip, full = skip_and_full(cb, ctx, ramp, channel_lines=lines)
         if shape[0] == 57:
             g = ctx.last_chain_geometry()
             assert g["nq"] == 0 and shape[0] - (-(-shape[0] // g["rows"]) - 1) * g["rows"] == 1, f"no last range of one row: {g}"
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert_equal_outputs(skip, full, "skipping against full form")
     assert_oracle(skip, ref, "skipping form")
     assert_oracle(full, ref, "full form")
@@ -121,27 +95,19 @@ def test_skip_vs_full_and_oracle(G, shape, k64, p):
 def test_skip_in_quad_mode_of_the_256_column_form():
     """f32 ipc4d x 8 groups on a frame whose last strip has 8 live columns, tall enough for quad mode (the inputs, and the way
     to the shape, of test_gpu_chain_geometry)"""
-    import test_gpu_chain_geometry as geo
-
     G, nx = 8, 512
-    ncu = geo.device_cus()
-    ny = geo.find_height(1376, 8, lambda ny: geo.is_quad(geo.geometry(G, F32, ny, nx, ncu), 8), "quad mode at nx = 512")
-    rp, cal, ramp, ref, lines = geo.inputs(G, False, ny, nx, 10, True)
-    geo.band_conditions(ref, G, geo.quad_columns(geo.geometry(G, F32, ny, nx, ncu), nx))
+    ncu = device_cus()
+    ny = find_height(1376, 8, lambda ny: is_quad(geometry(G, F32, ny, nx, ncu), 8), "quad mode at nx = 512")
+    rp, cal, ramp, ref, lines = inputs(G, False, ny, nx, 10, True)
+    band_conditions(ref, G, quad_columns(geometry(G, F32, ny, nx, ncu), nx))
     oracle_conditions(ref, G)
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         assert ctx.caldir_first_group_safe(SLOT)
-        set_defaults(ctx)
         skip = run(cb, ctx, ramp, True, channel_lines=lines)
-        assert geo.is_quad(ctx.last_chain_geometry(), 8), f"not quad mode: {ctx.last_chain_geometry()}"
-        ctx.set_option("skip_first", 0)
-        full = run(cb, ctx, ramp, False, channel_lines=lines)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
+        assert is_quad(ctx.last_chain_geometry(), 8), f"not quad mode: {ctx.last_chain_geometry()}"
+        with ctx.options(skip_first=0):
+            full = run(cb, ctx, ramp, False, channel_lines=lines)
     assert_equal_outputs(skip, full, "skipping against full form")
     assert_oracle(skip, ref, "skipping form in quad mode")
 
@@ -150,49 +116,31 @@ def test_skip_in_quad_mode_of_the_256_column_form():
 def test_skip_through_batch_host_and_device_calls():
     """the pre-pass's own channel lines (no caller's lines): single host calls, rip_calibrate_batch and device-resident calls back
     to back (the second call's pre-pass -- tables of groups 1 .. G-1 only -- runs beside the first call's kernel)"""
-    dev = torch.device("cuda", 0)
     G, ny, nx = 7, 136, 512
     rp = read_pattern(G)
     cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=8, seed=43, bias_amplitude=2.0)
     ramps = [synth.make_ramp(cal, read_pattern=rp, seed=44 + i, cr_frac=0.02, saturation_backup=0) for i in range(3)]
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    cb.load_caldir(SLOT, cal)
-    try:
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         assert ctx.caldir_first_group_safe(SLOT)
         both = [skip_and_full(cb, ctx, r) for r in ramps]
         many = cb.calibrate_many(SLOT, ramps, want_groupdq=True)
         assert ctx.last_chain_form() == 2 and ctx.last_chain_first_group() == 1
         pid, _meta = cb.plan_for(rp, synth.FRAME_TIME)
-
-        def to_dev(a):
-            a = np.ascontiguousarray(a)
-            view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-            return torch.from_numpy(a.view(view) if view else a).to(dev)
-
-        t = [[to_dev(r[k]) for k in ("data", "amp33", "groupdq", "pixeldq")] for r in ramps[:2]]
-        o = [[torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] +
-             [torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((G, ny, nx), dtype=torch.uint8, device=dev)] for _ in range(2)]
+        t = [ramp_to_dev(r) for r in ramps[:2]]
+        o = [device_outputs(G, ny, nx) for _ in range(2)]
         torch.cuda.synchronize()
         for i in (0, 1):
-            cb.calibrate_device(SLOT, pid, G, t[i][0].data_ptr(), True, t[i][1].data_ptr(), t[i][2].data_ptr(), t[i][3].data_ptr(),
-                                o[i][0].data_ptr(), o[i][1].data_ptr(), o[i][2].data_ptr(), o[i][3].data_ptr(), o[i][4].data_ptr())
+            calibrate_resident(cb, SLOT, pid, G, t[i], o[i])
         cb.synchronize()
         assert ctx.last_chain_form() == 2 and ctx.last_chain_first_group() == 1
-        got_dev = [[x.cpu().numpy() for x in oi] for oi in o]
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
+        got_dev = [outputs_to_numpy(oi) for oi in o]
     assert np.count_nonzero(both[0][0]["pixeldq"] & JUMP) > 5
     for i, (skip, full) in enumerate(both):
         assert_equal_outputs(skip, full, f"ramp {i}: skipping against full form")
         assert_equal_outputs(many[i], full, f"ramp {i}: batch against full form")
     for i in (0, 1):
-        full = both[i][1]
-        for k, name in enumerate(("slope", "err_read", "err_poisson")):
-            assert_same_bits(got_dev[i][k], full[name], f"device call {i}: {name}")
-        assert_same_bits(got_dev[i][3].view(np.uint32), full["pixeldq"], f"device call {i}: pixeldq")
-        assert_same_bits(got_dev[i][4], full["groupdq"], f"device call {i}: groupdq")
+        assert_equal_outputs(got_dev[i], both[i][1], f"device call {i}")
 
 
 # ---- 2. independence: what group 0 holds does not reach the results
@@ -215,20 +163,14 @@ def test_results_do_not_depend_on_group_0():
     ramp2["amp33"][0] = rng.integers(20000, 40000, size=ramp["amp33"][0].shape).astype(np.uint16)
     with np.errstate(all="ignore"):
         ref2 = oracle.calibrate_arrays(ramp2, cal2)
-    lines2 = _oracle_lines(ref2, G, shape[1] // 128)
+    lines2 = oracle_lines(ref2, G, shape[1] // 128)
     assert not np.array_equal(ref["data"][0], ref2["data"][0]) and not np.array_equal(lines[0], lines2[0])
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    try:
-        set_defaults(ctx)
-        cb.load_caldir(SLOT, cal)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         a = run(cb, ctx, ramp, True, channel_lines=lines)
         cb.load_caldir(SLOT, cal2)
         assert ctx.caldir_first_group_safe(SLOT)
         b = run(cb, ctx, ramp2, True, channel_lines=lines2)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert_equal_outputs(a, b, "other finite values in group 0", keys=("slope", "err_read", "err_poisson", "pixeldq"))
     assert_oracle(a, ref, "first inputs")
     assert_oracle(b, ref2, "second inputs")
@@ -281,16 +223,10 @@ def test_screen_says_no(what, where):
     if what == "dark_nan" and where == "interior":
         nan_slope = np.isnan(ref["slope"])
         assert nan_slope[17, 200] and np.all(np.isfinite(ref["data"][1:, 17, 200])), "no NaN slope from group 0 alone in the oracle's output"
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    try:
-        set_defaults(ctx)
-        cb.load_caldir(SLOT, cal)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb:
         assert not ctx.caldir_first_group_safe(SLOT), "the screen passed a set with a bad value"
-        got = run(cb, ctx, ramp, False, form=0 if what == "bias_inf" else 2, channel_lines=_oracle_lines(ref, G, shape[1] // 128))
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
+        got = run(cb, ctx, ramp, False, form=0 if what == "bias_inf" else 2, channel_lines=oracle_lines(ref, G, shape[1] // 128))
     assert_oracle(got, ref, f"{what} at an {where} pixel")
 
 
@@ -312,21 +248,13 @@ def test_calls_that_take_the_full_form(case):
     with np.errstate(all="ignore"):
         ref = oracle.calibrate_arrays(ramp, cal, exclude_first=exclude_first)
     oracle_conditions(ref, G, 1 if exclude_first else 0)
-    kw = dict(exclude_first=exclude_first, channel_lines=_oracle_lines(ref, G, shape[1] // 128))
+    kw = dict(exclude_first=exclude_first, channel_lines=oracle_lines(ref, G, shape[1] // 128))
     if case == "want_cube":
         kw["want_cube"] = True
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    try:
-        set_defaults(ctx)
-        cb.load_caldir(SLOT, cal)
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), SLOT, cal) as cb, ctx.options(skip_first=0 if case == "option_off" else 1):
         assert ctx.caldir_first_group_safe(SLOT)
-        if case == "option_off":
-            ctx.set_option("skip_first", 0)
         got = run(cb, ctx, ramp, False, form=0 if case == "f32_cube" else 2, **kw)   # (an f32 cube takes the stage kernels)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert_oracle(got, ref, case)
 
 

@@ -269,11 +269,8 @@ def test_1f_frames_of_other_lengths_against_numpy_fft(rows, width, form):
     ctx = gpu_context()
     rng = np.random.default_rng(5)
     normals = rng.standard_normal((3, 4 * rows * width))
-    ctx.set_option("pink_form", form)
-    try:
+    with ctx.options(pink_form=form):
         got = gen_noise_image.noise_1f_frames(3, rows=rows, width=width, normals=normals, ctx=ctx)
-    finally:
-        ctx.set_option("pink_form", -1)
     for f in range(3):
         want = onoise.noise_1f_frame(normals[f], rows, width)
         np.testing.assert_allclose(got[f], want, rtol=0, atol=2e-6 * np.abs(want).max())
@@ -358,15 +355,12 @@ def test_1f_frames_from_both_transforms_agree():
     rows, width, n = 4096, 128, 12
     dev = torch.device("cuda", ctx.device)
     outs = []
-    try:
-        for form in (0, -1):
-            ctx.set_option("pink_form", form)
+    for form in (0, -1):
+        with ctx.options(pink_form=form):
             out = torch.empty((n, rows, width), dtype=torch.float32, device=dev)
             ctx.check(ctx.lib.rip_synth_noise_1f(ctx.h, rows, width, n, 123, 9, out.data_ptr()))
             ctx.synchronize()
             outs.append(out)
-    finally:
-        ctx.set_option("pink_form", -1)
     a, b = outs
     scale = float(a.abs().max())
     assert float((a - b).abs().max()) <= 4e-7 * scale

@@ -15,24 +15,17 @@ from functools import lru_cache
 import numpy as np
 import pytest
 import torch  # before libromanhip is loaded: torch brings its own copy of the HIP runtime, and the first one loaded must be the one both use
-from conftest import assert_same_bits, gpu_context
-from test_gpu_chain_groups import _oracle_lines, read_pattern
+from conftest import assert_same_bits
+from chain_support import (F32, F64, assert_equal_outputs, assert_oracle, chain_context, device_outputs, loaded, oracle_lines,
+                           outputs_to_numpy, read_pattern, to_dev)
 
 import oracle
 from romanimpreprocess_amd import _native, pipeline, synth
 
-F32, F64 = np.float32, np.float64
 SLOT = 13
-OUT = ("slope", "err_read", "err_poisson", "pixeldq", "groupdq")
 GATE_US = 100    # the bound the cases run the gate with (microseconds); the library's default is 0: no gate
 NONE, RELEASED, GAVE_UP = 0, 1, 2
 gpu = pytest.mark.gpu
-
-
-def set_defaults(ctx):
-    for name, value in (("fused", 1), ("chain2", 1), ("chain_quad", 1), ("chain_reserve", 8), ("skip_first", 1), ("overlap", -1),
-                        ("prepass_gate", 0)):
-        ctx.set_option(name, value)
 
 
 @lru_cache(maxsize=4)
@@ -50,23 +43,16 @@ def inputs(G, shape, k64, p, seed):
     assert not np.array_equal(refs[0]["slope"], refs[1]["slope"])
     assert all(np.count_nonzero(r["pixeldq"] & 4) > 5 for r in refs), "no jump flags in the oracle's output"
     assert not np.array_equal(refs[0]["refpix_diag"][1]["channels"], refs[1]["refpix_diag"][1]["channels"])
-    return rp, cal, ramps, refs, [_oracle_lines(r, G, nx // 128) for r in refs]
-
-
-def to_dev(a):
-    a = np.ascontiguousarray(a)
-    view = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32}.get(a.dtype)
-    return torch.from_numpy(a.view(view) if view else a).to(torch.device("cuda", 0))
+    return rp, cal, ramps, refs, [oracle_lines(r, G, nx // 128) for r in refs]
 
 
 class Resident:
     """the two ramps of `inputs` on the device (with group 0 marked DO_NOT_USE, as the host path does for an excluded first
-    group) and a plan for them on the context of `cb`"""
+    group) and a plan for them on the context of `cb`; the caller holds the set in `slot`: ``with loaded(cb, slot, res.cal)``"""
 
     def __init__(self, cb, slot, G, shape, k64, p, seed, own_lines=False):
         self.rp, self.cal, self.ramps, self.refs, self.lines = inputs(G, shape, k64, p, seed)
         self.cb, self.slot, self.G, self.shape = cb, slot, G, shape
-        cb.load_caldir(slot, self.cal)
         self.pid, _meta = cb.plan_for(self.rp, synth.FRAME_TIME)
         self.t = []
         for r, ln in zip(self.ramps, self.lines):
@@ -77,11 +63,7 @@ class Resident:
         torch.cuda.synchronize()
 
     def outputs(self, n):
-        ny, nx = self.shape
-        dev = torch.device("cuda", 0)
-        return [[torch.empty((ny, nx), dtype=torch.float32, device=dev) for _ in range(3)] +
-                [torch.empty((ny, nx), dtype=torch.int32, device=dev), torch.empty((self.G, ny, nx), dtype=torch.uint8, device=dev)]
-                for _ in range(n)]
+        return [device_outputs(self.G, *self.shape) for _ in range(n)]
 
     def call(self, i, o):
         """call i of a sequence (ramp i % 2), queued; device-resident, complete inputs: the pre-pass runs ahead"""
@@ -99,18 +81,14 @@ class Resident:
 
 
 def as_numpy(o):
-    return [dict(zip(OUT, (oi[0].cpu().numpy(), oi[1].cpu().numpy(), oi[2].cpu().numpy(), oi[3].cpu().numpy().view(np.uint32),
-                           oi[4].cpu().numpy()))) for oi in o]
+    return [outputs_to_numpy(oi) for oi in o]
 
 
-def unarmed(res, gate):
+def unarmed(res):
     """one call WITHOUT the counter, so that the sequence that follows starts like the first call on a context: no gate"""
-    ctx = res.cb.ctx
-    ctx.set_option("prepass_gate", 0)
-    ctx.set_option("fused", 1)
-    res.call(0, res.outputs(1)[0])
-    res.cb.synchronize()
-    ctx.set_option("prepass_gate", gate)
+    with res.cb.ctx.options(prepass_gate=0, fused=1):
+        res.call(0, res.outputs(1)[0])
+        res.cb.synchronize()
 
 
 def sequence(res, gate, n=6, fused=None):
@@ -119,48 +97,35 @@ def sequence(res, gate, n=6, fused=None):
     -> (outputs of the first pass, per call; gate state per call of the second pass; kernel form per call; give-ups added)"""
     ctx = res.cb.ctx
     fused = fused or [1] * n
-    unarmed(res, gate)
-    _, giveups0 = ctx.last_prepass_gate()
-    o = res.outputs(n)
-    for i in range(n):
-        ctx.set_option("fused", fused[i])
-        res.call(i, o[i])
-    res.cb.synchronize()
-    got = as_numpy(o)
-    _, giveups1 = ctx.last_prepass_gate()
-    unarmed(res, gate)
-    o2 = res.outputs(n)
-    states, forms = [], []
-    for i in range(n):
-        ctx.set_option("fused", fused[i])
-        res.call(i, o2[i])
-        states.append(ctx.last_prepass_gate()[0])
-        forms.append(ctx.last_chain_form())
-    ctx.set_option("fused", 1)
+    unarmed(res)
+    with ctx.options(prepass_gate=gate):
+        _, giveups0 = ctx.last_prepass_gate()
+        o = res.outputs(n)
+        for i in range(n):
+            with ctx.options(fused=fused[i]):
+                res.call(i, o[i])
+        res.cb.synchronize()
+        got = as_numpy(o)
+        _, giveups1 = ctx.last_prepass_gate()
+    unarmed(res)
+    with ctx.options(prepass_gate=gate):
+        o2 = res.outputs(n)
+        states, forms = [], []
+        for i in range(n):
+            with ctx.options(fused=fused[i]):
+                res.call(i, o2[i])
+            states.append(ctx.last_prepass_gate()[0])
+            forms.append(ctx.last_chain_form())
     for i, (a, b) in enumerate(zip(got, as_numpy(o2))):
         assert_equal_outputs(a, b, f"call {i}: queued against synchronised")
     return got, states, forms, giveups1 - giveups0
 
 
-def assert_equal_outputs(a, b, what):
-    for k in OUT:
-        assert_same_bits(a[k], b[k], f"{what}: {k}")
-
-
-def assert_oracle(got, ref, what):
-    assert_same_bits(got["groupdq"], ref["groupdq"], f"{what}: groupdq")
-    assert_same_bits(got["pixeldq"], ref["pixeldq"], f"{what}: pixeldq")
-    for k in ("slope", "err_read", "err_poisson"):
-        assert_same_bits(got[k], ref[k], f"{what}: {k}", zero_sign_ok=True)
-
-
 def on_and_off(res, n=6, fused=None, gate=GATE_US):
     """the sequence with the gate at `gate` and with the gate off; every call bit for bit; the last call of each ramp against
     the oracle; -> (states with the gate on, forms, give-ups added with the gate on)"""
-    ctx = res.cb.ctx
     on, states, forms, giveups = sequence(res, gate, n, fused)
     off, states_off, _forms, giveups_off = sequence(res, 0, n, fused)
-    ctx.set_option("prepass_gate", 0)
     assert states_off == [NONE] * n and giveups_off == 0, f"option off: gates {states_off}, give-ups {giveups_off}"
     for i in range(n):
         assert_equal_outputs(on[i], off[i], f"call {i}: gate on against gate off")
@@ -178,15 +143,10 @@ def queued(states):
 # ---- 1. all calls fused, 8 groups, f32 ipc4d: 512 columns = two strips of the 256-column form and a last strip of 8 live columns
 @gpu
 def test_all_fused_8_groups():
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    set_defaults(ctx)
-    try:
-        res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    cb = pipeline.Calibrator(ctx=chain_context())
+    res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    with loaded(cb, SLOT, res.cal):
         _on, states, forms, _g = on_and_off(res)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert forms == [2] * 6
     assert states[0] == NONE, "a gate on the first call of a sequence that follows a call without the counter"
     assert queued(states) == [False] + [True] * 5, f"gates: {states}"
@@ -197,16 +157,11 @@ def test_all_fused_8_groups():
 @gpu
 @pytest.mark.parametrize("G,k64,overlap", [(16, False, -1), (8, True, -1), (8, True, 1)], ids=["g16_f32", "g8_k64_by_situation", "g8_k64_overlap"])
 def test_other_forms(G, k64, overlap):
-    ctx = gpu_context()
+    ctx = chain_context()
     cb = pipeline.Calibrator(ctx=ctx)
-    set_defaults(ctx)
-    try:
-        res = Resident(cb, SLOT, G, (64, 768), k64, 3 if k64 else 10, 510 + G)
-        ctx.set_option("overlap", overlap)
+    res = Resident(cb, SLOT, G, (64, 768), k64, 3 if k64 else 10, 510 + G)
+    with loaded(cb, SLOT, res.cal), ctx.options(overlap=overlap):
         _on, states, forms, _g = on_and_off(res)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert forms == [2] * 6
     if k64 and overlap == -1:
         assert states == [NONE] * 6, f"a gate in front of a pre-pass that runs on the main stream: {states}"
@@ -218,16 +173,11 @@ def test_other_forms(G, k64, overlap):
 # would show as a give-up instead of passing by timing: every queued gate must be RELEASED by the counter.
 @gpu
 def test_mixed_fused_and_stage_kernel_calls():
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    set_defaults(ctx)
+    cb = pipeline.Calibrator(ctx=chain_context())
     fused = [1, 1, 0, 0, 1, 1, 1]
-    try:
-        res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    with loaded(cb, SLOT, res.cal):
         _on, states, forms, giveups = on_and_off(res, n=7, fused=fused, gate=200000)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert forms == [2, 2, 0, 0, 2, 2, 2]
     # call 3 follows a fused call (its pre-pass is gated behind THAT launch); calls 4 and 5 follow stage-kernel calls
     assert states == [NONE, RELEASED, RELEASED, NONE, NONE, RELEASED, RELEASED], f"gates: {states}"
@@ -237,43 +187,35 @@ def test_mixed_fused_and_stage_kernel_calls():
 # ---- 4. a bound of one microsecond: released or given up, by timing; the results are the same
 @gpu
 def test_tiny_bound():
-    ctx = gpu_context()
-    cb = pipeline.Calibrator(ctx=ctx)
-    set_defaults(ctx)
-    try:
-        res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    cb = pipeline.Calibrator(ctx=chain_context())
+    res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500)
+    with loaded(cb, SLOT, res.cal):
         _on, states, _forms, _g = on_and_off(res, gate=1)
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert states[0] == NONE and queued(states) == [False] + [True] * 5, f"gates: {states}"
 
 
 # ---- 5. two contexts on one device, calls interleaved (the realisations workload): each has its own counter and total
 @gpu
 def test_two_contexts_interleaved():
-    ctx = gpu_context()
-    ctx2 = _native.Context(0)
+    ctx = chain_context()
+    ctx2 = _native.Context(0)   # (a new context starts at the defaults)
     cbs = [pipeline.Calibrator(ctx=ctx), pipeline.Calibrator(ctx=ctx2)]
     n = 6
     try:
-        for c in (ctx, ctx2):
-            set_defaults(c)
         res = [Resident(cbs[0], SLOT, 8, (64, 512), False, 8, 500), Resident(cbs[1], SLOT, 8, (96, 512), False, 8, 520)]
         got, giveups = {}, {}
-        for gate in (200000, 0):
-            base = []
-            for r in res:
-                r.cb.ctx.set_option("prepass_gate", gate)
-                base.append(r.cb.ctx.last_prepass_gate()[1])
-            o = [r.outputs(n) for r in res]
-            for i in range(n):
-                for r, oo in zip(res, o):
-                    r.call(i, oo[i])
-            states = [r.cb.ctx.last_prepass_gate() for r in res]   # (waits for the streams of its context)
-            got[gate] = [as_numpy(oo) for oo in o]
-            giveups[gate] = [s[1] - b for s, b in zip(states, base)]
-            assert [s[0] for s in states] == ([RELEASED] * 2 if gate else [NONE] * 2), f"gate {gate}: last gates {states}"
+        with loaded(cbs[0], SLOT, res[0].cal), loaded(cbs[1], SLOT, res[1].cal):
+            for gate in (200000, 0):
+                with ctx.options(prepass_gate=gate), ctx2.options(prepass_gate=gate):
+                    base = [r.cb.ctx.last_prepass_gate()[1] for r in res]
+                    o = [r.outputs(n) for r in res]
+                    for i in range(n):
+                        for r, oo in zip(res, o):
+                            r.call(i, oo[i])
+                    states = [r.cb.ctx.last_prepass_gate() for r in res]   # (waits for the streams of its context)
+                got[gate] = [as_numpy(oo) for oo in o]
+                giveups[gate] = [s[1] - b for s, b in zip(states, base)]
+                assert [s[0] for s in states] == ([RELEASED] * 2 if gate else [NONE] * 2), f"gate {gate}: last gates {states}"
         assert giveups[200000] == [0, 0], f"give-ups per context: {giveups[200000]}"
         for c, r in enumerate(res):
             for i in range(n):
@@ -281,8 +223,6 @@ def test_two_contexts_interleaved():
             for i in (n - 2, n - 1):
                 assert_oracle(got[200000][c][i], r.refs[i % 2], f"context {c} call {i}")
     finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
         ctx2.close()
 
 
@@ -291,19 +231,14 @@ def test_two_contexts_interleaved():
 @gpu
 @pytest.mark.parametrize("skip", (1, 0))
 def test_skip_first_on_and_off(skip):
-    ctx = gpu_context()
+    ctx = chain_context()
     cb = pipeline.Calibrator(ctx=ctx)
-    set_defaults(ctx)
-    try:
-        res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500, own_lines=True)
+    res = Resident(cb, SLOT, 8, (64, 512), False, 8, 500, own_lines=True)
+    with loaded(cb, SLOT, res.cal), ctx.options(skip_first=skip):
         assert ctx.caldir_first_group_safe(SLOT)
-        ctx.set_option("skip_first", skip)
         on, states, forms, _g = on_and_off(res)
         assert ctx.last_chain_first_group() == skip, "not the expected treatment of group 0"
         host = [cb.calibrate(SLOT, r) for r in res.ramps]   # the same lines, fitted on the device, through a host call
-    finally:
-        set_defaults(ctx)
-        ctx.drop_caldir(SLOT)
     assert forms == [2] * 6 and queued(states) == [False] + [True] * 5, f"forms {forms}, gates {states}"
     for i in (4, 5):
         assert_equal_outputs(on[i], host[i % 2], f"call {i} against a host call")
