@@ -161,6 +161,17 @@ __device__ __forceinline__ void c2_div64_shared(const double (&a)[NA], float bf,
     }
 }
 
+// operands of rip_legendre_series in registers: the coefficients of the prefetched row, the constants per degree
+template <int NP>
+struct C2Legendre {
+    const float (&cfs)[NP], (&c1s)[NP], (&c2s)[NP], (&chfs)[NP];
+    static constexpr __device__ int n() { return NP; }
+    __device__ __forceinline__ float cf(int L) const { return cfs[L]; }
+    __device__ __forceinline__ float c1(int L) const { return c1s[L]; }
+    __device__ __forceinline__ float c2(int L) const { return c2s[L]; }
+    __device__ __forceinline__ float chf(int L) const { return chfs[L]; }
+};
+
 template <int NP, int G, int START, typename KT, bool SKIP0 = false>
 __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C2Form<G + (G & 1), sizeof(KT) == 8>::wps)) void chain2_kernel(
     ChainArgs a, const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars, const float *__restrict__ kvals,
@@ -226,9 +237,8 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     float c1[NP], c2[NP], chf[NP];
 #pragma unroll
     for (int L = 1; L < NP; ++L) {
-        c1[L] = (float)((double)(2 * L + 1) / (double)(L + 1));
-        c2[L] = (float)((double)L / (double)(L + 1));
-        chf[L] = (float)((double)(L * (L + 1)) / 2.0);
+        const RipLegendreK k = rip_legendre_k(L);
+        c1[L] = k.c1, c2[L] = k.c2, chf[L] = k.chf;
     }
 
     const int nstrips = F::nstrips(nx);
@@ -275,7 +285,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
         }
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            const int dx = (k == 3 || k == 5 || k == 7) ? 1 : (k == 4 || k == 6 || k == 8) ? -1 : 0;
+            const int dx = RIP_IPC_DX(k);
             if (okx[dx + 1]) colmask |= 1u << k;
         }
         if (!col_act) colmask = 0;
@@ -288,66 +298,46 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     // its neighbours' (each such row costs HBM traffic and buys nothing)
     const int ylo = max(R0 - 2, 0), yhi = min(R1 + 1, ny - 1);
 
-    // coefficient loader: raw loads at clamped source positions + validity mask for destination (y, c);
-    // `want` is wave-uniform.  Planes are walked in memory order (plane = 3*(1+dy) + (1+dx)).
-    auto load_k = [&](const void *kern_base, int y, bool want, f2 (&kk2)[5]) -> unsigned {
-        if (dbg & 128) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) kk2[k] = f2{(k == 0) ? 1.0f : 0.001f, 0.001f};
-            return want ? lane_mask : 0u;
-        }
-        unsigned rowoff[3];
-        bool rok[3];
-#pragma unroll
-        for (int dyi = 0; dyi < 3; ++dyi) {
-            const int sy = y - (dyi - 1);
-            rok[dyi] = sy >= ay0 && sy < ay1;
-            rowoff[dyi] = (unsigned)min(max(sy, ylo), yhi) * row4;   // rows outside the range's own are never used: keep to lines it reads anyway
-        }
-        // terms by source row: dy = -1 -> k in {2, 7, 8}, dy = 0 -> {0, 3, 4}, dy = +1 -> {1, 5, 6}
-        const unsigned rowbits = (rok[0] ? 0x184u : 0u) | (rok[1] ? 0x019u : 0u) | (rok[2] ? 0x062u : 0u);
-        const __amdgpu_buffer_rsrc_t kr = c2_rsrc(kern_base);
-        unsigned pofs = 0;  // plane offset, planes walked in memory order (plane = 3*(1+dy) + (1+dx))
-#pragma unroll
-        for (int p = 0; p < 9; ++p) {
-            const int dy = p / 3 - 1, dx = p % 3 - 1;
-            // term index of (dy, dx) in the reference's order: 0 centre, 1 (1,0), 2 (-1,0), 3 (0,1), 4 (0,-1), 5 (1,1),
-            // 6 (1,-1), 7 (-1,1), 8 (-1,-1)
-            const int k = (dy == 0) ? (dx == 0 ? 0 : dx == 1 ? 3 : 4) : (dy == 1) ? (dx == 0 ? 1 : dx == 1 ? 5 : 6)
-                                                                                  : (dx == 0 ? 2 : dx == 1 ? 7 : 8);
-            const float kv_ = c2_ld_f32(kr, cx4[dx + 1], pofs + rowoff[dy + 1]);
-            if (k & 1)
-                kk2[k / 2].y = kv_;
-            else
-                kk2[k / 2].x = kv_;
-            pofs += pl4;
-        }
-        const unsigned um = (want && y >= ay0 && y < ay1) ? rowbits : 0u;
-        return lane_mask & um;
-    };
-
-    // f64 coefficients: the same walk with 8-byte loads, nine scalars in the reference's term order
-    // (kmin: terms below it are not loaded -- the fit role of a form with a partial K ring gets them through LDS)
-    auto load_kd = [&](const void *kern_base, int y, bool want, double (&kk)[9], auto kmin_c) -> unsigned {
+    // coefficient loader: raw loads at clamped source positions + validity mask for destination (y, c); `want` is wave-uniform.
+    // The nine planes are walked in memory order (plane = 3*(1+dy) + (1+dx)) and land in the reference's term order
+    // (rip_ipc_term): f32 coefficients as the five pairs kk[k / 2], f64 ones as nine scalars kk[k], with 8-byte loads.
+    // kmin: terms below it are not loaded -- the fit role of a form with a partial K ring gets them through LDS.
+    auto load_k = [&](const void *kern_base, int y, bool want, auto &kk, auto kmin_c) -> unsigned {
         constexpr int KMIN = decltype(kmin_c)::value;
+        constexpr bool PAIRS = sizeof(kk) == sizeof(f2[5]);   // f2 kk[5], else double kk[9]
+        constexpr unsigned ES = PAIRS ? 1u : 2u;   // element size in f32 words
+        if constexpr (PAIRS) {
+            if (dbg & 128) {
+#pragma unroll
+                for (int k = 0; k < 5; ++k) kk[k] = f2{(k == 0) ? 1.0f : 0.001f, 0.001f};
+                return want ? lane_mask : 0u;
+            }
+        }
         unsigned rowoff[3];
         bool rok[3];
 #pragma unroll
         for (int dyi = 0; dyi < 3; ++dyi) {
             const int sy = y - (dyi - 1);
             rok[dyi] = sy >= ay0 && sy < ay1;
-            rowoff[dyi] = (unsigned)min(max(sy, ylo), yhi) * (row4 * 2u);
+            rowoff[dyi] = (unsigned)min(max(sy, ylo), yhi) * (row4 * ES);   // rows outside the range's own are never used: keep to lines it reads anyway
         }
-        const unsigned rowbits = (rok[0] ? 0x184u : 0u) | (rok[1] ? 0x019u : 0u) | (rok[2] ? 0x062u : 0u);
+        const unsigned rowbits = rip_ipc_row_mask(rok[0], rok[1], rok[2]);
         const __amdgpu_buffer_rsrc_t kr = c2_rsrc(kern_base);
         unsigned pofs = 0;
 #pragma unroll
         for (int p = 0; p < 9; ++p) {
             const int dy = p / 3 - 1, dx = p % 3 - 1;
-            const int k = (dy == 0) ? (dx == 0 ? 0 : dx == 1 ? 3 : 4) : (dy == 1) ? (dx == 0 ? 1 : dx == 1 ? 5 : 6)
-                                                                                  : (dx == 0 ? 2 : dx == 1 ? 7 : 8);
-            if (k >= KMIN) kk[k] = c2_ld_f64(kr, cx4[dx + 1] * 2u, pofs + rowoff[dy + 1]);
-            pofs += pl4 * 2u;
+            const int k = rip_ipc_term(dy, dx);
+            if constexpr (PAIRS) {
+                const float kv_ = c2_ld_f32(kr, cx4[dx + 1], pofs + rowoff[dy + 1]);
+                if (k & 1)
+                    kk[k / 2].y = kv_;
+                else
+                    kk[k / 2].x = kv_;
+            } else {
+                if (k >= KMIN) kk[k] = c2_ld_f64(kr, cx4[dx + 1] * 2u, pofs + rowoff[dy + 1]);
+            }
+            pofs += pl4 * ES;
         }
         const unsigned um = (want && y >= ay0 && y < ay1) ? rowbits : 0u;
         return lane_mask & um;
@@ -355,8 +345,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     // validity mask of destination (y, c) alone, for the role that receives the coefficients through the K ring
     auto k_valid = [&](int y) -> unsigned {
         const bool r0 = (y + 1) >= ay0 && (y + 1) < ay1, r1 = y >= ay0 && y < ay1, r2 = (y - 1) >= ay0 && (y - 1) < ay1;
-        const unsigned rowbits = (r0 ? 0x184u : 0u) | (r1 ? 0x019u : 0u) | (r2 ? 0x062u : 0u);
-        return r1 ? (lane_mask & rowbits) : 0u;
+        return r1 ? (lane_mask & rip_ipc_row_mask(r0, r1, r2)) : 0u;
     };
 #ifdef CH_STAMP
     unsigned long long st_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -494,15 +483,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                                     continue;
                                 }
                             }
-                            float S = (float)rr.S[g];
-                            const float dk = rr.dk[g];
-                            float v = S - dk;
-                            v = (float)((double)v - rc[g]);
                             const double *ln = LN + (chr * G + g) * 2;
-                            const double iel = ln[0] * yd + ln[1];
-                            v = (float)((double)v - iel);
-                            S = v + dk;
-                            if (act) S = S - rr.bs[g];
+                            float S = rip_refpix_apply((float)rr.S[g], rr.dk[g], rc[g], ln[0], ln[1], yd);
+                            if (act) S = S - rr.bs[g];   // gen_cal_image.py:559-565
                             Sv[e] = S;
                             w[g / 4] |= (rr.q[g] & 0xffu) << (8 * (g & 3));
                         }
@@ -576,25 +559,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                                         continue;
                                     }
                                 }
-                                const float ze = e ? zz[b].y : zz[b].x;
-                                const float az = fabsf(ze);
-                                ex[b][e] = az > 1.0f;
-                                const float exc = az - 1.0f;
-                                const bool neg = ze < 0.0f;
-                                float phs = rr.cf[0], pp = 1.0f, pc = ze;
-#pragma unroll
-                                for (int L = 1; L < NP; ++L) {
-                                    float ee = 1.0f + chf[L] * exc;
-                                    ee = (neg && (L & 1)) ? -ee : ee;
-                                    const float sel = ex[b][e] ? ee : pc;
-                                    const float term = rr.cf[L] * sel;
-                                    phs = phs + term;
-                                    const float u = c1[L] * ze;
-                                    const float pn = u * pc - c2[L] * pp;
-                                    pp = pc;
-                                    pc = pn;
-                                }
-                                ph[e] = phs;
+                                ph[e] = rip_legendre_series(e ? zz[b].y : zz[b].x, C2Legendre<NP>{rr.cf, c1, c2, chf}, ex[b][e]);
                             }
                             phi[b] = f2{ph[0], ph[1]};
                         }
@@ -622,7 +587,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                             vout[e] = ((dq & bad) == 0) ? (e ? phi[b].y : phi[b].x) : (e ? fb.y : fb.x);
                             const bool first = (g == 0) && a.do_not_flag_first;
                             const uint32_t qg = w[g / 4] >> (8 * (g & 3));
-                            if (!first && ex[b][e] && (qg & DQ_SATURATED) == 0) dq |= DQ_NO_LIN_CORR;
+                            if (!first && ex[b][e] && rip_lin_attempt(qg)) dq |= DQ_NO_LIN_CORR;
                         }
                         f2 xv = {vout[0], vout[1]};
                         if (act) xv = xv * rr.gain;
@@ -655,13 +620,15 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             kC[4].y = 0.0f;
             unsigned vC;
             if constexpr (K64)
-                vC = load_kd(ka->kern, yc, do_c && wcol >= 1 && wcol < wl - 1, kCd, C2Int<0>{});
+                vC = load_k(ka->kern, yc, do_c && wcol >= 1 && wcol < wl - 1, kCd, C2Int<0>{});
             else
-                vC = load_k(ka->kern, yc, do_c && wcol >= 1 && wcol < wl - 1, kC);
+                vC = load_k(ka->kern, yc, do_c && wcol >= 1 && wcol < wl - 1, kC, C2Int<0>{});
             CH_T(2)
             C2_SYNC();
             CH_T(3)
             const RIP_K ChainArgs *kb2 = &c2_args(kargs)->a;  // S2 copy
+            // the share of the next row's coefficient planes that is requested beside pair p of C
+            auto fetch_coefs_beside = [&](int p) { fetch_coefs(kb2, r + 4, p * CO_STEP, min(p * CO_STEP + CO_STEP, NCO), rr); };
             // ---- S2: issue the raw loads of row r+4 (consumed in S1 of the next step), then C of row yc
             CH_T(4)
             {
@@ -689,7 +656,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                     for (int p0 = 0; p0 < GP; p0 += PBC) {
 #pragma unroll
                         for (int q = 0; q < PBC; ++q)
-                            fetch_coefs(kb2, r + 4, (p0 + q) * CO_STEP, ((p0 + q) * CO_STEP + CO_STEP < NCO) ? (p0 + q) * CO_STEP + CO_STEP : NCO, rr);
+                            fetch_coefs_beside(p0 + q);
                         if (do_c) {
                             float v[2 * PBC][9];
 #pragma unroll
@@ -719,7 +686,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                     for (int i = 0; i < 5; ++i) asm volatile("" : "+v"(kC[i]));
 #pragma unroll
                     for (int p0 = 0; p0 < GP; ++p0) {
-                        fetch_coefs(kb2, r + 4, p0 * CO_STEP, (p0 * CO_STEP + CO_STEP < NCO) ? p0 * CO_STEP + CO_STEP : NCO, rr);
+                        fetch_coefs_beside(p0);
                         const f2 *xb = X2 + p0 * XR * COLS;
                         const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
                         f2 f[1], xc[1];
@@ -733,7 +700,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                 } else {
 #pragma unroll
                     for (int p0 = 0; p0 < GP; ++p0) {
-                        fetch_coefs(kb2, r + 4, p0 * CO_STEP, (p0 * CO_STEP + CO_STEP < NCO) ? p0 * CO_STEP + CO_STEP : NCO, rr);
+                        fetch_coefs_beside(p0);
                         if (do_c && !(dbg & 1)) {
                             const f2 *xb = X2 + p0 * XR * COLS;
                             const f2 *xm[1] = {xb + sm * COLS}, *x0[1] = {xb + s0 * COLS}, *xp[1] = {xb + sp * COLS};
@@ -1023,25 +990,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                         er = div_rcp(er2, e_flat, rflat);
                         ep = div_rcp(ep2, e_flat, rflat);
                     } else {
-                        float err = hypot_f32(er, ep);
-                        float vp = ep * ep;
-                        if (!act) {
-                            s = 0.0f;
-                            err = 0.0f;
-                            vp = 0.0f;
-                        }
-                        if (act && kg->a.dark_rate) s = s - e_dark;
-                        float ep2 = sqrtf(vp);
-                        const float e2 = err * err;
-                        const float p2 = ep2 * ep2;
-                        float er2 = sqrtf(clip_lo<float>(e2 - p2, 0.0f));
-                        if (kg->a.flat) {
-                            s = s / e_flat;
-                            er2 = er2 / e_flat;
-                            ep2 = ep2 / e_flat;
-                        }
-                        er = er2;
-                        ep = ep2;
+                        rip_finish(act, [&] { return act && kg->a.dark_rate; }, e_dark, [&] { return kg->a.flat != nullptr; }, e_flat, s, er, ep);
                     }
                 }
                 const unsigned w4 = c2_opaque(cc4);
@@ -1087,9 +1036,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             // live registers; not bound by bytes)
             if constexpr (KFIT) {
                 if constexpr (K64)
-                    (void)load_kd(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn_d, C2Int<KRN>{});
+                    (void)load_k(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn_d, C2Int<KRN>{});
                 else
-                    (void)load_k(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn);
+                    (void)load_k(kg->a.kern, (dbg & 1024) ? R0 : r + 1, true, kn, C2Int<0>{});
             }
             CH_T(6)
             C2_SYNC();

@@ -34,17 +34,7 @@
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// IEEE a/b from the correctly rounded reciprocal rb = 1.0f/b: two Newton corrections with exact (fma)
-// residuals, i.e. the tail of the hardware division macro.  Bit-identical to a/b for finite normal
-// operands and quotients (tools/gpu_checks/divcheck.hip: 1e11 pairs, 0 mismatches); callers fall back
-// to the division operator when b is zero / subnormal / huge.
-__device__ __forceinline__ float div_rcp(float a, float b, float rb) {
-    const float q0 = a * rb;
-    const float r0 = fmaf(-b, q0, a);
-    const float q1 = fmaf(r0, rb, q0);
-    const float r1 = fmaf(-b, q1, a);
-    return fmaf(r1, rb, q1);
-}
+// div_rcp (device_rampfit.h) on a pair of groups
 __device__ __forceinline__ f2 div_rcp2(f2 a, float b, float rb) {
     const f2 nb = {-b, -b}, rr = {rb, rb};
     const f2 q0 = a * rr;

@@ -1,7 +1,13 @@
-// Device functions of the ramp fit (shared by rampfit.hip and chain.hip).
+// Device functions shared by the stage kernels (linearity.hip, ipc.hip, rampfit.hip) and the fused kernel (chain2_kernel.h):
+// every per-pixel formula of the chain is stated once here, in the reference's operation order, and called from both paths.
+//   1. exact short forms, clips                         (used everywhere below)
+//   2. linearity: reference-pixel apply, Legendre series, NO_LIN_CORR rule      -> lin_kernel, the fused kernel's phase A
+//   3. IPC terms: (dy, dx) of term k, term of (dy, dx), terms per source row    -> ipc.hip, the fused kernel's coefficient loads
+//   4. ramp fit: slope -> errors, exact threshold and significance, the fits    -> rampfit.hip, the fused kernel's phases F / T
+//   5. finish: hypot, error split, dark rate, flat                              -> rampfit_kernel, the fused kernel's phase T
 //   utils/fitting.py:89-255   jump_detect -> fit_variant()      (one pass over groups [0,g))
 //   utils/fitting.py:233-241  var_delta_slope in the reference's exact order -> exact_variance()
-// Arithmetic recipe: oracle/rampfit.py.
+// Arithmetic recipes: oracle/refpix.py, oracle/linearity.py, oracle/ipc.py, oracle/rampfit.py, oracle/finish.py.
 #pragma once
 #include "rip_common.h"
 
@@ -56,7 +62,11 @@ __device__ __forceinline__ float rip_rcp_mid(float b) {
     const float e = fmaf(-b, r0, 1.0f);
     return fmaf(e, r0, r0);
 }
-__device__ __forceinline__ float div_rcp_(float a, float b, float rb) {  // a / b from the exact reciprocal (chain_common.h)
+// IEEE a/b from the correctly rounded reciprocal rb = 1.0f/b: two Newton corrections with exact (fma)
+// residuals, i.e. the tail of the hardware division macro.  Bit-identical to a/b for finite normal
+// operands and quotients (tools/gpu_checks/divcheck.hip: 1e11 pairs, 0 mismatches); callers fall back
+// to the division operator when b is zero / subnormal / huge.
+__device__ __forceinline__ float div_rcp(float a, float b, float rb) {
     const float q0 = a * rb;
     const float r0 = fmaf(-b, q0, a);
     const float q1 = fmaf(r0, rb, q0);
@@ -94,6 +104,116 @@ struct GainConst<double> {
     static __device__ __forceinline__ double hi() { return 1e4; }
 };
 
+// ============================================================================================= 2. linearity
+// reference_subtraction.py:123 and :67-68 in f64, cast back to f32 after each step (gen_cal_image.py:534-535, 554-556:
+// image = data - dark ; row / channel subtraction ; + dark).  rc = row correction of (group, y); (m, c) = the channel's line.
+__device__ __forceinline__ float rip_refpix_apply(float S, float dk, double rc, double m, double c, double yd) {
+    float v = S - dk;
+    v = (float)((double)v - rc);
+    const double iel = m * yd + c;
+    v = (float)((double)v - iel);
+    return v + dk;
+}
+
+// constants of degree L: the Legendre recurrence P_{L+1} = c1 z P_L - c2 P_{L-1} and the end-point slope P_L'(1) = chf
+struct RipLegendreK {
+    float c1, c2, chf;
+};
+__device__ __forceinline__ RipLegendreK rip_legendre_k(int L) {
+    RipLegendreK k;
+    k.c1 = (float)((double)(2 * L + 1) / (double)(L + 1));
+    k.c2 = (float)((double)L / (double)(L + 1));
+    k.chf = (float)((double)(L * (L + 1)) / 2.0);
+    return k;
+}
+
+// ipc_linearity.py:192-231 (_lin): the series sum_L cf(L) P_L(z) by the recurrence, every term rounded then added in order of
+// L.  Out of range (|z| > 1: `ex`) P_L is replaced by its linear continuation from the end of the range,
+// (+-1)^L (1 + chf(L) (|z| - 1)); the recurrence runs on regardless.  T holds the operands however the caller keeps them: n()
+// planes, the pixel's coefficient cf(L), the constants c1(L), c2(L), chf(L) of rip_legendre_k.
+template <typename T>
+__device__ __forceinline__ float rip_legendre_series(float z, const T tab, bool &ex) {
+    const float az = fabsf(z);
+    ex = az > 1.0f;
+    const float exc = az - 1.0f;
+    const bool neg = z < 0.0f;
+    float phi = tab.cf(0);
+    float pp = 1.0f, pc = z;
+    for (int L = 1; L < tab.n(); ++L) {
+        float e = 1.0f + tab.chf(L) * exc;
+        e = (neg && (L & 1)) ? -e : e;
+        const float sel = ex ? e : pc;
+        const float term = tab.cf(L) * sel;
+        phi = phi + term;
+        const float u = tab.c1(L) * z;
+        const float pn = u * pc - tab.c2(L) * pp;
+        pp = pc;
+        pc = pn;
+    }
+    return phi;
+}
+
+// ipc_linearity.py:276-344 (multilin): a group outside the range (`ex` of rip_legendre_series) raises NO_LIN_CORR where a correction
+// was attempted -- not the first group under do_not_flag_first.  The chain attempts the groups that are not saturated
+// (gen_cal_image.py:588); q = the group's flags.
+__device__ __forceinline__ bool rip_lin_attempt(uint32_t q) { return (q & DQ_SATURATED) == 0; }
+
+// ============================================================================================= 3. IPC terms
+// ipc_linearity.py:69-94: term k of the forward operator reads the source (y - dy, x - dx) through plane 3 (1 + dy) + (1 + dx) of
+// the (3, 3, ny, nx) kernel; k = 0 is the centre, then (1,0), (-1,0), (0,1), (0,-1), (1,1), (1,-1), (-1,1), (-1,-1).  Macros: the
+// expression is compiled where it stands, as the unrolled term loops of ipc.hip and of the fused kernel always had it (behind a
+// function, inlined later, the same table gave some of those kernels another register assignment).
+#define RIP_IPC_DY(k) (((k) == 1 || (k) == 5 || (k) == 6) ? 1 : ((k) == 2 || (k) == 7 || (k) == 8) ? -1 : 0)
+#define RIP_IPC_DX(k) (((k) == 3 || (k) == 5 || (k) == 7) ? 1 : ((k) == 4 || (k) == 6 || (k) == 8) ? -1 : 0)
+constexpr __host__ __device__ __forceinline__ int rip_ipc_term(int dy, int dx) {  // the term of (dy, dx)
+    for (int k = 0; k < 9; ++k)
+        if (RIP_IPC_DY(k) == dy && RIP_IPC_DX(k) == dx) return k;
+    return -1;
+}
+constexpr unsigned rip_ipc_row_terms(int dy) {  // bit k: term k reads source row y - dy
+    unsigned m = 0;
+    for (int k = 0; k < 9; ++k)
+        if (RIP_IPC_DY(k) == dy) m |= 1u << k;
+    return m;
+}
+static_assert(rip_ipc_row_terms(-1) == 0x184u && rip_ipc_row_terms(0) == 0x019u && rip_ipc_row_terms(1) == 0x062u, "term order");
+// bit k: the source row of term k is active, given that of the rows y + 1, y, y - 1
+__device__ __forceinline__ unsigned rip_ipc_row_mask(bool below, bool same, bool above) {
+    constexpr unsigned mb = rip_ipc_row_terms(-1), ms = rip_ipc_row_terms(0), ma = rip_ipc_row_terms(1);
+    return (below ? mb : 0u) | (same ? ms : 0u) | (above ? ma : 0u);
+}
+
+// ============================================================================================= 4. ramp fit
+// fitting.py (jump_detect): slope s -> dv = clip(s / clip(gain)), the Poisson variance pv = clip(coef dv), and the two errors of
+// the variant.  SHORT (f32 gain): the division and the root in their short exact forms where every lane of the wave is in the
+// validated range (rip_rcp_mid), else the operators -- the same bits either way.
+template <typename GT, bool SHORT = false>
+__device__ __forceinline__ void rip_slope_errors(float s, GT gain, float rn, const RipVariant &v, GT &dv, float &er, float &ep) {
+    const GT gc = clip2<GT>(gain, GainConst<GT>::lo(), GainConst<GT>::hi());
+    GT dvq;
+    if constexpr (SHORT) {
+        if (__all(rip_mid_range(s) && rip_mid_range(gc)))
+            dvq = div_rcp(s, gc, rip_rcp_mid(gc));
+        else
+            dvq = s / gc;
+    } else {
+        dvq = (GT)s / gc;
+    }
+    dv = clip_lo<GT>(dvq, (GT)0);
+    const GT pv = clip_lo<GT>((GT)v.coef * dv, (GT)0);
+    er = rn * v.rfac;
+    if constexpr (SHORT) {
+        if (__all(pv == 0.0f || rip_mid_range(pv)))  // rip_sqrt_mid(0) = 0
+            ep = rip_sqrt_mid(pv);
+        else
+            ep = sqrtf(pv);
+    } else if constexpr (sizeof(GT) == 4) {
+        ep = sqrtf(pv);
+    } else {
+        ep = (float)sqrt(pv);
+    }
+}
+
 // var_delta_slope exactly as fitting.py:233-241 (order of accumulation and dtype of every term)
 template <typename GT>
 __device__ __noinline__ double exact_variance(const RipPlanHeader *__restrict__ h, const float *__restrict__ kv, int g,
@@ -120,43 +240,70 @@ __device__ __noinline__ double exact_variance(const RipPlanHeader *__restrict__ 
     return var;
 }
 
-// one jump_detect pass on the ramp D[t*STRIDE] (LDS column of this thread); ORs JUMP_DET into J[i*STRIDE] when `flag`
+// The jump threshold in the reference's exact operations (fitting.py: SthreshA + (SthreshB - SthreshA) log(xc / IthreshA) /
+// log(IthreshB / IthreshA) with xc the slope clipped to [IthreshA, IthreshB]).  KSPACE: the plan's f64 constants are read through
+// the constant address space (RIP_K), where they are used -- handing them in by value would move their loads in front of the
+// logarithm, and the fused kernel's register assignment with them.
+template <bool KSPACE>
+__device__ __forceinline__ double rip_exact_sth(float xc, float ia, const RipPlanHeader *__restrict__ h) {
+    const auto k = [](const double &x) -> double {
+        if constexpr (KSPACE)
+            return KLD(x);
+        else
+            return x;
+    };
+    const float lx = log_f32(xc / ia);
+    return k(h->sa) + k(h->dsb) * ((double)lx / k(h->loglen));
+}
+
+// The significance of the difference d[j] - d[i] over dt in the reference's exact operations (fitting.py:225-246): a jump
+// where (double)sme > sth.  s2 = the squared read noise.
+template <typename GT>
+__device__ __forceinline__ float rip_exact_sme(const RipPlanHeader *__restrict__ h, const float *__restrict__ kv, int g, int i,
+                                               int j, float dt, float di, float dj, float s, GT dv, float s2) {
+    const float num = dj - di;
+    const float delta = num / dt - s;
+    const double var = exact_variance<GT>(h, kv, g, i, j, dt, dv, s2);
+    return delta / (float)sqrt(var);
+}
+
+// head of a jump_detect pass on the ramp D[t*STRIDE] (LDS column of this thread): slope of the variant's weights, dv, errors
+template <typename GT, int STRIDE>
+__device__ __forceinline__ void fit_head(const float *D, const RipVariant &v, const float *__restrict__ kv, GT gain, float rn,
+                                         float &s_out, GT &dv, float &er, float &ep) {
+    const float d1 = D[STRIDE];
+    float s = 0.0f;
+    for (int t = 0; t < v.g; ++t) {
+        float diff = D[t * STRIDE] - d1;
+        float prod = kv[t] * diff;
+        s = s + prod;
+    }
+    s_out = s;
+    rip_slope_errors<GT>(s, gain, rn, v, dv, er, ep);
+}
+
+// one jump_detect pass on the ramp D[t*STRIDE]; ORs JUMP_DET into J[i*STRIDE] when `flag`
 template <typename GT, int STRIDE>
 __device__ __forceinline__ void fit_variant(const float *D, uint8_t *J, const RipPlanHeader *__restrict__ h,
                                             const RipVariant v, const float *__restrict__ kv,
                                             const RipDiff *__restrict__ df, GT gain, float rn, bool flag,
                                             double guard, float &s_out, float &er_out, float &ep_out) {
-    const int g = v.g;
-    const float d1 = D[STRIDE];
-    float s = 0.0f;
-    for (int t = 0; t < g; ++t) {
-        float diff = D[t * STRIDE] - d1;
-        float prod = kv[t] * diff;
-        s = s + prod;
-    }
-    GT gc = clip2<GT>(gain, GainConst<GT>::lo(), GainConst<GT>::hi());
-    GT dv = clip_lo<GT>((GT)s / gc, (GT)0);
-    GT pv = clip_lo<GT>((GT)v.coef * dv, (GT)0);
-    float ep;
-    if constexpr (sizeof(GT) == 4)
-        ep = sqrtf(pv);
-    else
-        ep = (float)sqrt(pv);
+    float s;
+    GT dv;
+    fit_head<GT, STRIDE>(D, v, kv, gain, rn, s, dv, er_out, ep_out);
     s_out = s;
-    er_out = rn * v.rfac;
-    ep_out = ep;
     if (!flag) return;
 
     float xc = clip2<float>(s, h->ia, h->ib);
-    float lx = log_f32(xc / h->ia);
-    double sth = h->sa + h->dsb * ((double)lx / h->loglen);
+    double sth = rip_exact_sth<false>(xc, h->ia, h);
     float sth32 = (float)sth;
     float band = (float)(guard * fabs(sth)) + 0.0f;
     const float s2 = rn * rn;
     const float dv32 = (float)dv;
     for (int k = 0; k < v.ndiff; ++k) {
         const RipDiff r = df[k];
-        float num = D[r.j * STRIDE] - D[r.i * STRIDE];
+        const float di = D[r.i * STRIDE], dj = D[r.j * STRIDE];
+        float num = dj - di;
         float delta = num / r.dt - s;
         float var32 = r.A * s2 + r.B * dv32;
         float sm = delta / sqrtf(var32);
@@ -164,8 +311,7 @@ __device__ __forceinline__ void fit_variant(const float *D, uint8_t *J, const Ri
         if (fabsf(sm - sth32) > band) {
             hit = sm > sth32;
         } else {  // within the guard band of the threshold (or NaN): redo in the reference's exact order
-            double var = exact_variance<GT>(h, kv, g, r.i, r.j, r.dt, dv, s2);
-            float sme = delta / (float)sqrt(var);
+            const float sme = rip_exact_sme<GT>(h, kv, v.g, r.i, r.j, r.dt, di, dj, s, dv, s2);
             hit = (double)sme > sth;
         }
         if (hit) J[r.i * STRIDE] |= (uint8_t)DQ_JUMP_DET;
@@ -215,12 +361,13 @@ __device__ __forceinline__ void rampfit_pixel(const float *D, const uint8_t *Q, 
     pdq_out = (pdq_in & DQ_REFERENCE_PIXEL) ? pdq_in : (pdq_in | pdq2);
 }
 
-// gen_cal_image.py:458-475 (err = hypot, var_poisson, trim + zero border), :213-229 (dark rate on the active
-// region), :607-613 (error split), :616-629 (flat flags + division).  Pointers may be null (step skipped).
-__device__ __forceinline__ void finish_pixel(bool active, size_t p, const float *__restrict__ dark_rate,
-                                             const uint32_t *__restrict__ dark_dq, const float *__restrict__ flat,
-                                             const uint32_t *__restrict__ flat_flags, float &s, float &er, float &ep,
-                                             uint32_t &pdq) {
+// ============================================================================================= 5. finish
+// gen_cal_image.py:458-475 (err = hypot, var_poisson, trim + zero border), :213-229 (dark rate on the active region), :607-613
+// (error split), :616-629 (division by the flat).  has_dark() / has_flat(): is the step taken?  Asked where the reference takes
+// the step (the fused kernel reads the answer from its argument block there, not before).
+template <typename HD, typename HF>
+__device__ __forceinline__ void rip_finish(bool active, HD has_dark, float dark, HF has_flat, float flat, float &s, float &er,
+                                           float &ep) {
     float err = hypot_f32(er, ep);
     float vp = ep * ep;
     if (!active) {
@@ -228,21 +375,29 @@ __device__ __forceinline__ void finish_pixel(bool active, size_t p, const float 
         err = 0.0f;
         vp = 0.0f;
     }
-    if (active && dark_rate) s = s - dark_rate[p];
-    if (active && dark_dq) pdq |= dark_dq[p];
+    if (has_dark()) s = s - dark;
     float ep2 = sqrtf(vp);
-    float e2 = err * err;
-    float p2 = ep2 * ep2;
+    const float e2 = err * err;
+    const float p2 = ep2 * ep2;
     float er2 = sqrtf(clip_lo<float>(e2 - p2, 0.0f));
-    if (flat) {
-        if (flat_flags) pdq |= flat_flags[p];
-        const float f = flat[p];
-        s = s / f;
-        er2 = er2 / f;
-        ep2 = ep2 / f;
+    if (has_flat()) {
+        s = s / flat;
+        er2 = er2 / flat;
+        ep2 = ep2 / flat;
     }
     er = er2;
     ep = ep2;
+}
+// the stage kernel's form: the planes from global memory, pointers may be null (step skipped); :616-629 also ORs the flat flags
+__device__ __forceinline__ void finish_pixel(bool active, size_t p, const float *__restrict__ dark_rate,
+                                             const uint32_t *__restrict__ dark_dq, const float *__restrict__ flat,
+                                             const uint32_t *__restrict__ flat_flags, float &s, float &er, float &ep,
+                                             uint32_t &pdq) {
+    const bool has_dark = active && dark_rate;
+    if (active && dark_dq) pdq |= dark_dq[p];
+    if (flat && flat_flags) pdq |= flat_flags[p];
+    rip_finish(active, [&] { return has_dark; }, has_dark ? dark_rate[p] : 0.0f, [&] { return flat != nullptr; }, flat ? flat[p] : 1.0f, s,
+               er, ep);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -269,12 +424,9 @@ __device__ __forceinline__ void fit_full_regs(const float (&d)[G], const RipPlan
         const float prod = KLD(kv[t]) * diff;
         s = s + prod;
     }
-    const float gc = clip2<float>(gain, 1e-4f, 1e4f);
-    const float dv = clip_lo<float>(s / gc, 0.0f);
-    const float pv = clip_lo<float>(v.coef * dv, 0.0f);
+    float dv;
+    rip_slope_errors<float>(s, gain, rn, v, dv, er_out, ep_out);
     s_out = s;
-    er_out = rn * v.rfac;
-    ep_out = sqrtf(pv);
     if (!__any(flag)) return;
 
     const float xc = clip2<float>(s, KLD(h->ia), KLD(h->ib));
@@ -312,11 +464,8 @@ __device__ __forceinline__ void fit_full_regs(const float (&d)[G], const RipPlan
             const bool unsure = force_exact || !(fabsf(sm - sth32) > band);
             if (__any(unsure && flag)) {
                 if (unsure) {
-                    const float lxe = log_f32(xc / KLD(h->ia));
-                    const double sth = KLD(h->sa) + KLD(h->dsb) * ((double)lxe / KLD(h->loglen));
-                    const float de = num / r.dt - s;
-                    const double var = exact_variance<float>(h, kv, G, r.i, r.j, r.dt, dv, s2);
-                    const float sme = de / (float)sqrt(var);
+                    const double sth = rip_exact_sth<true>(xc, KLD(h->ia), h);
+                    const float sme = rip_exact_sme<float>(h, kv, G, r.i, r.j, r.dt, d[i], d[j], s, dv, s2);
                     hit = (double)sme > sth;
                 }
             }
@@ -373,32 +522,23 @@ struct RipFitState {
     bool live;                 // wave-uniform: some lane of the wave keeps jump flags
 };
 
-// where the first half reads the dense per-plan table from: the device copy through scalar loads
-struct RipDenseK {
-    const RipDense *dn;
-    __device__ __forceinline__ float k2(int t) const { return KLD(dn->K2[t]); }
-    __device__ __forceinline__ uint32_t valid() const { return KLD(dn->valid); }
-    __device__ __forceinline__ float amin() const { return KLD(dn->amin); }
-    __device__ __forceinline__ void pair(RipDensePair &r, int ps) const { rip_load_pair(r, dn, ps); }
-};
-
 // first half: slope, errors, threshold, approximate significance of every tested difference
 // VALID != 0: the tested differences are known at compile time (no plan-uniform branches: the eight difference
 // slots become one basic block the scheduler can interleave)
-template <int G, uint32_t VALID, typename TAB, bool SKIP0 = false>
-__device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
-                                                const TAB tabsrc, float gain, float rn, bool flag, double guard,
-                                                RipFitState &st) {
+template <int G, uint32_t VALID = 0u, bool SKIP0 = false>
+__device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
+                                              const RipDense *__restrict__ dn, float gain, float rn, bool flag, double guard,
+                                              RipFitState &st) {
     constexpr int GP = (G + 1) / 2;  // odd G: the second half of the last pair is dead (no weight, no tested difference)
     constexpr int NS = 2 * GP;       // pair slots
     // scalar loads of the weights and of the first difference slot are issued before the slope arithmetic; slot
     // ps+1 is requested while slot ps is evaluated (scalar loads return out of order: every wait is lgkmcnt(0))
     float k2[G];
 #pragma unroll
-    for (int t = 0; t < G; ++t) k2[t] = tabsrc.k2(t);
-    const uint32_t valid = VALID ? VALID : tabsrc.valid();
+    for (int t = 0; t < G; ++t) k2[t] = KLD(dn->K2[t]);
+    const uint32_t valid = VALID ? VALID : KLD(dn->valid);
     RipDensePair tab[2];
-    tabsrc.pair(tab[0], 0);
+    rip_load_pair(tab[0], dn, 0);
     const float d1 = dA[0].y;
     const rf2 d11 = {d1, d1};
     float s = 0.0f;
@@ -424,21 +564,9 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
         s = s + prod.x;
         s = s + prod.y;
     }
-    const float gc = clip2<float>(gain, 1e-4f, 1e4f);
-    // s / gc and sqrt(pv): short exact forms when every lane is in their validated range (see rip_rcp_mid)
-    float dvq;
-    if (__all(rip_mid_range(s) && rip_mid_range(gc)))
-        dvq = div_rcp_(s, gc, rip_rcp_mid(gc));
-    else
-        dvq = s / gc;
-    const float dv = clip_lo<float>(dvq, 0.0f);
-    const float pv = clip_lo<float>(v.coef * dv, 0.0f);
+    float dv;
+    rip_slope_errors<float, true>(s, gain, rn, v, dv, st.er, st.ep);
     st.s = s;
-    st.er = rn * v.rfac;
-    if (__all(pv == 0.0f || rip_mid_range(pv)))  // rip_sqrt_mid(0) = 0
-        st.ep = rip_sqrt_mid(pv);
-    else
-        st.ep = sqrtf(pv);
     st.dv = dv;
     st.s2 = rn * rn;
     st.jfast = 0;
@@ -463,7 +591,7 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
     const float s2 = st.s2;
     const float s8 = fabsf(s) * 8.1e-7f;
     const float thp = sth32 + band0, thm = sth32 - band0;
-    const float rsmax = __frsqrt_rn(tabsrc.amin() * s2) * 1.000001f;
+    const float rsmax = __frsqrt_rn(KLD(dn->amin) * s2) * 1.000001f;
     const bool pass = fmaf(s8, rsmax, band0) <= 0.5f * sth32;  // false for NaN, for amin == 0 and for sth32 <= 0
     const bool lane_exact = !(guard < 1e300) || !pass;
     uint32_t jfast = 0, unsure_mask = 0;
@@ -472,7 +600,7 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
     for (int p = 0; p < GP; ++p) dB[p] = rf2{dA[p].y, (p + 1 < GP) ? dA[p + 1].x : 0.0f};
 #pragma unroll
     for (int ps = 0; ps < NS; ++ps) {
-        if (ps + 1 < NS) tabsrc.pair(tab[(ps + 1) & 1], ps + 1);
+        if (ps + 1 < NS) rip_load_pair(tab[(ps + 1) & 1], dn, ps + 1);
         const int ip = ps / 2, di = (ps & 1) + 1;
         const uint32_t vbits = (valid >> (2 * ps)) & 3u;
         if (vbits == 0) continue;  // plan-uniform
@@ -504,13 +632,6 @@ __device__ __forceinline__ void fit_full_pk_a_t(const rf2 (&dA)[(G + 1) / 2], co
     st.unsure = unsure_mask;
 }
 
-template <int G, uint32_t VALID = 0u, bool SKIP0 = false>
-__device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], const RipFitConst fc, const RipVariant v,
-                                              const RipDense *__restrict__ dn, float gain, float rn, bool flag,
-                                              double guard, RipFitState &st) {
-    fit_full_pk_a_t<G, VALID, RipDenseK, SKIP0>(dA, fc, v, RipDenseK{dn}, gain, rn, flag, guard, st);
-}
-
 // second half: exact re-evaluation where the approximate significance was not decisive, jump mask
 template <int G>
 __device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[(G + 1) / 2], const RipPlanHeader *__restrict__ h,
@@ -525,8 +646,7 @@ __device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[(G + 1) / 2], cons
     // differences whose approximate significance is within its error band of the threshold (or NaN): redo them in
     // the reference's exact operation order.  Rare; one wave-uniform test covers the whole pixel.
     if (__any(unsure_mask != 0 && flag)) {
-        const float lxe = log_f32(xc / fc.ia);
-        const double sth = KLD(h->sa) + KLD(h->dsb) * ((double)lxe / KLD(h->loglen));
+        const double sth = rip_exact_sth<true>(xc, fc.ia, h);
         for (int bit = 0; bit < 4 * GP; ++bit) {
             if (!__any((unsure_mask >> bit) & 1u)) continue;
             if ((unsure_mask >> bit) & 1u) {
@@ -538,9 +658,7 @@ __device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[(G + 1) / 2], cons
                     di_ = (rd.i == 2 * p) ? dA[p].x : (rd.i == 2 * p + 1) ? dA[p].y : di_;
                     dj_ = (rd.j == 2 * p) ? dA[p].x : (rd.j == 2 * p + 1) ? dA[p].y : dj_;
                 }
-                const float de = (dj_ - di_) / rd.dt - s;
-                const double varx = exact_variance<float>(h, kv, G, rd.i, rd.j, rd.dt, dv, s2);
-                const float smx = de / (float)sqrt(varx);
+                const float smx = rip_exact_sme<float>(h, kv, G, rd.i, rd.j, rd.dt, di_, dj_, s, dv, s2);
                 const bool hitx = (double)smx > sth;
                 jfast = hitx ? (jfast | (1u << bit)) : (jfast & ~(1u << bit));
             }
@@ -555,20 +673,6 @@ __device__ __forceinline__ void fit_full_pk_b(const rf2 (&dA)[(G + 1) / 2], cons
             if ((four & 2u) || (four & 8u)) jmask |= 1u << (2 * ip + 1);
         }
     }
-}
-
-template <int G>
-__device__ __forceinline__ void fit_full_pk(const rf2 (&dA)[(G + 1) / 2], const RipPlanHeader *__restrict__ h,
-                                            const RipFitConst fc, const RipVariant v, const RipDense *__restrict__ dn,
-                                            const float *__restrict__ kv, const RipDiff *__restrict__ df, float gain,
-                                            float rn, bool flag, double guard, float &s_out, float &er_out,
-                                            float &ep_out, uint32_t &jmask) {
-    RipFitState st;
-    fit_full_pk_a<G>(dA, fc, v, dn, gain, rn, flag, guard, st);
-    fit_full_pk_b<G>(dA, h, fc, dn, kv, df, flag, st, jmask);
-    s_out = st.s;
-    er_out = st.er;
-    ep_out = st.ep;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -605,31 +709,10 @@ __device__ __forceinline__ void trunc_layers(const float (&d)[GA], const uint32_
     }
 }
 
-// flag propagation of fitting.py:339-353 from registers; writes the updated group flags when gdq_out != null
-template <int G>
-__device__ __forceinline__ uint32_t propagate_flags(const uint32_t (&qe)[G], uint32_t jmask, int start, uint32_t pdq_in,
-                                                    uint8_t *gdq_out, unsigned gstride, unsigned lane_off = 0) {
-    uint32_t or_unsat = 0, any_sat = 0;
-    bool all_dnu = true;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const uint32_t rq = qe[g] | (((jmask >> g) & 1u) ? DQ_JUMP_DET : 0u);
-        if (gdq_out) *(gdq_out + (size_t)g * gstride + lane_off) = (uint8_t)rq;  // uniform base + per-lane offset
-        if ((rq & DQ_SATURATED) == 0) or_unsat |= rq;
-        any_sat |= rq & DQ_SATURATED;
-        all_dnu = all_dnu && ((rq & DQ_DO_NOT_USE) != 0);
-    }
-    uint32_t pdq2 = or_unsat & ~DQ_DO_NOT_USE;
-    if (all_dnu) pdq2 |= DQ_DO_NOT_USE;
-    const uint32_t q_early = start ? qe[(G > 2) ? 2 : G - 1] : qe[1];  // rdq[1 + start]
-    if (q_early & DQ_SATURATED) pdq2 |= DQ_DO_NOT_USE;
-    pdq2 |= any_sat;
-    return (pdq_in & DQ_REFERENCE_PIXEL) ? pdq_in : (pdq_in | pdq2);
-}
-
 // ---------------------------------------------------------------------------------------------
-// propagate_flags on the pixel's group flags PACKED four to a word (w0 = groups 0-3, w1 = groups 4-7, bytes of
-// groups >= G are zero): the same results with byte-parallel logic instead of G unpack / test / select sequences.
+// Flag propagation of fitting.py:339-353 (as at the end of rampfit_pixel) on the pixel's group flags PACKED four to a word
+// (w0 = groups 0-3, w1 = groups 4-7, bytes of groups >= G are zero): byte-parallel logic instead of G unpack / test / select
+// sequences.
 //   gdq_row  uniform byte pointer to element (group 0, row, column 0) of the output group flags, or null
 __device__ __forceinline__ uint32_t rip_spread_bit1(uint32_t t) {  // bytes holding 0x02 -> 0xFF, others (0x00) -> 0x00
     t |= t >> 1;
@@ -640,7 +723,7 @@ __device__ __forceinline__ uint32_t rip_spread_bit1(uint32_t t) {  // bytes hold
 template <int G>
 __device__ __forceinline__ uint32_t propagate_flags_packed(const uint32_t (&w)[(G + 3) / 4], uint32_t jmask, int start,
                                                            uint32_t pdq_in, uint8_t *gdq_row, unsigned gstride,
-                                                           unsigned lane_off, uint32_t *rq_out = nullptr) {
+                                                           unsigned lane_off) {
     static_assert(G > 4 && G <= 16, "flag words");
     constexpr int QW = (G + 3) / 4;
     // bytes of the last word beyond group G-1: missing groups count as DO_NOT_USE in the all-groups test
@@ -649,10 +732,6 @@ __device__ __forceinline__ uint32_t propagate_flags_packed(const uint32_t (&w)[(
 #pragma unroll
     for (int i = 0; i < QW; ++i)  // bit g of jmask -> JUMP_DET (0x04) of byte g
         rq[i] = w[i] | ((__umul24((jmask >> (4 * i)) & 0xFu, 0x00204081u) & 0x01010101u) << 2);
-    if (rq_out) {  // the updated group flags, still packed (the caller stores them later)
-#pragma unroll
-        for (int i = 0; i < QW; ++i) rq_out[i] = rq[i];
-    }
     if (gdq_row) {  // uniform
         uint8_t *p = gdq_row;
 #pragma unroll

@@ -12,7 +12,7 @@
 // to exploit with matrix cores: this is a 5x5-footprint stencil bound by HBM (9 coefficient planes
 // + the cube), tiled through LDS.  Per destination pixel the 9 coefficients are loaded ONCE into
 // registers and reused for both Neumann iterations and for all groups of the cube.
-#include "rip_common.h"
+#include "device_rampfit.h"   // section 3: the term table RIP_IPC_DY / RIP_IPC_DX, shared with the fused kernel
 
 #define IPC_TW 64
 #define IPC_TH 16
@@ -23,9 +23,11 @@
 #define IPC_OH (IPC_TH + 2)
 #define IPC_RING (2 * IPC_OW + 2 * IPC_TH)  // 164 positions of the halo-1 ring
 
-// (dy,dx) of term k (k = 0 is the centre); plane index in the (3,3) kernel = 3*(1+dy)+(1+dx)
-__device__ __constant__ int8_t IPC_DY[9] = {0, 1, -1, 0, 0, 1, 1, -1, -1};
-__device__ __constant__ int8_t IPC_DX[9] = {0, 0, 0, 1, -1, 1, -1, 1, -1};
+// (dy, dx) of term k for the image kernels, which walk the terms through constant memory: the same table
+__device__ __constant__ int8_t IPC_DY[9] = {RIP_IPC_DY(0), RIP_IPC_DY(1), RIP_IPC_DY(2), RIP_IPC_DY(3), RIP_IPC_DY(4),
+                                            RIP_IPC_DY(5), RIP_IPC_DY(6), RIP_IPC_DY(7), RIP_IPC_DY(8)};
+__device__ __constant__ int8_t IPC_DX[9] = {RIP_IPC_DX(0), RIP_IPC_DX(1), RIP_IPC_DX(2), RIP_IPC_DX(3), RIP_IPC_DX(4),
+                                            RIP_IPC_DX(5), RIP_IPC_DX(6), RIP_IPC_DX(7), RIP_IPC_DX(8)};
 
 template <typename A, typename B>
 struct Promote {
@@ -51,8 +53,8 @@ __device__ __forceinline__ T fwd_at(const ST *S, int stride, const KT (&kk)[9], 
     T acc = (T)S[0] * (T)kk[0];
 #pragma unroll
     for (int k = 1; k < 9; ++k) {
-        const int dy = (k == 1 || k == 5 || k == 6) ? 1 : (k == 2 || k == 7 || k == 8) ? -1 : 0;
-        const int dx = (k == 3 || k == 5 || k == 7) ? 1 : (k == 4 || k == 6 || k == 8) ? -1 : 0;
+        const int dy = RIP_IPC_DY(k);
+        const int dx = RIP_IPC_DX(k);
         T prod = (T)S[-dy * stride - dx] * (T)kk[k];
         T sum = acc + prod;
         acc = (valid >> k) & 1u ? sum : acc;
@@ -68,8 +70,8 @@ __device__ __forceinline__ unsigned load_coeffs(const KT *__restrict__ kern, siz
     const bool dest_ok = (y >= y0 && y < y1 && x >= x0 && x < x1);
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
-        const int dy = (k == 1 || k == 5 || k == 6) ? 1 : (k == 2 || k == 7 || k == 8) ? -1 : 0;
-        const int dx = (k == 3 || k == 5 || k == 7) ? 1 : (k == 4 || k == 6 || k == 8) ? -1 : 0;
+        const int dy = RIP_IPC_DY(k);
+        const int dx = RIP_IPC_DX(k);
         const int sy = y - dy, sx = x - dx;
         const bool ok = dest_ok && sy >= y0 && sy < y1 && sx >= x0 && sx < x1;
         kk[k] = ok ? kern[(size_t)(3 * (1 + dy) + (1 + dx)) * plane + (size_t)sy * nx + sx] : (KT)0;

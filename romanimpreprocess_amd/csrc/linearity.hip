@@ -9,19 +9,25 @@
 //        utils/reference_subtraction.py:123 and :67-68 is applied here per pixel)
 //   L1_to_L2/gen_cal_image.py:559-565          data[act] -= biascorr
 //   utils/ipc_linearity.py:192-231, 276-344    _lin, multilin ; gen_cal_image.py:588 pdq |= dq_lin
-// Arithmetic recipe: oracle/refpix.py, oracle/linearity.py.
+// The per-pixel formulas are those of device_rampfit.h (section 2), shared with the fused kernel.
 //
 // Roofline: HBM.  Algorithmic bytes per pixel = G*(2|4 data + 4 dark + 4 bias + 1 gdq + 4 phi)
 // + 4*(nplanes + 3) + 4 (lin dq) + 4 + 4 (pdq in/out).
-#include "rip_common.h"
+#include "device_rampfit.h"
 
 #define LIN_THREADS 256
 #define LIN_MAX_PLANES 32
 
-template <typename T>
-__device__ __forceinline__ T clip2(T x, T lo, T hi) {
-    return x < lo ? lo : (x > hi ? hi : x);
-}
+// operands of rip_legendre_series in LDS: the pixel's coefficients [plane][thread], the constants per degree
+struct LinLds {
+    const float *CL, *C1, *C2, *CH;
+    int nplanes;
+    __device__ __forceinline__ int n() const { return nplanes; }
+    __device__ __forceinline__ float cf(int L) const { return CL[L * LIN_THREADS]; }
+    __device__ __forceinline__ float c1(int L) const { return C1[L]; }
+    __device__ __forceinline__ float c2(int L) const { return C2[L]; }
+    __device__ __forceinline__ float chf(int L) const { return CH[L]; }
+};
 
 template <typename DT>
 __global__ __launch_bounds__(LIN_THREADS) void lin_kernel(LinArgs a) {
@@ -36,10 +42,10 @@ __global__ __launch_bounds__(LIN_THREADS) void lin_kernel(LinArgs a) {
     const size_t p = (size_t)blockIdx.x * LIN_THREADS + tid;
     const bool lin = a.coefs != nullptr;
     if (lin && tid < a.nplanes && tid >= 1) {
-        const int L = tid;
-        C1[L] = (float)((double)(2 * L + 1) / (double)(L + 1));
-        C2[L] = (float)((double)L / (double)(L + 1));
-        CH[L] = (float)((double)(L * (L + 1)) / 2.0);
+        const RipLegendreK k = rip_legendre_k(tid);
+        C1[tid] = k.c1;
+        C2[tid] = k.c2;
+        CH[tid] = k.chf;
     }
     __syncthreads();
     if (p >= npix) return;
@@ -62,14 +68,8 @@ __global__ __launch_bounds__(LIN_THREADS) void lin_kernel(LinArgs a) {
     for (int g = 0; g < a.ngrp; ++g) {
         float S = (float)data[(size_t)g * npix + p];
         if (a.rowcorr) {
-            // reference_subtraction.py:123 and :67-68 in f64, cast back to f32 after each step
-            const float dk = a.dark_data[(size_t)g * npix + p];
-            float v = S - dk;
-            v = (float)((double)v - a.rowcorr[(size_t)g * a.ny + y]);
             const double *ln = a.lines + ((size_t)g * nch + x / RIP_CW) * 2;
-            const double iel = ln[0] * (double)y + ln[1];
-            v = (float)((double)v - iel);
-            S = v + dk;
+            S = rip_refpix_apply(S, a.dark_data[(size_t)g * npix + p], a.rowcorr[(size_t)g * a.ny + y], ln[0], ln[1], (double)y);
         }
         if (a.bias && active) S = S - a.bias[(size_t)g * npix + p];
         float val = S;
@@ -79,29 +79,14 @@ __global__ __launch_bounds__(LIN_THREADS) void lin_kernel(LinArgs a) {
             float z = -1.0f + t / span;
             const bool first = (g == 0) && a.do_not_flag_first;
             if (first) z = clip2<float>(z, -1.0f, 1.0f);
-            const float az = fabsf(z);
-            const bool ex = az > 1.0f;
-            const float exc = az - 1.0f;
-            const bool neg = z < 0.0f;
-            float phi = CL[tid];
-            float pp = 1.0f, pc = z;
-            for (int L = 1; L < a.nplanes; ++L) {
-                float e = 1.0f + CH[L] * exc;
-                e = (neg && (L & 1)) ? -e : e;
-                const float sel = ex ? e : pc;
-                const float term = CL[L * LIN_THREADS + tid] * sel;
-                phi = phi + term;
-                const float u = C1[L] * z;
-                const float pn = u * pc - C2[L] * pp;
-                pp = pc;
-                pc = pn;
-            }
+            bool ex;
+            const float phi = rip_legendre_series(z, LinLds{CL + tid, C1, C2, CH, a.nplanes}, ex);
             val = ((dq & bad) == 0) ? phi : (S - sref);
             if (!first && ex) {
-                bool attempt = true;
+                bool attempt = true;   // attempt_corr: every group, the groups the caller marks, or the unsaturated ones
                 if (a.gdq) {
                     const uint8_t q = a.gdq[(size_t)g * npix + p];
-                    attempt = a.gdq_is_attempt ? (q != 0) : ((q & DQ_SATURATED) == 0);
+                    attempt = a.gdq_is_attempt ? (q != 0) : rip_lin_attempt(q);
                 }
                 if (attempt) dq |= DQ_NO_LIN_CORR;
             }

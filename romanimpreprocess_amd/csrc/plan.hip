@@ -124,7 +124,7 @@ int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
             dn.pairs[ps].inv_dt[e] = df.inv_dt;
             dn.pairs[ps].A[e] = df.A;
             dn.pairs[ps].B[e] = df.B;
-            // acceptance factors of the packed fast path (device_rampfit.h, fit_full_pk): r = relerr + 4.1e-7 covers
+            // acceptance factors of the packed fast path (device_rampfit.h, fit_full_pk_a): r = relerr + 4.1e-7 covers
             // the variance approximation and the part of the difference's rounding that scales with the significance
             const double r = (double)df.relerr + 4.1e-7;
             if (r < 9.9e-3) {

@@ -107,34 +107,16 @@ __global__ __launch_bounds__(RF_THREADS) void jumpdetect_kernel(const float *__r
     const RipDiff *df = diffs + v.diff_ofs;
     const GT gain = reinterpret_cast<const GT *>(gain_)[p];
     const float rn = read_noise[p];
-    const float d1 = D[RF_THREADS];
-    float s = 0.0f;
-    for (int t = 0; t < v.g; ++t) {
-        const float diff = D[t * RF_THREADS] - d1;
-        const float prod = kv[t] * diff;
-        s = s + prod;
-    }
-    const GT gc = clip2<GT>(gain, GainConst<GT>::lo(), GainConst<GT>::hi());
-    const GT dv = clip_lo<GT>((GT)s / gc, (GT)0);
-    const GT pv = clip_lo<GT>((GT)v.coef * dv, (GT)0);
-    float ep;
-    if constexpr (sizeof(GT) == 4)
-        ep = sqrtf(pv);
-    else
-        ep = (float)sqrt(pv);
+    float s, er, ep;
+    GT dv;
+    fit_head<GT, RF_THREADS>(D, v, kv, gain, rn, s, dv, er, ep);
     slope[p] = s;
-    err_read[p] = rn * v.rfac;
+    err_read[p] = er;
     err_poisson[p] = ep;
-    const float xc = clip2<float>(s, h->ia, h->ib);
-    const float lx = log_f32(xc / h->ia);
-    const double sth = h->sa + h->dsb * ((double)lx / h->loglen);
-    const float s2 = rn * rn;
+    const double sth = rip_exact_sth<false>(clip2<float>(s, h->ia, h->ib), h->ia, h);
     for (int k = 0; k < v.ndiff; ++k) {
         const RipDiff r = df[k];
-        const float num = D[r.j * RF_THREADS] - D[r.i * RF_THREADS];
-        const float delta = num / r.dt - s;
-        const double var = exact_variance<GT>(h, kv, v.g, r.i, r.j, r.dt, dv, s2);
-        const float sme = delta / (float)sqrt(var);
+        const float sme = rip_exact_sme<GT>(h, kv, v.g, r.i, r.j, r.dt, D[r.i * RF_THREADS], D[r.j * RF_THREADS], s, dv, rn * rn);
         smap[(size_t)k * npix + p] = sme;
         if (active && (double)sme > sth) rdq[(size_t)r.i * npix + p] |= (uint8_t)DQ_JUMP_DET;
     }

@@ -50,8 +50,8 @@ struct RipPlanHeader {
     float tbar[RIP_MAX_GROUPS], tau[RIP_MAX_GROUPS], nreads[RIP_MAX_GROUPS];  // nreads as f32(N)
 };
 
-// Dense, compile-time-indexable view of the FULL-ramp variant for the register-resident fit
-// (fit_full_regs): pair slot ps = 2*(i/2) + (di-1) holds the differences (i, i+di) and (i+1, i+1+di), i even.
+// Dense, compile-time-indexable view of the FULL-ramp variant for the packed register-resident fit
+// (fit_full_pk_a / fit_full_pk_b, device_rampfit.h): pair slot ps = 2*(i/2) + (di-1) holds the differences (i, i+di) and (i+1, i+1+di), i even.
 struct RipDensePair {
     float inv_dt[2], A[2], B[2];  // per element e: difference (i+e, i+e+di)
     float k1[2];                   // k1 >= 1/(1-r), r = relative error bound of the approximate significance (2 - k1 <= 1/(1+r))

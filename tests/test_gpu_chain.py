@@ -54,6 +54,74 @@ def test_chain_vs_oracle(name, shape, rp, p, gdt, kdt, fused):
         assert np.all(np.abs(got2["err_poisson"] - ref["err_poisson"]) <= 1e-5 * tot + 1e-12)
 
 
+NO_LIN_CORR = 1 << 20
+NARROWED = [
+    # name, (ny, nx), read pattern, p_order, gain dtype, ipc dtype: the 256-column form, a narrow form with the partial K ring,
+    # the 16-group form
+    ("g8_f32", (64, 256), synth.READ_PATTERN_8, 8, np.float32, np.float32),
+    ("g6_k64", (48, 384), synth.READ_PATTERN_6, 3, np.float32, np.float64),
+    ("g16_f32", (40, 128), synth.READ_PATTERN_16, 10, np.float32, np.float32),
+]
+
+
+def narrow_linearity_range(cal, ramp, rng, margin=16.0):
+    """Narrows [Smin, Smax] on about 2 % of the pixels so that some of their groups leave it: on half of them Smax drops below
+    the raw value of the middle group (later groups lie above the range), on the other half Smin rises above the raw value of the
+    second group (early groups lie below it); Smax - Smin stays >= 100.  Returns the masks (upper, lower) of the two halves."""
+    lin = cal["linearitylegendre"]
+    raw = ramp["data"].astype(np.float32)
+    pick = rng.random(raw.shape[1:]) < 0.02
+    upper = pick & (rng.random(raw.shape[1:]) < 0.5)
+    lower = pick & ~upper
+    smin, smax = lin["Smin"], lin["Smax"]
+    smax[upper] = raw[raw.shape[0] // 2][upper] - np.float32(margin)
+    smin[upper] = np.minimum(smin[upper], smax[upper] - np.float32(100.0))
+    smin[lower] = raw[1][lower] + np.float32(margin)
+    smax[lower] = np.maximum(smax[lower], smin[lower] + np.float32(100.0))
+    return upper, lower
+
+
+def narrowed_inputs(shape, rp, p, gdt, kdt):
+    """the set and ramp of test_chain_vs_oracle with the linearity range narrowed, the oracle's result, and the masks of the halves"""
+    ny, nx = shape
+    cal = synth.make_caldir(ny, nx, read_pattern=rp, p_order=p, seed=77, gain_dtype=gdt, ipc_dtype=kdt,
+                            bias_amplitude=2.0, bad_lin_frac=0.01)
+    ramp = synth.make_ramp(cal, read_pattern=rp, seed=78, cr_frac=0.02)
+    upper, lower = narrow_linearity_range(cal, ramp, np.random.default_rng(5))
+    area = 1.0 + 0.01 * np.cos(np.arange(ny * nx, dtype=np.float64).reshape(ny, nx) / 50.0)
+    with np.errstate(all="ignore"):
+        ref = oracle.calibrate_arrays(ramp, cal, area_factor=area)
+    return cal, ramp, area, ref, upper, lower
+
+
+def chain_raised_no_lin_corr(cal, ref, nb=4):
+    """science pixels that never saturate on which the chain itself raised NO_LIN_CORR (the file's dq did not carry it)"""
+    m = (ref["pixeldq"] & NO_LIN_CORR) != 0
+    m &= (cal["linearitylegendre"]["dq"] & NO_LIN_CORR) == 0
+    m &= ((ref["groupdq"] & 2) == 0).all(axis=0)
+    m[:nb], m[-nb:], m[:, :nb], m[:, -nb:] = False, False, False, False
+    return m
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+@pytest.mark.parametrize("name,shape,rp,p,gdt,kdt", NARROWED)
+def test_chain_raises_no_lin_corr(name, shape, rp, p, gdt, kdt, fused):
+    """Groups outside [Smin, Smax], above and below: the extrapolated series and the NO_LIN_CORR flag the chain raises itself (in
+    test_chain_vs_oracle every flagged pixel has the flag from the file's dq), fused kernel and stage kernels, bit for bit."""
+    cal, ramp, area, ref, upper, lower = narrowed_inputs(shape, rp, p, gdt, kdt)
+    raised = chain_raised_no_lin_corr(cal, ref)
+    n, nu, nl = (int(np.count_nonzero(m)) for m in (raised, raised & upper, raised & lower))
+    print(f"{name}: the chain raises NO_LIN_CORR on {n} unsaturated science pixels ({nu} above the range, {nl} below)")
+    assert n >= 10 and nu >= 10 and nl >= 10
+
+    ctx = chain_context()
+    with loaded(pipeline.Calibrator(ctx=ctx), 3, cal) as cb, ctx.options(fused=fused):
+        got = cb.calibrate(3, ramp, area_factor=area, want_cube=True, channel_lines=oracle_lines(ref, len(rp), shape[1] // 128))
+        if fused:
+            assert ctx.last_chain_form() == 2, "the fused kernel did not run"
+    assert_oracle(got, ref, "narrowed linearity range", cube=True)
+
+
 def test_stage_subsets_and_f32_input():
     """stage mask: reduced chain of BASELINE config 1 (ramp fit + dark rate on an already-corrected f32 cube)."""
     rp = synth.READ_PATTERN_8
