@@ -702,6 +702,26 @@ int rip_cal_dark_planes(rip_ctx *ctx, const float *dark1, const float *dark2, co
                         const float *cds, int location, int ny, int nx, size_t row_stride, float *dark_slope, float *dark_slope_err,
                         float *read_noise);
 
+/* ---- gain and ipc4d files ------------------------------------------------------------------ */
+/* What runs/2026_July/make_gain_file.py of the reference (the same script in runs/summer2025run) expands from solid-waffle's
+   superpixel tables.  means[4][nsy*nsx] (g, aH, aV, aD: the script's meanvals, bad superpixels already filled with the array
+   mean) and good[nsy*nsx] (non-zero: at least one summary file has N > 0 there) are HOST arrays; the frame is ny = nsy * ry rows
+   of nx = nsx * rx pixels, pixel (Y,X) belongs to superpixel (Y / ry, X / rx).  The four outputs live where `location` says
+   (RIP_HOST: filled through a scoped device buffer; RIP_DEVICE: written where they are); each may be NULL (not wanted).
+     gain      f32 (ny,nx)   f32(mean_g) of the superpixel, 0.0 on the nb border rows and columns            (:59-68, 88)
+     gain_dq   u32 (ny,nx)   0 where the superpixel is good and the pixel is off the border, else 2**19      (:104)
+     kernel    (3,3,ny-2nb,nx-2nb) of kernel_dtype.  With a_t(p) = f64(f32(mean_t)) of the superpixel of active pixel p:
+               kernel[1+dy][1+dx][p] = (a_t(p) + a_t(p+o)) / 2.0 in f64 for o = (dy,dx) != (0,0) where p+o is an active pixel,
+               0.0 where it is not; t = aV for (+-1,0), aH for (0,+-1), aD for the diagonals.  kernel[1][1][p] = 1.0 - S, S the
+               f64 sum of the nine planes in row-major order, the centre taken as 0.0.  RIP_F64 is what the script writes
+               (:130-175); RIP_F32 is each of those values rounded once.
+     kernel_dq u32 (ny-2nb,nx-2nb)   all zero: the script convolves its bad-pixel map with an all-zero kernel (:130, 195)
+   All nine kernel planes of a pixel are written by one launch.  The call returns when its kernels and copies are done.
+   RIP_EINVAL, before anything is launched or copied: nsy or nsx below 1; superpixels that do not tile the frame (nsy * ry != ny
+   or nsx * rx != nx); nb negative or leaving no active pixel; kernel_dtype neither RIP_F32 nor RIP_F64; every output NULL. */
+int rip_cal_gain_ipc4d(rip_ctx *ctx, const double *means, const uint8_t *good, int nsy, int nsx, int ny, int nx, int nb, int location,
+                       float *gain, uint32_t *gain_dq, void *kernel, int kernel_dtype, uint32_t *kernel_dq);
+
 #ifdef __cplusplus
 }
 #endif

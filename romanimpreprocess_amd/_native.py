@@ -166,6 +166,7 @@ SYMBOLS = {
     "rip_cal_group_means": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _I]),
     "rip_cal_sigma_clip_mean": (_I, [_VP, _VP, _I, _I, C.c_size_t, C.c_size_t, C.c_double, C.c_double, _I, _VP, _VP]),
     "rip_cal_dark_planes": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_size_t, _VP, _VP, _VP]),
+    "rip_cal_gain_ipc4d": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _I, _VP]),
     "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
     "rip_get_option": (_I, [_VP, C.c_char_p, C.POINTER(_I)]),

@@ -4,8 +4,11 @@ GPU (``csrc/calfiles.hip``).  The array-level functions below take numpy arrays 
 HBM as ``DevArray`` too) and reproduce the scripts' numpy arithmetic bit for bit (numpy >= 2 promotion rules, float32 planes);
 ``postprocess_calfiles.run`` and ``makemask.run`` are the scripts' file-level drop-ins.  The step in front of them, the ``dark`` and
 ``read`` files of ``make_dark_file.py``, is ``darkstack.py`` (``DarkStack``, ``sigma_clip_mean``, ``derive_dark_planes``) and the
-drop-in ``make_dark_file.run``.
+drop-in ``make_dark_file.run``.  The ``gain`` and ``ipc4d`` files that all of them read come from ``summary_means`` (numpy, on
+the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hip``), with the drop-in ``make_gain_file.run``.
 """
+
+import warnings
 
 import numpy as np
 
@@ -36,7 +39,7 @@ def _empty(shape, dtype, on_device, ctx):
         return np.empty(shape, dtype)
     import torch
 
-    tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint32): torch.int32}[np.dtype(dtype)]
+    tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.uint32): torch.int32}[np.dtype(dtype)]
     return DevArray(torch.empty(shape, dtype=tdt, device=f"cuda:{ctx.device}"), dtype)
 
 
@@ -143,6 +146,69 @@ def derive_mask(lin_dq, pflat0, dark_slope, gain_dq, nb=NBORDER, ctx=None):
     ctx.check(ctx.lib.rip_cal_mask(ctx.h, ny, nx, int(nb), l.ctypes.data, p.ctypes.data, float(med), d.ctypes.data, g.ctypes.data,
                                    dq.ctypes.data))
     return dq
+
+SUMMARY_COLS = {"X": 0, "Y": 1, "N": 2, "g": 5, "aH": 6, "aV": 7, "aD": 10}   # solid-waffle output columns (make_gain_file.py:21)
+GAIN_OUTPUTS = ("gain", "gain_dq", "kernel", "kernel_dq")
+
+
+def summary_means(tables):
+    """``make_gain_file.py:39-56``: the superpixel tables of solid-waffle summary files.  ``tables`` is (N_in, nrow, ncol), one
+    ``np.loadtxt`` array per file.  Returns ``(means, good, tmean)``: ``means`` the float64 (nsy,nsx) tables of ``g``, ``aH``,
+    ``aV``, ``aD`` -- the ``nanmean`` over the files that have ``N > 0`` in a superpixel, the ``nanmean`` of that over the array
+    (``tmean[e]``) where no file has; ``good`` the bool (nsy,nsx) table of superpixels with ``N > 0`` in at least one file;
+    ``nsx = 1 + max X`` and ``nsy = 1 + max Y`` of the first file.  numpy's own sums, so that the bits are the script's."""
+    alldata = np.zeros(np.shape(tables))   # float64, as the script's np.zeros((N_in, nrow, ncol))
+    alldata[...] = tables
+    if alldata.ndim != 3 or alldata.shape[0] < 1 or alldata.shape[2] <= max(SUMMARY_COLS.values()):
+        raise ValueError(f"summary tables must be (N_in, nrow, >= {max(SUMMARY_COLS.values()) + 1} columns), not {alldata.shape}")
+    cols = SUMMARY_COLS
+    good = np.count_nonzero(alldata[:, :, cols["N"]], axis=0) > 0
+    nsx = 1 + int(np.amax(alldata[0, :, cols["X"]]))
+    nsy = 1 + int(np.amax(alldata[0, :, cols["Y"]]))
+    if nsy * nsx != alldata.shape[1]:
+        raise ValueError(f"{alldata.shape[1]} table rows are not {nsy} x {nsx} superpixels")
+    means, tmean = {}, {}
+    with warnings.catch_warnings(), np.errstate(all="ignore"):
+        warnings.simplefilter("ignore")   # "Mean of empty slice" where no file covers a superpixel
+        for e in ("g", "aH", "aV", "aD"):
+            m = np.nanmean(np.where(alldata[:, :, cols["N"]] > 0, alldata[:, :, cols[e]], np.nan), axis=0)
+            tmean[e] = np.nanmean(m)
+            means[e] = np.where(good, m, tmean[e]).reshape((nsy, nsx))
+    return means, good.reshape((nsy, nsx)), tmean
+
+
+def derive_gain_ipc4d(means, good, shape=(pars.nside, pars.nside), nb=NBORDER, ipc_dtype=np.float64, on_device=False, ctx=None,
+                      outputs=GAIN_OUTPUTS):
+    """``make_gain_file.py:59-68, 88, 104, 130-175, 195``: the tables of ``summary_means`` expanded to a frame of ``shape``, each
+    superpixel ``shape[0] // nsy`` rows by ``shape[1] // nsx`` columns (a frame they do not tile exactly is refused).  Returns
+    ``(gain, gain_dq, kernel, kernel_dq)``: gain f32 and its flags u32 (ny,nx), zero and ``2**19`` on the ``nb`` border; the ipc4d
+    kernel (3,3,ny-2nb,nx-2nb) and its all-zero flags u32 (ny-2nb,nx-2nb), as the script leaves them.  ``ipc_dtype`` float64 is
+    what the script writes; float32 is each of those values rounded once (the fused chain's faster form reads it).  numpy arrays,
+    or ``DevArray`` with ``on_device`` (the inputs are small host tables, so residency cannot follow them).  ``outputs`` names
+    the results wanted; the others are not computed and come back as None."""
+    ctx = ctx or _native.default_context()
+    t = np.ascontiguousarray([np.asarray(means[e], dtype=np.float64) for e in ("g", "aH", "aV", "aD")])
+    if t.ndim != 3:
+        raise ValueError("the four mean tables must be (nsy,nsx) arrays of one shape")
+    gd = np.ascontiguousarray(np.asarray(good) != 0, dtype=np.uint8)
+    if gd.shape != t.shape[1:]:
+        raise ValueError(f"good is {gd.shape}, the mean tables {t.shape[1:]}")
+    unknown = [o for o in outputs if o not in GAIN_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}; known: {GAIN_OUTPUTS}")
+    nsy, nsx = t.shape[1:]
+    ny, nx, nb = int(shape[0]), int(shape[1]), int(nb)
+    code = {np.dtype(np.float32): _native.RIP_F32, np.dtype(np.float64): _native.RIP_F64}.get(np.dtype(ipc_dtype), -1)
+    active = (max(ny - 2 * nb, 0), max(nx - 2 * nb, 0))
+    specs = {"gain": ((ny, nx), np.float32), "gain_dq": ((ny, nx), np.uint32), "kernel": ((3, 3) + active, ipc_dtype),
+             "kernel_dq": (active, np.uint32)}
+    # a dtype the library has no code for is refused there, by name, like the other arguments: nothing is allocated for it
+    out = {o: _empty(*specs[o], on_device, ctx) if o in outputs and code >= 0 and min(ny, nx) > 0 else None for o in GAIN_OUTPUTS}
+    p = {o: None if a is None else a.ctypes.data for o, a in out.items()}
+    ctx.check(ctx.lib.rip_cal_gain_ipc4d(ctx.h, t.ctypes.data, gd.ctypes.data, nsy, nsx, ny, nx, nb,
+                                         _native.RIP_DEVICE if on_device else _native.RIP_HOST, p["gain"], p["gain_dq"], p["kernel"],
+                                         code, p["kernel_dq"]))
+    return tuple(out[o] for o in GAIN_OUTPUTS)
 
 
 from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E402, F401

@@ -1108,8 +1108,78 @@ def case_calfiles():
         shutil.rmtree(tmp_root, ignore_errors=True)
 
 
+def case_gainfile():
+    """Gain and ipc4d files: the reference's runs/2026_July/make_gain_file.py is EXECUTED as it stands (read from the reference
+    tree at run time) on the summary tables of tests/gainfile_cases.py, written as the text files it reads, with sys.argv
+    arranged around it.  Nothing arithmetic is changed:
+      * the literal `nside = 4096` becomes the case's frame side;
+      * asdf.AsdfFile(tree).write_to keeps the trees in memory and astropy.io.fits is a stand-in whose writeto does nothing
+        (the two _asdf_data.fits dumps are for display only);
+      * `from datetime import UTC` needs Python 3.11: on an older interpreter datetime.UTC is set to timezone.utc meanwhile.
+    scipy.signal.convolve is the real one.  The fixture keeps the script's outputs verbatim and its filled tables."""
+    import contextlib
+    import datetime as _dt
+    import io
+    import shutil
+    import tempfile
+    import warnings
+
+    import gainfile_cases as gc
+
+    class _AF:
+        def __init__(self, tr):
+            self.tr = tr
+
+        def write_to(self, path_):
+            _STORE[path_] = self.tr
+
+    class _HDU:
+        def __init__(self, *a, **k):
+            pass
+
+        def writeto(self, *a, **k):
+            pass
+
+    sys.modules["asdf"].AsdfFile = _AF
+    astropy, aio, fits = types.ModuleType("astropy"), types.ModuleType("astropy.io"), types.ModuleType("astropy.io.fits")
+    fits.HDUList = fits.PrimaryHDU = fits.ImageHDU = _HDU
+    astropy.io, aio.fits = aio, fits
+    sys.modules.update({"astropy": astropy, "astropy.io": aio, "astropy.io.fits": fits})
+    path = os.path.join(os.path.dirname(REF_SRC), "runs", "2026_July", "make_gain_file.py")
+    script = open(path).read()
+    tmp = tempfile.mkdtemp(prefix="goldens_gainfile_")
+    had_utc = hasattr(_dt, "UTC")
+    if not had_utc:
+        _dt.UTC = _dt.timezone.utc
+    argv = sys.argv
+    try:
+        for sca, (name, c) in enumerate(gc.CASES.items(), start=1):
+            listfile, _, notes = gc.write_summaries(tmp, name)
+            src = script.replace("nside = 4096", f"nside = {c['nside']}")
+            assert src != script
+            out = os.path.join(tmp, f"{name}_gain_X.asdf")
+            sys.argv = ["make_gain_file.py", listfile, str(sca), out]
+            ns = {"__name__": "__main__"}
+            with np.errstate(all="ignore"), contextlib.redirect_stdout(io.StringIO()), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                exec(compile(src, path, "exec"), ns)
+            gain, ipc = _STORE[out], _STORE[os.path.join(tmp, f"{name}_ipc4d_X.asdf")]
+            assert gain["notes"]["solid_waffle_config"] == notes == ipc["notes"]["solid_waffle_config"]
+            assert gain["roman"]["meta"]["reftype"] == "GAIN" and ipc["roman"]["meta"]["reftype"] == "IPC4D"
+            shape = (c["nsy"], c["nsx"])
+            save(name, nside=np.int32(c["nside"]), sca=np.int32(sca), gain=gain["roman"]["data"], gain_dq=gain["roman"]["dq"],
+                 kernel=ipc["roman"]["data"], kernel_dq=ipc["roman"]["dq"], good=np.asarray(ns["good"]).reshape(shape),
+                 tmean=np.array([ns["tmean"][e] for e in ("g", "aH", "aV", "aD")], np.float64),
+                 **{"mean_" + e: np.asarray(ns["meanvals"][e], np.float64).reshape(shape) for e in ("g", "aH", "aV", "aD")})
+    finally:
+        sys.argv = argv
+        if not had_utc:
+            del _dt.UTC
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
 CASES = {
-    "calfiles": case_calfiles,
+    "calfiles": case_calfiles, "gainfile": case_gainfile,
     "lin_known_answer": case_lin_known_answer, "multilin": case_multilin, "ipc": case_ipc,
     "weights": case_weights, "rampfit": case_rampfit, "flat": case_flat, "refpix": case_refpix,
     "chain": case_chain, "post": case_post, "harness": case_harness, "il": case_il, "il_example": case_il_example,
