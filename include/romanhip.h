@@ -203,6 +203,18 @@ int rip_caldir_drop(rip_ctx *ctx, int sca_slot);
    (option "skip_first").  0: it did not (one NaN anywhere is enough; such a set runs the full kernel form, same results).
    RIP_EINVAL for an empty slot. */
 int rip_caldir_first_group_safe(rip_ctx *ctx, int sca_slot);
+/* Has the set in sca_slot a bias correction to make?
+     RIP_BIAS_ABSENT   no biascorr was given
+     RIP_BIAS_PRESENT  one was given and is subtracted by every call with RIP_STAGE_BIAS
+     RIP_BIAS_DROPPED  one was given and EVERY 32-bit word of it, over all its planes, was 0x00000000 (+0.0f): S - (+0.0f) is S
+                       for every f32, so rip_caldir_upload keeps no device copy of it and calls subtract nothing.  The test is on
+                       bits: one -0.0 (S - (-0.0f) turns an S of -0 into +0) or one non-zero sample anywhere keeps the array.
+                       A ramp with more groups than the array had planes still fails with RIP_EINVAL, as on any biascorr.
+   A set that is ABSENT or DROPPED is screened for rip_caldir_first_group_safe like any other and takes the fused kernel without
+   its biascorr stream (rip_last_chain_bias_stream), as does a call whose stage mask leaves RIP_STAGE_BIAS out.
+   RIP_EINVAL for an empty slot. */
+enum { RIP_BIAS_ABSENT = 0, RIP_BIAS_PRESENT = 1, RIP_BIAS_DROPPED = 2 };
+int rip_caldir_bias_state(rip_ctx *ctx, int sca_slot);
 
 /* plan: replaces meta{ngrp,N,tbar,tau,K,jump_detect_pars} of gen_cal_image.py:123-145,439-444 */
 int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *desc, int *plan_id);
@@ -480,6 +492,9 @@ int rip_option_info(int index, const char **name, int *def, int *lo, int *hi);
 int rip_last_chain_form(rip_ctx *ctx);
 /* 1: the fused launch of the last rip_calibrate skipped group 0 (option "skip_first"); 0: it did not, or the stage kernels ran */
 int rip_last_chain_first_group(rip_ctx *ctx);
+/* 1: the fused launch of the last rip_calibrate streamed the biascorr planes; 0: it ran without that stream (the set has no bias
+   correction to make -- rip_caldir_bias_state -- or the stage mask left RIP_STAGE_BIAS out), or the stage kernels ran */
+int rip_last_chain_bias_stream(rip_ctx *ctx);
 /* the gate in front of the overlapped pre-pass of the last rip_calibrate (option "prepass_gate"): 0 = none was queued, 1 = the
    counter released it, 2 = it gave up at its bound; *giveups (may be NULL) receives the give-ups of all gates of this context so
    far.  Waits for the context's streams.  Negative: an error code. */

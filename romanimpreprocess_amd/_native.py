@@ -18,6 +18,7 @@ RIP_TIMING_BUILD_FLAG = 1000000   # include/romanhip.h
 RIP_F32, RIP_F64, RIP_U16 = 0, 1, 2
 RIP_HOST, RIP_DEVICE = 0, 1
 RIP_INPUTS_STREAM_ORDERED, RIP_INPUTS_COMPLETE = 0, 1
+BIAS_ABSENT, BIAS_PRESENT, BIAS_DROPPED = 0, 1, 2   # rip_caldir_bias_state
 RIP_PROJ_TAN, RIP_PROJ_STG, RIP_PROJ_ZEA, RIP_PROJ_ARC, RIP_PROJ_SIN = 0, 1, 2, 3, 4
 RIP_SIP_MAX_ORDER = 9
 
@@ -119,6 +120,7 @@ SYMBOLS = {
     "rip_caldir_upload": (_I, [_VP, _I, C.POINTER(CaldirDesc)]),
     "rip_caldir_drop": (_I, [_VP, _I]),
     "rip_caldir_first_group_safe": (_I, [_VP, _I]),
+    "rip_caldir_bias_state": (_I, [_VP, _I]),
     "rip_plan_create": (_I, [_VP, C.POINTER(PlanDesc), C.POINTER(_I)]),
     "rip_plan_destroy": (_I, [_VP, _I]),
     "rip_plan_desc_first_weight_zero": (_I, [C.POINTER(PlanDesc)]),
@@ -175,6 +177,7 @@ SYMBOLS = {
     "rip_option_info": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "rip_last_chain_form": (_I, [_VP]),
     "rip_last_chain_first_group": (_I, [_VP]),
+    "rip_last_chain_bias_stream": (_I, [_VP]),
     "rip_last_prepass_gate": (_I, [_VP, C.POINTER(C.c_int)]),
     "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
     "rip_chain_geometry_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
@@ -387,6 +390,18 @@ class Context:
         if rc < 0:
             self.check(rc)
         return rc == 1
+
+    def caldir_bias_state(self, slot):
+        """``BIAS_ABSENT`` (no biascorr in the set of ``slot``), ``BIAS_PRESENT`` (subtracted by every call with ``STAGE_BIAS``) or
+        ``BIAS_DROPPED`` (given, every word +0: no device copy is kept and calls subtract nothing)"""
+        rc = int(self.lib.rip_caldir_bias_state(self.h, int(slot)))
+        if rc < 0:
+            self.check(rc)
+        return rc
+
+    def last_chain_bias_stream(self):
+        """1 = the fused launch of the last calibrate call streamed the biascorr planes, 0 = it ran without them (or stage kernels)."""
+        return int(self.lib.rip_last_chain_bias_stream(self.h))
 
     def last_chain_geometry(self):
         """launch geometry of the last calibrate call's fused kernel (keys ``GEOMETRY_FIELDS``); all zeros after a stage-kernel run"""

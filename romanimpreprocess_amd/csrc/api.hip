@@ -284,6 +284,7 @@ int rip_prepass_stamps(rip_ctx *ctx, int nwg, unsigned long long *out) {
 
 int rip_last_chain_form(rip_ctx *ctx) { return ctx ? ctx->last_form : RIP_EINVAL; }
 int rip_last_chain_first_group(rip_ctx *ctx) { return ctx ? (ctx->last_form == 2 ? ctx->last_first_group : 0) : RIP_EINVAL; }
+int rip_last_chain_bias_stream(rip_ctx *ctx) { return ctx ? (ctx->last_form == 2 ? ctx->last_bias_stream : 0) : RIP_EINVAL; }
 // the gate of the last rip_calibrate: 0 none queued, 1 released by the counter, 2 gave up at its bound; *giveups (may be NULL):
 // the give-ups of every gate of this context so far.  Waits for both streams.
 int rip_last_prepass_gate(rip_ctx *ctx, int *giveups) {
@@ -300,6 +301,12 @@ int rip_caldir_first_group_safe(rip_ctx *ctx, int slot) {
     if (!ctx) return RIP_EINVAL;
     if (slot < 0 || slot >= (int)ctx->cals.size() || !ctx->cals[slot].valid) return rip_fail(ctx, RIP_EINVAL, "caldir slot %d is empty", slot);
     return ctx->cals[slot].first_group_safe ? 1 : 0;
+}
+int rip_caldir_bias_state(rip_ctx *ctx, int slot) {
+    if (!ctx) return RIP_EINVAL;
+    if (slot < 0 || slot >= (int)ctx->cals.size() || !ctx->cals[slot].valid) return rip_fail(ctx, RIP_EINVAL, "caldir slot %d is empty", slot);
+    const RipCal &c = ctx->cals[slot];
+    return c.has_bias ? RIP_BIAS_PRESENT : (c.bias_dropped ? RIP_BIAS_DROPPED : RIP_BIAS_ABSENT);
 }
 int rip_last_chain_geometry(rip_ctx *ctx, int out[8]) {
     if (!ctx || !out) return RIP_EINVAL;

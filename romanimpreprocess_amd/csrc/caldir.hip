@@ -48,19 +48,22 @@ int dev_copy_in(rip_ctx *ctx, void **dst, const void *src, size_t bytes) {
 // (f64 ipc4d: the iterates and the division are f64 with the same bounds, rounded to f32 at the end.)  So |d[0]| < 2^91: twelve
 // binades below the 2^103 the argument needs, 36 below overflow.  A set that fails takes the full kernel form, call by call
 // (RipCal::has_inf: one with an INFINITE value among these arrays takes the stage kernels).
+// A set WITHOUT a bias correction -- no biascorr given, or one whose every word was +0 and that was dropped at upload
+// (rip_caldir_upload) -- is screened like any other: the chain holds with biascorr = 0 (S' = v3 + dark < 2^51, and every later
+// line only needs S' < 2^52), and so does a call whose stage mask leaves the bias step out.
 constexpr double SCREEN_V = 1048576.0, SCREEN_GAIN = 1024.0, SCREEN_K = 16.0, SCREEN_SLOPE = 1024.0;
 
 int screen_first_group(rip_ctx *ctx, RipCal &c, const rip_caldir_desc *d) {
     c.first_group_safe = c.has_inf = false;
     // what the fused chain needs anyway
-    if (!c.dark_data || !c.has_bias || !c.lin_coefs || !c.has_ipc || c.gain_dtype != RIP_F32) return RIP_OK;
+    if (!c.dark_data || !c.lin_coefs || !c.has_ipc || c.gain_dtype != RIP_F32) return RIP_OK;
     const size_t npix = (size_t)c.ny * c.nx;
     DevBuf<uint32_t> bad(ctx);
     int rc;
     if ((rc = bad.alloc(1))) return rc;
     RIP_HIP(ctx, hipMemsetAsync(bad.p, 0, 4, ctx->stream));
     if ((rc = rip_launch_screen(ctx, c.dark_data, RIP_F32, npix * c.ngrp_dark, 0.0, SCREEN_V, bad.p)) ||
-        (rc = rip_launch_screen(ctx, c.bias, RIP_F32, npix * c.ngrp_bias, 0.0, SCREEN_V, bad.p)) ||
+        (rc = rip_launch_screen(ctx, c.bias, RIP_F32, npix * c.ngrp_bias, 0.0, SCREEN_V, bad.p)) ||   // (none, or dropped: null, nothing to screen)
         // Legendre planes, Smin, Smax, Sref: planes [0, NP + 3) of the slab
         (rc = rip_launch_screen(ctx, c.slab, RIP_F32, npix * (size_t)(c.lin_nplanes + 3), 0.0, SCREEN_V, bad.p)) ||
         (rc = rip_launch_screen_span(ctx, c.lin_smin, c.lin_smax, npix, bad.p)) ||
@@ -198,6 +201,23 @@ int rip_caldir_upload(rip_ctx *ctx, int slot, const rip_caldir_desc *d) {
         RIP_HIP(ctx, hipMemcpyAsync(tmp, d->biascorr, nb_in, hipMemcpyHostToDevice, ctx->stream));
         if ((rc = rip_launch_embed(ctx, tmp, c.bias, d->ngrp_bias, c.ny, c.nx, c.nb, 4))) return rc;
         c.has_bias = true;
+        // A bias correction of +0 everywhere corrects nothing: S - (+0.0f) is S for every f32 (-0, infinities, NaN included).  The
+        // test is on BITS and over EVERY plane (which planes a ramp uses depends on its group count): a single -0.0 keeps the
+        // array, because S - (-0.0f) turns an S of -0 into +0.  Such a set keeps no device copy (RipCal::bias_dropped) and its
+        // calls run without the bias stream, like those of a set that never had a biascorr.
+        DevBuf<uint32_t> nz(ctx);
+        if ((rc = nz.alloc(1))) return rc;
+        uint32_t h_nz = 1;
+        RIP_HIP(ctx, hipMemsetAsync(nz.p, 0, 4, ctx->stream));
+        if ((rc = rip_launch_screen_zero_words(ctx, (const uint32_t *)c.bias, (size_t)d->ngrp_bias * npix, nz.p))) return rc;
+        RIP_HIP(ctx, hipMemcpyAsync(&h_nz, nz.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (h_nz == 0) {
+            (void)hipFree(c.bias);
+            c.bias = nullptr;
+            c.has_bias = false;
+            c.bias_dropped = true;
+        }
     }
     // IPC-deconvolved dark rate (gen_cal_image.py:217-221)
     if (c.dark_slope) {

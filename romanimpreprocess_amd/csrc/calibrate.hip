@@ -113,9 +113,11 @@ struct Calibration {
     // computed: a u16 cube on a CALDIR set that passed the screen at upload (caldir.hip: the chain of bounds), no corrected cube
     // to write, and channel lines that are either the pre-pass's own or a HOST array whose group-0 entries are within the
     // bounds that chain assumes of them (|m| <= 2^32, |c| <= 2^35; lines on the device cannot be looked at here).
+    // A bias correction is not required: without one (no biascorr in the set, an all +0 one dropped at upload, or a stage mask
+    // without RIP_STAGE_BIAS) the chain of bounds holds with biascorr = 0.
     void choose_skip() {
         skip0 = false;
-        if (!(do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 && !out->cube && c.first_group_safe)) return;
+        if (!(do_ref && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 && !out->cube && c.first_group_safe)) return;
         const bool with_flat = (stages & RIP_STAGE_FLAT) && c.has_flat;
         const int merged = c.merged_plane[(with_flat ? 1 : 0) | ((stages & RIP_STAGE_DARK) ? 2 : 0)];   // as fused_chain sets it
         if (!rip_chain_may_skip_first(ctx, plan, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype, merged, c.nb)) return;
@@ -144,7 +146,9 @@ struct Calibration {
         do_ref = stages & RIP_STAGE_REFPIX, do_bias = (stages & RIP_STAGE_BIAS) && c.has_bias;
         do_lin = stages & RIP_STAGE_LIN, do_ipc = (stages & RIP_STAGE_IPC) && c.has_ipc;
         if (do_ref && (!c.dark_data || c.ngrp_dark < G)) return rip_fail(ctx, RIP_EINVAL, "calibrate: dark.data has %d groups, ramp %d", c.ngrp_dark, G);
-        if (do_bias && c.ngrp_bias < G) return rip_fail(ctx, RIP_EINVAL, "calibrate: biascorr has %d groups, ramp %d", c.ngrp_bias, G);
+        // (a biascorr that was all +0 and dropped at upload subtracts nothing, but one with too few planes fails like any other)
+        if ((do_bias || ((stages & RIP_STAGE_BIAS) && c.bias_dropped)) && c.ngrp_bias < G)
+            return rip_fail(ctx, RIP_EINVAL, "calibrate: biascorr has %d groups, ramp %d", c.ngrp_bias, G);
         if (do_lin && !c.lin_coefs) return rip_fail(ctx, RIP_EINVAL, "calibrate: no linearity arrays in caldir slot %d", slot);
         do_sat = in->flag_saturation != 0;
         if (do_sat && !c.sat_thr) return rip_fail(ctx, RIP_EINVAL, "calibrate: flag_saturation needs the saturation array in caldir slot %d", slot);
@@ -307,13 +311,16 @@ struct Calibration {
     }
 
     // ---- one kernel: refpix apply + bias + linearity + IPC + ramp fit + finish (chain.hip).  It covers the complete chain on a
-    // Level-1 (u16) cube; sub-chains and f32 cubes take the stage-by-stage kernels
+    // Level-1 (u16) cube, with or without the bias step (no biascorr in the set, an all +0 one dropped at upload, a stage mask
+    // without RIP_STAGE_BIAS: the launch then carries no bias stream, ChainArgs::bias_records); other sub-chains and f32 cubes
+    // take the stage-by-stage kernels
     int fused_chain() {
         ctx->last_form = 0;
         ctx->last_first_group = 0;
+        ctx->last_bias_stream = 0;
         memset(ctx->last_geo, 0, sizeof ctx->last_geo);
         ctx->gate_armed = false;   // (the launcher sets it: the next call's gate waits for a launch that carries the counter)
-        if (!(ctx->use_fused && !c.has_inf && do_ref && do_bias && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
+        if (!(ctx->use_fused && !c.has_inf && do_ref && do_lin && do_ipc && do_fit && in->data_dtype == RIP_U16 &&
               rip_chain_supported(ctx, c.lin_nplanes, G, c.ipc_dtype, c.gain_dtype))) {
             // (a call planned without group 0 must reach the fused kernel: the stage kernels would read unwritten tables)
             if (skip0) return rip_fail(ctx, RIP_ESTATE, "calibrate: a call planned without group 0 does not take the fused kernel");
@@ -329,7 +336,15 @@ struct Calibration {
         ca.rowcorr = rowcorr;
         ca.rowcorr_t = rowcorr_t;
         ca.lines = lines;
-        ca.bias = c.bias + (size_t)(c.ngrp_bias - G) * npix;
+        if (do_bias) {
+            ca.bias = c.bias + (size_t)(c.ngrp_bias - G) * npix;   // biascorr[de:], gen_cal_image.py:561-562
+            ca.bias_records = -1;
+        } else {
+            // no bias stream: a descriptor of zero records (every load dropped) on a base that is valid all the same, with at
+            // least G planes behind it (validate)
+            ca.bias = c.dark_data;
+            ca.bias_records = 0;
+        }
         ca.planes = c.slab;
         ca.do_not_flag_first = plan->h.do_not_flag_first;
         ca.kern = c.ipc;

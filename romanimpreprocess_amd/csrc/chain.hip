@@ -120,7 +120,7 @@ int rip_launch_chain(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, int 
     // (merged_dq < 0: this CALDIR set's flag words cannot be merged, RipCal)
     if (!launch || !ctx->use_chain2 || a.merged_dq < 0) return 1;
     const int rc = launch(ctx, plan, a, skip0);
-    if (rc != 1) ctx->last_form = 2, ctx->last_first_group = skip0 ? 1 : 0;
+    if (rc != 1) ctx->last_form = 2, ctx->last_first_group = skip0 ? 1 : 0, ctx->last_bias_stream = a.bias_records ? 1 : 0;
     return rc;
 }
 

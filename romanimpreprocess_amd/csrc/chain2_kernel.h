@@ -55,8 +55,11 @@ __device__ __forceinline__ unsigned c2_opaque(unsigned x) {
 // Buffer addressing for the global loads: descriptor (base, no stride, no bound) in four scalar registers, the
 // loop-invariant column offset of the lane as the vector offset, plane + row as a 32-bit scalar offset -- one s_add per
 // load where a 64-bit base costs two.  Every array addressed this way is smaller than 4 GiB.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t c2_rsrc(const void *p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, -1, 0x00020000);
+// records: the bound the hardware's range check holds offsets against.  -1 everywhere but on the biascorr planes, whose
+// descriptor has 0 records where the call has no bias stream (ChainArgs::bias_records): every load through it is dropped by the
+// range check and returns 0.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t c2_rsrc(const void *p, int records = -1) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, records, 0x00020000);
 }
 template <int AUX = 0>
 __device__ __forceinline__ float c2_ld_f32(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
@@ -359,7 +362,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             __builtin_amdgcn_sched_barrier(0);
             const unsigned yl = (unsigned)min(max(y, ylo), yhi);
             const __amdgpu_buffer_rsrc_t rs = c2_rsrc(ka->data), rq = c2_rsrc(ka->gdq), rd = c2_rsrc(ka->dark_data),
-                                         rb = c2_rsrc(ka->bias);
+                                         rb = c2_rsrc(ka->bias, ka->bias_records);
             unsigned o4 = yl * row4 + (unsigned)g0 * pl4, o2 = yl * (row4 >> 1) + (unsigned)g0 * (pl4 >> 1),
                      o1 = yl * (row4 >> 2) + (unsigned)g0 * npix;
 #pragma unroll

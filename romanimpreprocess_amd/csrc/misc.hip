@@ -257,6 +257,13 @@ __global__ __launch_bounds__(256) void screen_span_kernel(const float *__restric
     }
     if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
 }
+// is every word of an array 0x00000000 (bit 0 of *bad otherwise)?  The bit test behind RipCal::bias_dropped: the magnitude screen
+// above would take a -0.0 for a zero
+__global__ __launch_bounds__(256) void screen_zero_words_kernel(const uint32_t *__restrict__ w, size_t n, uint32_t *__restrict__ bad) {
+    uint32_t any = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) any |= w[i];
+    if (__any(any != 0) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+}
 static unsigned screen_grid(size_t n) {
     const size_t g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
@@ -268,6 +275,12 @@ int rip_launch_screen(rip_ctx *ctx, const void *p, int dtype, size_t n, double l
     else
         hipLaunchKernelGGL(screen_kernel<float>, dim3(screen_grid(n)), dim3(256), 0, ctx->stream, (const float *)p, n, (float)lo,
                            (float)hi, d_bad);
+    RIP_HIP(ctx, hipGetLastError());
+    return RIP_OK;
+}
+int rip_launch_screen_zero_words(rip_ctx *ctx, const uint32_t *w, size_t n, uint32_t *d_bad) {
+    if (!w || !n) return RIP_OK;
+    hipLaunchKernelGGL(screen_zero_words_kernel, dim3(screen_grid(n)), dim3(256), 0, ctx->stream, w, n, d_bad);
     RIP_HIP(ctx, hipGetLastError());
     return RIP_OK;
 }

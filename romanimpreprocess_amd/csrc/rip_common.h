@@ -114,6 +114,11 @@ struct RipCal {
     float *flat_dn = nullptr;     // output of get_flat (ny,nx); border = 1
     uint32_t *flat_flags = nullptr;  // NO_FLAT_FIELD / NO_GAIN_VALUE bits get_flat would OR into pdq
     float *bias = nullptr;        // (ngrp_bias, ny, nx) embedded in the full frame, border = 0
+    // a biascorr was given and every word of its device copy was 0x00000000 (+0.0f; a -0.0 keeps the array: S - (-0) turns an S
+    // of -0 into +0): the copy is freed, has_bias is false and the chain subtracts nothing -- S - (+0) is S for every f32 --
+    // while ngrp_bias still says how many planes were given (a ramp with more groups fails as it does on a non-zero array).
+    // The three states of a set (rip_caldir_bias_state): absent (neither flag), present (has_bias), dropped (bias_dropped)
+    bool bias_dropped = false;
     float *sat_thr = nullptr;     // saturation threshold (ny,nx) or null
     uint32_t *sat_dq = nullptr;   // saturation dq (ny,nx) or null
     // one allocation holding the per-pixel planes the fused kernel walks together, in this order:
@@ -225,6 +230,7 @@ struct rip_ctx {   // host-only: no kernel reads it
     // ---- diagnostics and profiling
     int last_form = 0;       // diagnostic: how the last rip_calibrate ran (0 stage kernels, 2 the fused kernel; 1 and 3 were the general and the wave-private fused kernels of rounds 1-2)
     int last_first_group = 0;   // diagnostic: 1 = the last fused launch skipped group 0 (rip_last_chain_first_group)
+    int last_bias_stream = 0;   // diagnostic: 1 = the last fused launch streamed the biascorr planes (rip_last_chain_bias_stream)
     int last_geo[8] = {};    // diagnostic: launch geometry of the last fused launch (rip_last_chain_geometry; zeros after a stage-kernel run)
     int chain_dbg;           // timing experiments only (option "chain_dbg"): the fused kernel skips phases, results invalid
     unsigned long long *chain_dbg_buf = nullptr;  // 4096 waves x 6 phases (diagnostic builds)
@@ -331,9 +337,18 @@ struct ChainArgs {
     const float *dark_data;
     const double *rowcorr, *lines;
     const double *rowcorr_t;  // (ny, G) copy of rowcorr (wave-private kernel: one wide scalar load per row)
-    const float *bias;  // embedded planes, already offset to the first group used; null -> skipped
+    // embedded planes, already offset to the first group used (bias_records -1).  No bias stream (bias_records 0): the base of
+    // dark_data, a valid address of the same plane size that is never read -- see bias_records
+    const float *bias;
     const float *planes;  // RipCal::slab
     int do_not_flag_first;
+    // num_records of the buffer descriptor the biascorr loads go through: -1 = unbounded like every other array, 0 = no bias
+    // stream: the range check of a raw buffer descriptor with zero records drops every load through it -- the load returns 0
+    // (+0.0f, and S - (+0) is S) and sends no request to the caches, while the instruction stream and the waits stay as they
+    // are, so that one kernel form serves sets with and without a bias correction.  The base stays a valid address whose
+    // extent covers every offset the loads form: were the check ever not to fire, the kernel would read dark samples (every
+    // pixel wrong, which the tests see) instead of faulting.
+    int bias_records;
     const void *kern;   // (9, ny, nx) embedded ipc4d
     int finish;
     int dark_rate;        // 1: subtract plane NP+6 on the active region
@@ -429,6 +444,8 @@ int rip_launch_or_bytes(rip_ctx *ctx, uint8_t *bytes, size_t n, uint8_t bit, hip
 int rip_launch_prepass_gate(rip_ctx *ctx, uint32_t *words, uint32_t target, int bound_us, hipStream_t stream);
 // *d_bad |= 1 unless lo <= |p[i]| <= hi for every i < n (NaN fails), |= 2 where some p[i] is infinite; p of RIP_F32 / RIP_F64 elements
 int rip_launch_screen(rip_ctx *ctx, const void *p, int dtype, size_t n, double lo, double hi, uint32_t *d_bad);
+// *d_bad |= 1 unless every 32-bit word w[i], i < n, is 0x00000000 (an array of +0.0f: a -0.0 fails)
+int rip_launch_screen_zero_words(rip_ctx *ctx, const uint32_t *w, size_t n, uint32_t *d_bad);
 // *d_bad |= 1 unless f32(smax[i] - smin[i]) is non-zero and not NaN for every i < n
 int rip_launch_screen_span(rip_ctx *ctx, const float *smin, const float *smax, size_t n, uint32_t *d_bad);
 // dq-init + saturation flagging (misc.hip): gdq_in / pdq_in may be null (= zeros)

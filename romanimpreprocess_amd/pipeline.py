@@ -82,6 +82,11 @@ class Calibrator:
         self.shapes.pop(slot, None)
         self.ctx.__dict__.get("_caldir_owner", {}).pop(slot, None)
 
+    def bias_state(self, slot):
+        """``_native.BIAS_ABSENT`` / ``BIAS_PRESENT`` / ``BIAS_DROPPED`` for the CALDIR set of ``slot`` (``rip_caldir_bias_state``): a
+        set without biascorr, or with one that is +0 everywhere (dropped at upload), runs the fused kernel without that stream."""
+        return self.ctx.caldir_bias_state(slot)
+
     def slot_owner(self, slot):
         return self.ctx.__dict__.get("_caldir_owner", {}).get(slot)
 
