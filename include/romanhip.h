@@ -166,6 +166,19 @@ typedef struct {
        the array itself when the first group is excluded; a host caller that wants its own array untouched would otherwise copy
        134 MB to set one plane's bit).  The groupdq returned carries the bit, as the reference's does. */
     int32_t or_first_group;
+    /* location == RIP_HOST only: a Level-1 exposure stored with the reference read subtracted (the EXTRACT_REF block of
+       sim_to_isim.py:711-730, rip_synth_extract_ref: data[k] = clip(i32(resultant k+1) - (i32(resultant 0) - offset), 0, 65535),
+       reference_read = resultant 0, the read pattern without its first group).  The library decodes its device copies of data
+       and amp33 in place behind the upload -- v = i32(enc) + i32(reference) - offset, rip_stage_decode_reference_read -- before
+       anything reads them; the chain then sees a u16 cube of ngrp groups, one fewer than the exposure had (the CALDIR arrays may
+       hold that one group more: biascorr[de:], gen_cal_image.py:561-562).  A v outside 0..65535 means that the three pieces do
+       not belong together: the samples are counted, and the call (in a batch: that ramp) fails with RIP_EINVAL once the results
+       are down; its outputs are invalid.  RIP_EINVAL at once: reference_read with data_dtype != RIP_U16, reference_amp33 without
+       amp33, either with location == RIP_DEVICE (a device caller decodes its own arrays with the stage entry on the context's
+       stream and then calibrates as usual).  All zero = the data are not encoded: nothing changes. */
+    const uint16_t *reference_read;    /* (ny,nx) or NULL = data is not encoded */
+    const uint16_t *reference_amp33;   /* (ny,128) or NULL = amp33 is used as stored */
+    int32_t data_encoding_offset;
 } rip_ramp_desc;
 
 typedef struct {
@@ -610,6 +623,19 @@ int rip_synth_frames_ahead(rip_ctx *ctx, int rows, int width, int nframes, uint6
 /* EXTRACT_REF (:711-730) on n-element planes: reference_read = data[0]; data[k] = clip(i32(data[k]) - (i32(data[0]) -
    offset), 0, 65535) for k = 1..ngrp-1, in place (the caller drops plane 0).  Used for the cube and for amp33.  Exact. */
 int rip_synth_extract_ref(rip_ctx *ctx, uint16_t *data, int ngrp, size_t n, int offset, uint16_t *reference_read);
+
+/* The inverse of EXTRACT_REF, what romancal's dq-init does to such an exposure before calibrateimage sees it (gen_cal_image.py:
+   117-118; its source is not in the reference tree: PARITY UNPINNED): per pixel and stored resultant
+   v = i32(data[k]) + i32(reference_read) - offset, out[k] = clip(v, 0, 65535), k = 0..ngrp-1; *n_out_of_range = the number of
+   samples the clip changed (0 for everything the encoder made of u16 data: where it did not clip v is the original sample,
+   where it clipped v stays inside 0..65535).  data, out (ngrp,n) u16, reference_read (n) u16; out may equal data (in place).
+   Used for the cube (n = ny * nx) and for amp33 (n = ny * 128, reference_amp33).  `location` holds for all four pointers:
+   RIP_HOST: staged through HBM, complete on return; RIP_DEVICE: asynchronous on the context's stream, n_out_of_range is one
+   device word that the entry zeroes first.
+   RIP_EINVAL, before anything is copied or launched: a NULL pointer, ngrp < 1, n < 1, |offset| > 2^30, an unknown location,
+   out overlapping data without being equal to it.  Exact. */
+int rip_stage_decode_reference_read(rip_ctx *ctx, const uint16_t *data, int ngrp, size_t n, const uint16_t *reference_read,
+                                    int offset, int location, uint16_t *out, uint64_t *n_out_of_range);
 
 /* Cosmic-ray hits (the model of romanisim's cr module, restated in DESIGN.md 7: romanisim is absent from the reference tree, so
    parity is unpinned and every constant is a parameter).  Defaults in brackets. */

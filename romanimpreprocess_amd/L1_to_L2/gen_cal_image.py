@@ -42,11 +42,24 @@ def wcs_from_config(config):
 
 
 def initializationstep(config, caldir, mylog):
-    """Read the L1 file and the mask: data (u16 cube), amp33, groupdq (zeros), pixeldq (mask dq), meta."""
+    """Read the L1 file and the mask: data (u16 cube), amp33, groupdq (zeros), pixeldq (mask dq), meta.
+
+    An exposure stored with its reference read subtracted (the EXTRACT_REF block of ``sim_to_isim.py:711-730``; the reference
+    leaves the decoding to romancal's dq-init, :117-118) also yields ``reference_read``, ``reference_amp33`` (None where amp33
+    is not encoded) and ``data_encoding_offset``: data, amp33 and the read pattern stay as stored, one group fewer than the
+    exposure had, and the chain call decodes on the device.  ValueError when such a tree does not say its offset."""
     with calio.open_tree(config["IN"]) as f:
         r = f["roman"]
         data = np.ascontiguousarray(r["data"])
         amp33 = np.ascontiguousarray(r["amp33"]) if "amp33" in r else None
+        encoded = {}
+        if "reference_read" in r:
+            instrument = r["meta"]["instrument"] if "instrument" in r["meta"] else {}
+            if "data_encoding_offset" not in instrument:
+                raise ValueError("the L1 tree has reference_read but no meta.instrument.data_encoding_offset")
+            encoded = {"reference_read": np.ascontiguousarray(r["reference_read"]),
+                       "reference_amp33": np.ascontiguousarray(r["reference_amp33"]) if "reference_amp33" in r else None,
+                       "data_encoding_offset": int(instrument["data_encoding_offset"])}
         exposure = r["meta"]["exposure"]
         frame_time = float(exposure["frame_time"])
         read_pattern = [list(map(int, g)) for g in exposure["read_pattern"]]
@@ -62,7 +75,7 @@ def initializationstep(config, caldir, mylog):
     meta = planmod.exposure_meta(read_pattern, frame_time)
     if config.get("EXCLUDE_FIRST", True):
         groupdq[0] |= np.uint8(group.DO_NOT_USE)
-    return {"data": data, "amp33": amp33, "groupdq": groupdq, "pixeldq": pixeldq, "meta": l1meta}, meta
+    return dict({"data": data, "amp33": amp33, "groupdq": groupdq, "pixeldq": pixeldq, "meta": l1meta}, **encoded), meta
 
 
 def load_caldir_arrays(caldir):
@@ -135,6 +148,8 @@ def calibrateimage(config, verbose=True, calibrator=None):
     meta["nborder"] = pars.nborder
     nb = pars.nborder
     mylog.append("Initialized data\n")
+    if ramp.get("reference_read") is not None:
+        mylog.append(f"Reference read subtracted in the file (data_encoding_offset = {ramp['data_encoding_offset']}): decoded on the device\n")
 
     cb = calibrator or pipeline.Calibrator()
     slot = _caldir_slot(cb, caldir)

@@ -162,10 +162,15 @@ class _Files:
         return self.tree(src)["roman"]
 
 
-def _device_path_applies(config, rng):
+def _device_path_applies(config, rng, tree=None):
     """The layer loop keeps its arrays in HBM when the exposures stay in memory, the deviates are the device's and nothing asks for a
-    host-side ingredient (an ``AREAFACTOR`` file; a ``FITSWCS`` pixel-area map is made on the device and stays there)."""
+    host-side ingredient (an ``AREAFACTOR`` file; a ``FITSWCS`` pixel-area map is made on the device and stays there).  An
+    exposure stored with its reference read subtracted (``config["IN"]`` a tree with ``reference_read``, or ``tree`` = the tree
+    read from it) keeps its layers on host arrays: every chain run is then a ``calibrateimage`` call, which decodes."""
     if not bool(config["NOISE"].get("IN_MEMORY", True)) or not bool(config["NOISE"].get("DEVICE_RESIDENT", True)):
+        return False
+    src = tree if tree is not None else config.get("IN")
+    if isinstance(src, dict) and "reference_read" in (src["roman"] if "roman" in src else src):
         return False
     if isinstance(rng, np.random.Generator) or "AREAFACTOR" in config or not config["NOISE"].get("CORRELATED", True):
         return False
@@ -385,7 +390,7 @@ def make_noise_cube(config, rng=None):
     ngrp = len(read_pattern)
     cube_dtype = np.asarray(base_tree["roman"]["data"]).dtype
     # the chain's u16 path is what the HBM-resident back end drives; a cube of anything else stays on the host
-    if _device_path_applies(config, rng) and cube_dtype == np.uint16:
+    if _device_path_applies(config, rng, base_tree) and cube_dtype == np.uint16:
         be = _DeviceArrays(config, files, base_tree, read_pattern)
     else:
         be = _HostArrays(config, files, base_tree, host_rng)

@@ -66,6 +66,7 @@ class RampDesc(C.Structure):
         ("flag_saturation", C.c_int32), ("sat_backup", C.c_int32), ("sat_skip_firstn", C.c_int32),
         ("sat_dilution", C.c_void_p),
         ("inputs_ready", C.c_int32), ("ready_event", C.c_void_p), ("or_first_group", C.c_int32),
+        ("reference_read", C.c_void_p), ("reference_amp33", C.c_void_p), ("data_encoding_offset", C.c_int32),
     ]
 
 
@@ -161,6 +162,7 @@ SYMBOLS = {
     "rip_synth_cr_tracks": (_I, [_VP, C.POINTER(CrParams), _I, C.c_double, _I, _I, C.c_uint64, _VP, _VP, _I, _VP, _VP]),
     "rip_synth_cr_deposit": (_I, [_VP, C.POINTER(CrParams), _I, _I, _I, _VP, _VP, _I, C.c_uint64, _VP, _VP, _VP]),
     "rip_synth_extract_ref": (_I, [_VP, _VP, _I, C.c_size_t, _I, _VP]),
+    "rip_stage_decode_reference_read": (_I, [_VP, _VP, _I, C.c_size_t, _VP, _I, _I, _VP, _VP]),
     "rip_cal_biascorr": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, C.c_double, _I, _VP, _VP, _VP]),
     "rip_cal_pflat": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, C.c_float, _VP, _VP]),
     "rip_cal_saturation": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),

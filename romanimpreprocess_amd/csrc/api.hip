@@ -172,6 +172,8 @@ void rip_ctx_destroy(rip_ctx *ctx) {
     if (ctx->chain_dbg_buf) (void)hipFree(ctx->chain_dbg_buf);
     if (ctx->prepass_stamps) (void)hipFree(ctx->prepass_stamps);
     if (ctx->gate_words) (void)hipFree(ctx->gate_words);
+    if (ctx->refread_dev) (void)hipFree(ctx->refread_dev);
+    if (ctx->refread_host) (void)hipHostFree(ctx->refread_host);
     if (ctx->stream3) {
         (void)hipStreamSynchronize(ctx->stream3);
         (void)hipStreamDestroy(ctx->stream3);

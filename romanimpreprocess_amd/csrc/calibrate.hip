@@ -5,17 +5,34 @@
 
 #include "rip_host.h"
 
-// bytes that take a ramp's inputs: data, amp33, groupdq, pixeldq, area factor, channel lines, each in a 256-byte aligned slot
-// (every array counted, present or not)
+// bytes that take a ramp's inputs: data, amp33, groupdq, pixeldq, area factor, channel lines, reference read, reference amp33,
+// each in a 256-byte aligned slot (every array counted, present or not)
 size_t rip_host_ramp_bytes(const rip_ramp_desc &in, int ny, int nx) {
     const size_t G = in.ngrp, npix = (size_t)ny * nx;
     return al256(G * npix * (in.data_dtype == RIP_U16 ? 2 : 4)) + al256(G * ny * RIP_CW * 2) + al256(G * npix) + al256(npix * 4) +
-           al256(npix * 8) + al256(G * (nx / RIP_CW) * 16);
+           al256(npix * 8) + al256(G * (nx / RIP_CW) * 16) + al256(npix * 2) + al256((size_t)ny * RIP_CW * 2);
+}
+
+// what a ramp stored with its reference read subtracted must satisfy (include/romanhip.h, rip_ramp_desc::reference_read)
+int rip_check_reference_read(rip_ctx *ctx, const rip_ramp_desc &in, const char *who) {
+    if (!rip_ramp_is_encoded(in)) return RIP_OK;
+    if (in.location == RIP_DEVICE)
+        return rip_fail(ctx, RIP_EINVAL, "%s: reference_read / reference_amp33 come with host ramps only (a device caller decodes its arrays with "
+                        "rip_stage_decode_reference_read and calibrates them as usual)", who);
+    if (in.reference_read && in.data_dtype != RIP_U16) return rip_fail(ctx, RIP_EINVAL, "%s: reference_read needs u16 data", who);
+    if (in.reference_amp33 && !in.amp33) return rip_fail(ctx, RIP_EINVAL, "%s: reference_amp33 without amp33", who);
+    if (in.data_encoding_offset > (1 << 30) || in.data_encoding_offset < -(1 << 30))
+        return rip_fail(ctx, RIP_EINVAL, "%s: data_encoding_offset %d (|offset| <= 2^30 supported)", who, (int)in.data_encoding_offset);
+    return RIP_OK;
 }
 
 // queues the copies of the host arrays of `in` into `w` on `st`, in the order above (an absent array takes no slot), and sets
-// DO_NOT_USE on the copy of the first group with or_first_group; `dev` = `in` with the device copies in place of the host arrays
-int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev) {
+// DO_NOT_USE on the copy of the first group with or_first_group; `dev` = `in` with the device copies in place of the host arrays.
+// A ramp stored with its reference read subtracted (checked by the caller: rip_check_reference_read) is decoded in place on the
+// device copies of data and amp33, on `st` behind the copies and before anything reads them: `dev` then describes a plain u16
+// ramp, and *count (zeroed here, on `st`) receives the samples that left 0..65535.
+int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev,
+                         unsigned long long *count) {
     const size_t G = in.ngrp, npix = (size_t)ny * nx;
     hipError_t e = hipSuccess;
     auto put = [&](const void *src, size_t bytes) -> void * {
@@ -36,7 +53,22 @@ int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, 
     dev->pixeldq = (const uint32_t *)put(in.pixeldq, npix * 4);
     dev->area_factor = (const double *)put(in.area_factor, npix * 8);
     dev->channel_lines = (const double *)put(in.channel_lines, G * (nx / RIP_CW) * 16);
+    const uint16_t *ref = (const uint16_t *)put(in.reference_read, npix * 2);
+    const uint16_t *ref33 = (const uint16_t *)put(in.reference_amp33, (size_t)ny * RIP_CW * 2);
+    dev->reference_read = dev->reference_amp33 = nullptr;   // (decoded below: the chain sees a plain ramp)
+    dev->data_encoding_offset = 0;
     if (e != hipSuccess) return rip_fail(ctx, RIP_EHIP, "calibrate: upload of the ramp failed: %s", hipGetErrorString(e));
+    if (ref || ref33) {
+        if (!count) return rip_fail(ctx, RIP_ESTATE, "calibrate: a ramp with a reference read and no counting word");
+        RIP_HIP(ctx, hipMemsetAsync(count, 0, 8, st));
+        int rc;
+        if (ref && (rc = rip_launch_decode_reference_read(ctx, (const uint16_t *)dev->data, (int)G, npix, ref, in.data_encoding_offset,
+                                                          (uint16_t *)dev->data, count, st)))
+            return rc;
+        if (ref33 && (rc = rip_launch_decode_reference_read(ctx, dev->amp33, (int)G, (size_t)ny * RIP_CW, ref33, in.data_encoding_offset,
+                                                            (uint16_t *)dev->amp33, count, st)))
+            return rc;
+    }
     // gen_cal_image.py:142-143 (rdq[0] |= DO_NOT_USE with EXCLUDE_FIRST) on the device copy, so that the host need not copy a
     // 134 MB array to set one plane's bit
     if (in.or_first_group && dev->groupdq) return rip_launch_or_bytes(ctx, (uint8_t *)dev->groupdq, npix, (uint8_t)DQ_DO_NOT_USE, st);
@@ -107,6 +139,7 @@ struct Calibration {
     const uint32_t *pdq_mid = nullptr;  // pixeldq after the cube stage
     bool ran_fused = false;
     bool skip0 = false;   // the fused kernel of this call skips group 0, and the pre-pass leaves its tables out
+    bool decoded = false;   // a host ramp stored with its reference read subtracted: decoded on the device behind its upload
 
     // ---- May this call's fused kernel skip group 0 (option "skip_first")?  Decided before the pre-pass.  Group 0 must be dead in
     // the fit (rip_chain_may_skip_first: the plan, and that the fused kernel WILL run) and known to be finite without being
@@ -131,6 +164,7 @@ struct Calibration {
 
     int validate(int slot, int plan_id) {
         if (in->location != out->location) return rip_fail(ctx, RIP_EINVAL, "calibrate: inputs and outputs must share a location");
+        if (const int rc = rip_check_reference_read(ctx, *in, "calibrate")) return rc;
         RIP_HIP(ctx, hipSetDevice(ctx->device));
         G = in->ngrp, ny = c.ny, nx = c.nx, nch = nx / RIP_CW;
         npix = (size_t)ny * nx;
@@ -169,7 +203,11 @@ struct Calibration {
         if (!host) return RIP_OK;
         char *w = (char *)rip_ws(ctx, RIP_WS_STAGING, rip_host_ramp_bytes(*in, ny, nx));
         if (!w) return RIP_ENOMEM;
-        if (const int rc = rip_upload_host_ramp(ctx, *in, ny, nx, w, ctx->stream, &d)) return rc;
+        // (a ramp stored with its reference read subtracted: decoded behind the upload, counting word 0; read_back looks at it)
+        decoded = rip_ramp_is_encoded(*in);
+        if (decoded)
+            if (const int rc = rip_refread_words(ctx, 1)) return rc;
+        if (const int rc = rip_upload_host_ramp(ctx, *in, ny, nx, w, ctx->stream, &d, decoded ? ctx->refread_dev : nullptr)) return rc;
         RIP_HIP(ctx, hipGetLastError());
         w = (char *)rip_ws(ctx, RIP_WS_RESULTS, rip_result_bytes(G, npix, out->groupdq != nullptr));
         if (!w) return RIP_ENOMEM;
@@ -501,7 +539,17 @@ struct Calibration {
             RIP_HIP(ctx, hipMemcpyAsync(out->pixeldq, pdq_mid, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         if (out->cube) RIP_HIP(ctx, hipMemcpyAsync(out->cube, cur, (size_t)G * npix * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (decoded) RIP_HIP(ctx, hipMemcpyAsync(ctx->refread_host, ctx->refread_dev, 8, hipMemcpyDeviceToHost, ctx->stream));
         RIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (decoded && ctx->refread_host[0] != 0) {
+            // the pieces do not belong together: what was computed from the clamped samples is not a result.  The word is cleared
+            // so that the next call starts clean whatever it does.
+            const unsigned long long bad = ctx->refread_host[0];
+            ctx->refread_host[0] = 0;
+            RIP_HIP(ctx, hipMemsetAsync(ctx->refread_dev, 0, 8, ctx->stream));
+            return rip_fail(ctx, RIP_EINVAL, "calibrate: %llu samples of the decoded ramp lie outside 0..65535: reference_read, data and "
+                            "data_encoding_offset %d do not belong together (the outputs are invalid)", bad, (int)in->data_encoding_offset);
+        }
         return RIP_OK;
     }
 };

@@ -245,6 +245,12 @@ struct rip_ctx {   // host-only: no kernel reads it
     size_t batch_bytes[4] = {0, 0, 0, 0};
     int batch_completed = 0;  // of the last rip_calibrate_batch: ramps completed (all of them unless it returned an error)
 
+    // ---- host ramps stored with the reference read subtracted (rip_ramp_desc::reference_read; refread.hip): the device words the
+    // decode kernels count their out-of-range samples in (one per ramp of a batch) and their page-locked mirror, made by the first
+    // call that decodes (rip_refread_words) and kept
+    unsigned long long *refread_dev = nullptr, *refread_host = nullptr;
+    int refread_cap = 0;
+
     // ---- 1/f frames (pink.hip): transform plan and buffers of the last (length, batch) kept between calls
     void *pink_plan = nullptr, *pink_z = nullptr, *pink_s = nullptr, *pink_tab = nullptr;   // (library plan OR own tables: pink_own)
     bool pink_own = false;
@@ -430,6 +436,14 @@ int rip_refpix_row_general(rip_ctx *ctx, float *d_image, int ny, int width, int 
                            double slope, float *d_ref_med, float *d_sci_med, float *d_ctr);
 int rip_refpix_channel_general(rip_ctx *ctx, float *d_image, int ny, int width, int channel_start, int channel_end, int nchan,
                                const double *d_lines, float *d_bottom_top);
+
+// refread.hip
+// out[k] = clip(i32(data[k]) + i32(ref) - offset, 0, 65535) on (ngrp, n) u16 device arrays (out may be data), *count += the samples
+// the clip changed; queued on `stream` (null: the context's main stream).  The caller zeroes *count.
+int rip_launch_decode_reference_read(rip_ctx *ctx, const uint16_t *data, int ngrp, size_t n, const uint16_t *ref, int offset,
+                                     uint16_t *out, unsigned long long *count, hipStream_t stream = nullptr);
+// at least n counting words on the device (rip_ctx::refread_dev) with their page-locked mirror; RIP_OK or the error recorded
+int rip_refread_words(rip_ctx *ctx, int n);
 
 // misc.hip
 int rip_launch_embed(rip_ctx *ctx, const void *src, void *dst, int nplanes, int ny, int nx, int nb, int elem_size);

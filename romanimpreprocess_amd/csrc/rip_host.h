@@ -86,7 +86,13 @@ RIP_SHARED RipPlan *get_plan(rip_ctx *ctx, int id);   // nullptr (error recorded
 // calibrate.hip: a ramp in HOST memory is staged into device buffers, its results laid out there and copied back, by
 // rip_calibrate and by rip_calibrate_batch (batch.hip)
 RIP_SHARED size_t rip_host_ramp_bytes(const rip_ramp_desc &in, int ny, int nx);
-RIP_SHARED int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev);
+// (count: the device word that receives the out-of-range samples of a ramp stored with its reference read subtracted, zeroed and
+// added to on `st`; not looked at for a ramp without reference planes)
+RIP_SHARED int rip_upload_host_ramp(rip_ctx *ctx, const rip_ramp_desc &in, int ny, int nx, char *w, hipStream_t st, rip_ramp_desc *dev,
+                                    unsigned long long *count = nullptr);
+// the refusals of rip_ramp_desc::reference_read / reference_amp33 (`who`: the entry's name, for the error text)
+RIP_SHARED int rip_check_reference_read(rip_ctx *ctx, const rip_ramp_desc &in, const char *who);
+inline bool rip_ramp_is_encoded(const rip_ramp_desc &in) { return in.reference_read || in.reference_amp33; }
 RIP_SHARED size_t rip_result_bytes(int G, size_t npix, bool groupdq);
 RIP_SHARED rip_outputs rip_result_planes(char *w, const rip_outputs &host, size_t npix);
 RIP_SHARED int rip_download_results(rip_ctx *ctx, const rip_outputs &dev, const rip_outputs &host, int G, size_t npix, hipStream_t st);

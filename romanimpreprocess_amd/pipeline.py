@@ -134,6 +134,11 @@ class Calibrator:
         ``ramp``: dict(data u16|f32 (G,ny,nx), amp33 u16 (G,ny,128)|None, groupdq u8, pixeldq u32,
         read_pattern, frame_time).  Returns dict(slope, err_read, err_poisson, pixeldq[, groupdq][, cube], K, meta).
 
+        An exposure stored with its reference read subtracted (``sim_to_isim.extract_ref``) also carries ``reference_read`` u16
+        (ny,nx), ``data_encoding_offset`` and -- where amp33 is encoded too -- ``reference_amp33`` u16 (ny,128): data, amp33 and
+        read_pattern are then the stored ones (one group fewer than the exposure had), and the library decodes its device copies
+        before the chain.  ValueError when the pieces do not belong together (a decoded sample outside 0..65535).
+
         ``flag_saturation``: dq-init + saturation flagging on the device before the chain (the CALDIR slot must hold
         ``saturation``); ``ramp["groupdq"]`` may then be None and ``ramp["pixeldq"]`` is the mask dq.
         ``saturation_read_pattern``: compare groups of several reads with threshold * mean(reads) / last read (the read-pattern
@@ -181,6 +186,20 @@ class Calibrator:
         amp33 = None if ramp.get("amp33") is None else np.ascontiguousarray(ramp["amp33"], dtype=np.uint16)
         area = None if area_factor is None else np.ascontiguousarray(area_factor, dtype=np.float64)
         lines = None if channel_lines is None else np.ascontiguousarray(channel_lines, dtype=np.float64)
+        who = "ramp" if i is None else f"ramp {i}:"
+        ref = ref33 = None
+        if ramp.get("reference_read") is not None:   # stored with the reference read subtracted (rip_ramp_desc::reference_read)
+            if ramp.get("data_encoding_offset") is None:
+                raise ValueError(f"{who} reference_read without data_encoding_offset")
+            ref = self._reference_plane(ramp["reference_read"], (ny, nx), f"{who} reference_read")
+            if data.dtype != np.uint16:
+                raise ValueError(f"{who} reference_read needs uint16 data, not {data.dtype}")
+        if ramp.get("reference_amp33") is not None:
+            if ramp.get("data_encoding_offset") is None:
+                raise ValueError(f"{who} reference_amp33 without data_encoding_offset")
+            if amp33 is None:
+                raise ValueError(f"{who} reference_amp33 without amp33")
+            ref33 = self._reference_plane(ramp["reference_amp33"], (ny, amp33.shape[-1]), f"{who} reference_amp33")
 
         rd.location, rd.ngrp = _native.RIP_HOST, G
         rd.data, rd.data_dtype = data.ctypes.data, _native.dtype_code(data)
@@ -192,6 +211,9 @@ class Calibrator:
         rd.sat_dilution = None if dil is None else dil.ctypes.data
         rd.area_factor = None if area is None else area.ctypes.data
         rd.channel_lines = None if lines is None else lines.ctypes.data
+        rd.reference_read = None if ref is None else ref.ctypes.data
+        rd.reference_amp33 = None if ref33 is None else ref33.ctypes.data
+        rd.data_encoding_offset = 0 if (ref is None and ref33 is None) else int(ramp["data_encoding_offset"])
 
         def result(name, shape, dtype):
             a = None if given is None else given.get(name)
@@ -213,7 +235,16 @@ class Calibrator:
         if want_cube:
             res["cube"] = result("cube", (G, ny, nx), np.float32)
             od.cube = res["cube"].ctypes.data
-        return res, (data, gdq, pdq, amp33, area, lines)
+        return res, (data, gdq, pdq, amp33, area, lines, ref, ref33)
+
+    @staticmethod
+    def _reference_plane(a, shape, what):
+        """the reference plane of an encoded ramp as the library takes it: C-contiguous uint16 of ``shape`` (no silent cast: a
+        plane of another dtype is not what the encoder wrote)"""
+        a = np.asarray(a)
+        if a.dtype != np.uint16 or a.shape != tuple(shape):
+            raise ValueError(f"{what} must be a uint16 array of shape {tuple(shape)}, not {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
 
     # ---- a batch of ramps in host memory, pipelined over PCIe --------------------------------
     def calibrate_many(self, slot, ramps, exclude_first=True, ramp_opt_pars=None, jump_pars=None, want_groupdq=False,
@@ -273,6 +304,25 @@ class Calibrator:
         out.slope, out.err_read, out.err_poisson = slope_ptr, err_read_ptr, err_poisson_ptr
         out.pixeldq, out.groupdq = pixeldq_out_ptr, groupdq_out_ptr
         self.ctx.calibrate_raw(slot, plan_id, stages, rd, out)
+
+    def decode_reference_read(self, data_ptr, ngrp, n, ref_ptr, offset, out_ptr=None, want_count=False):
+        """``rip_stage_decode_reference_read`` on device memory: (ngrp, n) u16 samples at ``data_ptr`` stored with the reference
+        read at ``ref_ptr`` (n u16) subtracted become ``clip(i32(data) + i32(reference) - offset, 0, 65535)`` at ``out_ptr`` (None:
+        in place).  For the cube n = ny * nx, for amp33 n = ny * 128 with reference_amp33.  Asynchronous on the context's stream,
+        where ``calibrate_device`` finds the result.  ``want_count=True`` waits and returns the number of samples the clip
+        changed (non-zero: the pieces do not belong together); otherwise None and no synchronisation."""
+        import torch
+
+        count = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", self.ctx.device))
+        torch.cuda.current_stream(count.device).synchronize()   # torch's fill runs on torch's stream, the entry on the context's
+        self.ctx.check(self.ctx.lib.rip_stage_decode_reference_read(
+            self.ctx.h, data_ptr, int(ngrp), int(n), ref_ptr, int(offset), _native.RIP_DEVICE,
+            data_ptr if out_ptr is None else out_ptr, count.data_ptr()))
+        if not want_count:
+            self.ctx.__dict__["_refread_count"] = count   # the kernel adds to it: alive until the next call replaces it
+            return None
+        self.ctx.synchronize()
+        return int(count.item())
 
     # ---- pixel-area map ------------------------------------------------------------------
     def area_factor(self, wcs, ny, nx, device=False):
