@@ -488,7 +488,7 @@ int rip_profile_read(rip_ctx *ctx, double out_ms[4], int *ncalls);
      "pink_form"       -1     any           the complex-to-real transform of the 1/f frames: the library's own two-pass transform for power-of-two lengths (2^8 .. 2^21 points; csrc/pink_fft.h) and hipFFT otherwise; 0 = hipFFT for every length
      "overlap"         -1     -1 .. 1       the reference-pixel pre-pass of a ramp on a second stream beside the previous ramp's fused kernel: -1 by situation (wherever that kernel leaves room on the CUs: every form except the f64-ipc4d one of 5 to 8 groups, whose partial coefficient ring fills the LDS), 0 never, 1 always; a context without a second stream never overlaps
      "chain_dbg"        0     any           timing builds only: the fused kernel skips phases, results invalid
-     "guard_band"    1e-5     0 .. INFINITY (f64: the _f64 calls, and only they, take it) relative half-width of the band around the jump threshold inside which the significance is re-evaluated in the reference's exact operation order; INFINITY = always exact.  Results do not depend on it unless it is set below ~1e-6 */
+     "guard_band"    1e-5     0 .. INFINITY (f64: the _f64 calls, and only they, take it) relative half-width of the band around the jump threshold inside which the significance is re-evaluated in the reference's exact operation order; INFINITY = always exact.  It is the stage kernels' band (the fused kernel derives its own and takes only INFINITY from here).  The default 1e-5 is tested, not proven: the flags are the reference's on every ramp tried, those made to sit at the threshold included (tests/test_gpu_jump_band.py), but the bound plan.hip derives per difference (RipDiff::relerr) reaches 2.7e-5, and at 1e-6 an emulation of the stage kernel's f32 path gives wrong flags on such ramps of 16 and more groups (profiles/jump_band.txt) */
 int rip_set_option(rip_ctx *ctx, const char *name, int value);
 int rip_set_option_f64(rip_ctx *ctx, const char *name, double value);
 /* the value as it was set (what rip_set_option stored: "overlap" reads -1, 0 or 1 whatever the context can do) */

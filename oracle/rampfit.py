@@ -108,10 +108,11 @@ def difference_list(g, start):
     return out
 
 
-def fit_and_flag(data, flags, gain, read, meta, nborder, exclude_first=True, truncate=None, jump_pars=None):
+def fit_and_flag(data, flags, gain, read, meta, nborder, exclude_first=True, truncate=None, jump_pars=None, diag=None):
     """One pass of slope fit + jump flagging (``jump_detect``).  ``flags`` (G,ny,nx) is OR-ed in place.
 
-    Returns slope, err_read, err_poisson (f32 planes) and the significance cube (f32).
+    Returns slope, err_read, err_poisson (f32 planes) and the significance cube (f32).  ``diag``: optional dict that receives
+    the threshold plane the significances were compared with (``sthresh``).
     """
     pars = dict(DEFAULT_JUMP_PARS)
     if jump_pars:
@@ -139,6 +140,8 @@ def fit_and_flag(data, flags, gain, read, meta, nborder, exclude_first=True, tru
     x = np.clip(slope, IA, IB)
     x = np.log(x / IA) / np.log(IB / IA)
     sthresh = SA + (SB - SA) * x
+    if diag is not None:
+        diag["sthresh"] = sthresh
 
     pairs = difference_list(g, start)
     smap = np.zeros((2 * (g - start) - 3, ny, nx), dtype=np.float32)

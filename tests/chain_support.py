@@ -19,12 +19,13 @@ MAX_NY = 1600
 
 
 def read_pattern(G):
-    """G groups of uneven lengths (1, 1, 2, 3, 5, 2, 1, 4, ... reads), consecutive reads, the first group the single read 0"""
+    """G groups of uneven lengths (1, 1, 2, 3, 5, 2, 1, 4, ... reads), consecutive reads, the first group the single read 0; the
+    16 lengths repeat for a count above 16"""
     lens = [1, 1, 2, 3, 5, 2, 1, 4, 2, 3, 1, 2, 6, 1, 2, 1]
     rp, at = [], 0
     for g in range(G):
-        rp.append(list(range(at, at + lens[g])))
-        at += lens[g]
+        rp.append(list(range(at, at + lens[g % 16])))
+        at += lens[g % 16]
     return rp
 
 
