@@ -25,8 +25,7 @@ def classify(tilnu_21, tilnu_31, tilnu_41, I_arr, ctx=None):
     I = np.ascontiguousarray(I_arr, dtype=np.float64)
     types = np.empty(I.shape, np.int32)
     params = np.empty(I.shape + (4,), np.float64)
-    ctx.check(ctx.lib.rip_stage_pearson(ctx.h, I.size, I.ctypes.data, float(tilnu_21), float(tilnu_31), float(tilnu_41), 0, 0,
-                                        None, types.ctypes.data, params.ctypes.data))
+    ctx.call("rip_stage_pearson", I.size, I, tilnu_21, tilnu_31, tilnu_41, 0, 0, None, types, params)
     return types, params
 
 
@@ -46,7 +45,6 @@ def draw_from_Pearson(tilnu_21, tilnu_31, tilnu_41, I_arr, *, atol=0.0, rng=None
     if I.size == 0:
         return out
     _calls[0] += 1
-    ctx.check(ctx.lib.rip_stage_pearson(ctx.h, I.size, I.ctypes.data, float(tilnu_21), float(tilnu_31), float(tilnu_41),
-                                        _seed_from(rng), int(_calls[0] if stream is None else stream) & 0xFFFFFFFF,
-                                        out.ctypes.data, None, None))
+    ctx.call("rip_stage_pearson", I.size, I, tilnu_21, tilnu_31, tilnu_41, _seed_from(rng),
+             int(_calls[0] if stream is None else stream) & 0xFFFFFFFF, out, None, None)
     return out

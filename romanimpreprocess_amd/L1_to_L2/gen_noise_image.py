@@ -65,9 +65,7 @@ def inject_read_noise(data, read_noise, read_pattern, nb=pars.nborder, normals=N
         if normals.shape != (G, ny - 2 * nb, nx - 2 * nb):
             raise ValueError(f"normals have shape {normals.shape}")
     out = data if is_dev(data) else np.empty_like(data)   # the entry point allows in == out
-    ctx.check(ctx.lib.rip_stage_noise_inject(ctx.h, data.ctypes.data, G, ny, nx, nb, read.ctypes.data, nreads.ctypes.data,
-                                             None if normals is None else normals.ctypes.data, int(seed) & (2**64 - 1),
-                                             int(layer), out.ctypes.data))
+    ctx.call("rip_stage_noise_inject", data, G, ny, nx, nb, read, nreads, normals, int(seed) & (2**64 - 1), layer, out)
     return out
 
 
@@ -80,8 +78,7 @@ def noise_1f_frames(nframes, rows=pars.nside, width=pars.channelwidth, normals=N
         if normals.shape != (nframes, 4 * rows * width):
             raise ValueError(f"normals have shape {normals.shape}, expected {(nframes, 4 * rows * width)}")
     out = np.empty((nframes, rows, width), np.float32)
-    ctx.check(ctx.lib.rip_stage_noise_1f(ctx.h, rows, width, nframes, None if normals is None else normals.ctypes.data,
-                                         int(seed) & (2**64 - 1), int(stream) & 0xFFFFFFFF, out.ctypes.data))
+    ctx.call("rip_stage_noise_1f", rows, width, nframes, normals, int(seed) & (2**64 - 1), int(stream) & 0xFFFFFFFF, out)
     return out
 
 
@@ -136,10 +133,8 @@ def poisson_resample(diff, skylevel, gain, frame_time, read_pattern, weights, ha
         samples = np.ascontiguousarray(samples, dtype=np.float64)
         if samples.shape != (nsamp,) + diff.shape:
             raise ValueError(f"samples have shape {samples.shape}, expected {(nsamp,) + diff.shape}")
-    ctx.check(ctx.lib.rip_stage_poisson_resample(
-        ctx.h, sky_.ctypes.data, g_.ctypes.data, _native.dtype_code(g_), diff.size, float(frame_time), ngrp, first.ctypes.data,
-        count.ctypes.data, w.ctypes.data, hw.ctypes.data, es.ctypes.data, None if samples is None else samples.ctypes.data,
-        nsamp, int(seed) & (2**64 - 1), int(layer), diff.ctypes.data))
+    ctx.call("rip_stage_poisson_resample", sky_, g_, _native.dtype_code(g_), diff.size, frame_time, ngrp, first, count, w, hw, es,
+             samples, nsamp, int(seed) & (2**64 - 1), layer, diff)
     return diff
 
 

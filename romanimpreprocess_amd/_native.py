@@ -10,183 +10,33 @@ import os
 
 import numpy as np
 
+from . import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROMANHIP_LIB") or os.path.join(_HERE, "libromanhip.so")   # the env var: A/B timing of library variants
 
-RIP_MAX_GROUPS = 64
-RIP_TIMING_BUILD_FLAG = 1000000   # include/romanhip.h
-RIP_F32, RIP_F64, RIP_U16 = 0, 1, 2
-RIP_HOST, RIP_DEVICE = 0, 1
-RIP_INPUTS_STREAM_ORDERED, RIP_INPUTS_COMPLETE = 0, 1
-BIAS_ABSENT, BIAS_PRESENT, BIAS_DROPPED = 0, 1, 2   # rip_caldir_bias_state
-RIP_PROJ_TAN, RIP_PROJ_STG, RIP_PROJ_ZEA, RIP_PROJ_ARC, RIP_PROJ_SIN = 0, 1, 2, 3, 4
-RIP_SIP_MAX_ORDER = 9
+# The C interface is stated once, in include/romanhip.h; everything below is read from it (``_header.parse``).
+with open(os.path.join(os.path.dirname(_HERE), "include", "romanhip.h")) as _f:
+    HEADER = _header.parse(_f.read())
+PROTOTYPES = HEADER.prototypes   # name -> _header.Proto: per parameter its name, ctypes type and pointee
 
-STAGE_REFPIX, STAGE_BIAS, STAGE_LIN, STAGE_IPC, STAGE_RAMPFIT, STAGE_DARK, STAGE_FLAT = (1 << i for i in range(7))
-STAGE_ALL = 0x7F
+# every constant of the header under its own name (RIP_F32, RIP_HOST, RIP_PROJ_TAN, RIP_MAX_GROUPS, RIP_EINVAL, ...); the stage
+# bits and the bias states also without the prefix (STAGE_REFPIX .. STAGE_ALL, BIAS_ABSENT / BIAS_PRESENT / BIAS_DROPPED)
+globals().update(HEADER.constants)
+globals().update({k[4:]: v for k, v in HEADER.constants.items() if k.startswith(("RIP_STAGE_", "RIP_BIAS_"))})
 
-c_float_p = C.POINTER(C.c_float)
-c_double_p = C.POINTER(C.c_double)
-c_u8_p = C.POINTER(C.c_uint8)
-c_u16_p = C.POINTER(C.c_uint16)
-c_u32_p = C.POINTER(C.c_uint32)
+# the structs; a pointer field of any kind is a c_void_p that the caller fills with an address
+CaldirDesc = HEADER.structs["rip_caldir_desc"]
+PlanDesc = HEADER.structs["rip_plan_desc"]
+RampDesc = HEADER.structs["rip_ramp_desc"]
+Outputs = HEADER.structs["rip_outputs"]
+SynthCal = HEADER.structs["rip_synth_cal"]    # DEVICE pointers
+CrParams = HEADER.structs["rip_cr_params"]    # the cosmic-ray model's constants (defaults: romanisim's)
+WcsDesc = HEADER.structs["rip_wcs_desc"]      # a FITS zenithal (+SIP) WCS, crpix 0-based, angles in degrees
 
-
-class CaldirDesc(C.Structure):
-    _fields_ = [
-        ("ny", C.c_int32), ("nx", C.c_int32), ("nborder", C.c_int32),
-        ("ngrp_dark", C.c_int32), ("dark_data", c_float_p), ("dark_slope", c_float_p), ("dark_dq", c_u32_p),
-        ("read_noise", c_float_p), ("amp33_med", c_float_p), ("refout_slope", C.c_double),
-        ("gain", C.c_void_p), ("gain_dtype", C.c_int32),
-        ("lin_nplanes", C.c_int32), ("lin_coefs", c_float_p),
-        ("lin_smin", c_float_p), ("lin_smax", c_float_p), ("lin_sref", c_float_p), ("lin_dq", c_u32_p),
-        ("ipc4d", C.c_void_p), ("ipc_dtype", C.c_int32),
-        ("flat", c_float_p),
-        ("ngrp_bias", C.c_int32), ("biascorr", c_float_p),
-        ("saturation", c_float_p), ("saturation_dq", c_u32_p),
-    ]
-
-
-class PlanDesc(C.Structure):
-    _fields_ = [
-        ("ngrp", C.c_int32), ("exclude_first", C.c_int32), ("do_not_flag_first", C.c_int32),
-        ("tbar", C.c_float * RIP_MAX_GROUPS), ("tau", C.c_float * RIP_MAX_GROUPS),
-        ("nreads", C.c_int16 * RIP_MAX_GROUPS), ("K", C.c_float * RIP_MAX_GROUPS),
-        ("nvariants", C.c_int32), ("variant_g", C.c_int32 * RIP_MAX_GROUPS),
-        ("variant_coef", C.c_float * RIP_MAX_GROUPS), ("variant_rfac", C.c_float * RIP_MAX_GROUPS),
-        ("sthresh_a", C.c_double), ("sthresh_b", C.c_double), ("ithresh_a", C.c_double), ("ithresh_b", C.c_double),
-    ]
-
-
-class RampDesc(C.Structure):
-    _fields_ = [
-        ("location", C.c_int32), ("ngrp", C.c_int32), ("data", C.c_void_p), ("data_dtype", C.c_int32),
-        ("amp33", C.c_void_p), ("groupdq", C.c_void_p), ("pixeldq", C.c_void_p), ("area_factor", C.c_void_p),
-        ("channel_lines", C.c_void_p),
-        ("flag_saturation", C.c_int32), ("sat_backup", C.c_int32), ("sat_skip_firstn", C.c_int32),
-        ("sat_dilution", C.c_void_p),
-        ("inputs_ready", C.c_int32), ("ready_event", C.c_void_p), ("or_first_group", C.c_int32),
-        ("reference_read", C.c_void_p), ("reference_amp33", C.c_void_p), ("data_encoding_offset", C.c_int32),
-    ]
-
-
-class Outputs(C.Structure):
-    _fields_ = [
-        ("location", C.c_int32), ("slope", C.c_void_p), ("err_read", C.c_void_p), ("err_poisson", C.c_void_p),
-        ("pixeldq", C.c_void_p), ("groupdq", C.c_void_p), ("cube", C.c_void_p),
-    ]
-
-
-class SynthCal(C.Structure):   # rip_synth_cal: DEVICE pointers
-    _fields_ = [
-        ("ny", C.c_int32), ("nx", C.c_int32), ("nb", C.c_int32), ("channelwidth", C.c_int32), ("nplanes", C.c_int32),
-        ("gain_dtype", C.c_int32), ("ipc_dtype", C.c_int32), ("amp33_valid", C.c_int32),
-        ("gain", C.c_void_p), ("read_noise", C.c_void_p), ("resetnoise", C.c_void_p), ("dark_slope", C.c_void_p),
-        ("dark", C.c_void_p), ("lin_coefs", C.c_void_p), ("smin", C.c_void_p), ("smax", C.c_void_p), ("ipc4d", C.c_void_p),
-        ("biascorr", C.c_void_p), ("tbias", C.c_double), ("amp33_med", C.c_void_p), ("amp33_std", C.c_void_p),
-        ("m_pink", C.c_double), ("ru_pink", C.c_double), ("u_pink", C.c_double), ("c_pink", C.c_double),
-    ]
-
-
-class CrParams(C.Structure):   # rip_cr_params: the cosmic-ray model's constants (defaults: romanisim's)
-    _fields_ = [
-        ("flux", C.c_double), ("area", C.c_double), ("conversion_factor", C.c_double), ("pixel_size", C.c_double),
-        ("pixel_depth", C.c_double), ("min_dedx", C.c_double), ("max_dedx", C.c_double), ("moyal_location", C.c_double),
-        ("moyal_scale", C.c_double), ("min_len", C.c_double), ("max_len", C.c_double), ("len_slope", C.c_double),
-        ("grid_size", C.c_int32), ("_pad", C.c_int32),
-    ]
-
-
-class WcsDesc(C.Structure):   # rip_wcs_desc: a FITS zenithal (+SIP) WCS, crpix 0-based, angles in degrees
-    _fields_ = [
-        ("projection", C.c_int32), ("sip_order", C.c_int32), ("crpix", C.c_double * 2), ("cd", (C.c_double * 2) * 2),
-        ("crval", C.c_double * 2), ("lonpole", C.c_double),
-        ("sip_a", (C.c_double * (RIP_SIP_MAX_ORDER + 1)) * (RIP_SIP_MAX_ORDER + 1)),
-        ("sip_b", (C.c_double * (RIP_SIP_MAX_ORDER + 1)) * (RIP_SIP_MAX_ORDER + 1)),
-    ]
-
-
-# every symbol include/romanhip.h declares: name -> (restype, argtypes)
-_VP = C.c_void_p
-_I = C.c_int
-SYMBOLS = {
-    "rip_version": (_I, []),
-    "rip_ctx_create": (_I, [_I, C.POINTER(_VP)]),
-    "rip_ctx_destroy": (None, [_VP]),
-    "rip_last_error": (C.c_char_p, [_VP]),
-    "rip_synchronize": (_I, [_VP]),
-    "rip_stream": (_VP, [_VP]),
-    "rip_host_alloc": (_VP, [_VP, C.c_size_t]),
-    "rip_host_free": (None, [_VP, _VP]),
-    "rip_caldir_upload": (_I, [_VP, _I, C.POINTER(CaldirDesc)]),
-    "rip_caldir_drop": (_I, [_VP, _I]),
-    "rip_caldir_first_group_safe": (_I, [_VP, _I]),
-    "rip_caldir_bias_state": (_I, [_VP, _I]),
-    "rip_plan_create": (_I, [_VP, C.POINTER(PlanDesc), C.POINTER(_I)]),
-    "rip_plan_destroy": (_I, [_VP, _I]),
-    "rip_plan_desc_first_weight_zero": (_I, [C.POINTER(PlanDesc)]),
-    "rip_calibrate": (_I, [_VP, _I, _I, C.c_uint, C.POINTER(RampDesc), C.POINTER(Outputs)]),
-    "rip_calibrate_batch": (_I, [_VP, _I, _I, C.c_uint, _I, C.POINTER(RampDesc), C.POINTER(Outputs)]),
-    "rip_calibrate_batch_completed": (_I, [_VP]),
-    "rip_stage_pearson": (_I, [_VP, C.c_size_t, _VP, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_uint32, _VP, _VP, _VP]),
-    "rip_stage_refpix_image": (_I, [_VP, _VP, _I, _I, C.c_double, _I, _I, _VP, _VP, _VP, _VP]),
-    "rip_stage_refpix_row": (_I, [_VP, _VP, _I, _I, _I, _I, _I, C.c_double, _VP, _VP, _VP]),
-    "rip_stage_refpix_channel": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
-    "rip_stage_refpix_tables": (_I, [_VP, _VP, _I, _VP, _VP, _VP, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP]),
-    "rip_synth_frames_ahead": (_I, [_VP, _I, _I, _I, C.c_uint64]),
-    "rip_stage_jump_detect": (_I, [_VP, _I, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
-    "rip_stage_multilin": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
-    "rip_stage_ipc_image": (_I, [_VP, _I, _I, _VP, _I, _I, _I, _VP, _I, _VP, _I, _VP]),
-    "rip_stage_correct_cube": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _I]),
-    "rip_stage_ramp_fit": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP]),
-    "rip_stage_get_flat": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP]),
-    "rip_stage_build_mask": (_I, [_VP, _VP, _I, _I, _VP, _VP]),
-    "rip_stage_endslice": (_I, [_VP, _VP, _I, _I, _I, _I, _VP]),
-    "rip_stage_bin_mean": (_I, [_VP, _VP, _VP, _I, _I, _I, _VP]),
-    "rip_stage_select_ranks": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
-    "rip_stage_gauss_hist": (_I, [_VP, _VP, C.c_int64, _VP, _I, C.c_double, _VP]),
-    "rip_stage_legendre2d": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _I, _VP]),
-    "rip_stage_pixel_area": (_I, [_VP, C.POINTER(WcsDesc), _I, _I, C.c_double, _I, _VP]),
-    "rip_stage_invlinearity": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
-    "rip_stage_noise_inject": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, C.c_uint64, C.c_uint32, _VP]),
-    "rip_stage_noise_1f": (_I, [_VP, _I, _I, _I, _VP, C.c_uint64, C.c_uint32, _VP]),
-    "rip_stage_poisson_resample": (_I, [_VP, _VP, _VP, _I, C.c_size_t, C.c_double, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I,
-                                        C.c_uint64, C.c_uint32, _VP]),
-    "rip_stats_l1_diff": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP]),
-    "rip_stats_l2_pack": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
-    "rip_stats_reduce": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
-    "rip_synth_apportion": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, C.c_uint64, _VP]),
-    "rip_synth_resultants": (_I, [_VP, C.POINTER(SynthCal), _I, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP]),
-    "rip_synth_fill": (_I, [_VP, C.POINTER(SynthCal), _I, _VP, _I, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
-    "rip_synth_noise_1f": (_I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint32, _VP]),
-    "rip_synth_cr_tracks": (_I, [_VP, C.POINTER(CrParams), _I, C.c_double, _I, _I, C.c_uint64, _VP, _VP, _I, _VP, _VP]),
-    "rip_synth_cr_deposit": (_I, [_VP, C.POINTER(CrParams), _I, _I, _I, _VP, _VP, _I, C.c_uint64, _VP, _VP, _VP]),
-    "rip_synth_extract_ref": (_I, [_VP, _VP, _I, C.c_size_t, _I, _VP]),
-    "rip_stage_decode_reference_read": (_I, [_VP, _VP, _I, C.c_size_t, _VP, _I, _I, _VP, _VP]),
-    "rip_cal_biascorr": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, C.c_double, _I, _VP, _VP, _VP]),
-    "rip_cal_pflat": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, C.c_float, _VP, _VP]),
-    "rip_cal_saturation": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
-    "rip_cal_mask": (_I, [_VP, _I, _I, _I, _VP, _VP, C.c_float, _VP, _VP, _VP]),
-    "rip_cal_group_means": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _VP, _I, _I, _VP, _I, _I]),
-    "rip_cal_sigma_clip_mean": (_I, [_VP, _VP, _I, _I, C.c_size_t, C.c_size_t, C.c_double, C.c_double, _I, _VP, _VP]),
-    "rip_cal_dark_planes": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, C.c_size_t, _VP, _VP, _VP]),
-    "rip_cal_gain_ipc4d": (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _I, _VP]),
-    "rip_set_option_f64": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
-    "rip_set_option": (_I, [_VP, C.c_char_p, _I]),
-    "rip_get_option": (_I, [_VP, C.c_char_p, C.POINTER(_I)]),
-    "rip_get_option_f64": (_I, [_VP, C.c_char_p, c_double_p]),
-    "rip_reset_options": (_I, [_VP]),
-    "rip_option_info": (_I, [_I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
-    "rip_last_chain_form": (_I, [_VP]),
-    "rip_last_chain_first_group": (_I, [_VP]),
-    "rip_last_chain_bias_stream": (_I, [_VP]),
-    "rip_last_prepass_gate": (_I, [_VP, C.POINTER(C.c_int)]),
-    "rip_chain_form_for": (_I, [_I, _I, _I, _I]),
-    "rip_chain_geometry_for": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
-    "rip_last_chain_geometry": (_I, [_VP, C.POINTER(_I)]),
-    "rip_profile_enable": (_I, [_VP, _I]),
-    "rip_profile_read": (_I, [_VP, C.POINTER(C.c_double), C.POINTER(_I)]),
-}
+# every symbol the header declares: name -> (restype, argtypes).  Pointers to a header struct are POINTER(mirror), const char *
+# is c_char_p, every other pointer c_void_p: raw callers pass ndarray.ctypes.data, data_ptr(), byref(...) and ctypes arrays.
+SYMBOLS = {name: (p.restype, [q.ctype for q in p.params]) for name, p in PROTOTYPES.items()}
 
 _lib = None
 
@@ -221,20 +71,100 @@ def load_library():
     return lib
 
 
+# ---- one checked call path ------------------------------------------------------------------------------------------------
+# numpy dtype of a pointer's element type (``Param.elem``); void, rip_ctx and pointers to pointers are not in it: anything goes
+_ELEM_DTYPE = {name: np.dtype(t) for name, t in _header.SCALARS.items() if name != "char"}
+_CTYPES = (C._SimpleCData, C.Array, C.Structure, C._Pointer, type(C.byref(C.c_int())))
+
+
+def _convert(fn, p, x):
+    """``x`` as the library takes it for parameter ``p`` of ``fn``; TypeError where it is not what the header declares"""
+    t = type(x)
+    if p.depth == 0:
+        to = float if p.ctype is C.c_double or p.ctype is C.c_float else int
+        if t is int or t is float or t is bool or getattr(x, "shape", None) == ():   # Python and numpy scalars, never an array
+            try:
+                return to(x)
+            except (TypeError, ValueError):
+                pass
+        raise TypeError(f"{fn}: parameter '{p.name}' is a scalar ({p.ctext}), got {_describe(x)}")
+    if x is None or t is int:
+        return x
+    want = _ELEM_DTYPE.get(p.elem) if p.depth == 1 else None
+    if t is np.ndarray or (hasattr(x, "ctypes") and hasattr(x, "dtype")):   # a numpy array or a DevArray
+        if (want is not None or p.elem == "void") and x.flags.c_contiguous \
+                and (want is None or x.dtype == want or (want == np.uint8 and x.dtype == np.bool_)):
+            return x.ctypes.data
+    elif hasattr(x, "data_ptr"):   # a torch tensor: u16 / u32 bits live in int16 / int32 tensors, so width and kind are compared
+        if (want is not None or p.elem == "void") and x.is_contiguous() \
+                and (want is None or (x.element_size() == want.itemsize and not x.dtype.is_complex
+                                      and x.dtype.is_floating_point == (want.kind == "f"))):
+            return x.data_ptr()
+    elif isinstance(x, _CTYPES):   # byref(...), ctypes arrays and pointers, a handle; a struct goes by reference
+        return C.byref(x) if isinstance(x, C.Structure) else x
+    elif p.ctype is C.c_char_p and isinstance(x, (str, bytes)):
+        return x.encode() if isinstance(x, str) else x
+    elif isinstance(x, np.integer):
+        return int(x)
+    raise TypeError(f"{fn}: parameter '{p.name}' ({p.ctext}): expected a C-contiguous array of "
+                    f"{want.name if want is not None else p.elem}, None or an address, got {_describe(x)}")
+
+
+def _describe(x):
+    if hasattr(x, "data_ptr"):
+        return f"a {'contiguous' if x.is_contiguous() else 'non-contiguous'} tensor of {x.dtype}"
+    if hasattr(x, "dtype") and hasattr(x, "flags"):
+        return f"a {'C-contiguous' if x.flags.c_contiguous else 'non-contiguous'} array of {x.dtype}"
+    return f"{type(x).__name__} {x!r}"[:80]
+
+
+def marshal(name, args):
+    """The arguments of entry ``name`` checked against its prototype in the header and converted to what ctypes passes on: an
+    array (numpy, ``DevArray``, torch tensor) must be contiguous and of the pointer's element type and gives its address; None
+    is NULL; an int is an address; ``byref(...)`` and ctypes objects go through (a struct by reference); scalars are converted
+    by their C type.  It checks, it never casts.  Needs no GPU and no context."""
+    params = PROTOTYPES[name].params
+    if len(args) != len(params):
+        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(p.name for p in params)}), got {len(args)}")
+    return [_convert(name, p, x) for p, x in zip(params, args)]
+
+
+def _fail(lib, h, rc, exc=RuntimeError):
+    msg = lib.rip_last_error(h)
+    text = msg.decode() if msg else f"status {rc}"
+    raise (ValueError if rc == RIP_EINVAL else exc)(f"libromanhip: {text}")
+
+
+def call(name, *args):
+    """Entry ``name`` of the library on ``marshal``-ed arguments.  A negative return of an ``int`` entry raises (ValueError for
+    RIP_EINVAL, RuntimeError otherwise) with the library's message.  This is the form for the entries without a context
+    (``rip_chain_form_for``, ``rip_option_info``, ...); ``Context.call`` puts the handle in front."""
+    lib = load_library()
+    rc = getattr(lib, name)(*marshal(name, args))
+    if rc is not None and rc < 0 and PROTOTYPES[name].restype is C.c_int:
+        _fail(lib, args[0] if _takes_ctx(name) else None, rc)
+    return rc
+
+
+def _takes_ctx(name):
+    params = PROTOTYPES[name].params
+    return bool(params) and params[0].elem == "rip_ctx" and params[0].depth == 1
+
+
 def chain_form_for(lin_nplanes, ngroups, ipc_dtype=RIP_F32, gain_dtype=RIP_F32):
     """2 where the library has a fused-kernel form for a complete chain on a ramp of ``ngroups`` groups with ``lin_nplanes``
     Legendre planes and these ipc4d / gain dtypes (RIP_F32, RIP_F64), 0 where the stage kernels run.  Needs no GPU.  It does not
     know the plan or the CALDIR set: a ramp also takes the stage kernels when the plan's differences are not the full set or
     the set's flag words cannot be merged (``Context.last_chain_form`` tells what a call really ran)."""
-    return int(load_library().rip_chain_form_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype)))
+    return call("rip_chain_form_for", lin_nplanes, ngroups, ipc_dtype, gain_dtype)
 
 
 def option_table():
     """The library's option table (``rip_option_info``) as name -> (default, lowest, highest accepted value); the one f64 option,
     "guard_band", appears with its values cut to int.  Needs no GPU."""
-    lib, table = load_library(), {}
+    table = {}
     name, d, lo, hi = C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
-    while lib.rip_option_info(len(table), C.byref(name), C.byref(d), C.byref(lo), C.byref(hi)):
+    while call("rip_option_info", len(table), C.byref(name), C.byref(d), C.byref(lo), C.byref(hi)):
         table[name.value.decode()] = (d.value, lo.value, hi.value)
     return table
 
@@ -250,35 +180,22 @@ def chain_geometry_for(lin_nplanes, ngroups, ipc_dtype, ny, nx, ncu, reserve=Non
     if reserve is None:
         reserve = option_table()["chain_reserve"][0]
     out = (C.c_int * 8)()
-    rc = load_library().rip_chain_geometry_for(int(lin_nplanes), int(ngroups), int(ipc_dtype), int(gain_dtype), int(ny), int(nx),
-                                               int(ncu), int(reserve), int(bool(quad_ok)), out)
+    rc = call("rip_chain_geometry_for", lin_nplanes, ngroups, ipc_dtype, gain_dtype, ny, nx, ncu, reserve, bool(quad_ok), out)
     return dict(zip(GEOMETRY_FIELDS, out)) if rc == 2 else None
 
 
+def float_array(a):
+    """C-contiguous float32 or float64 array of ``a`` (any other dtype becomes float64): what goes to a ``const void *`` parameter
+    that comes with a ``dtype_code``"""
+    a = np.ascontiguousarray(a)
+    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+
 def dtype_code(arr):
-    if arr.dtype == np.float32:
-        return RIP_F32
-    if arr.dtype == np.float64:
-        return RIP_F64
-    if arr.dtype == np.uint16:
-        return RIP_U16
-    raise TypeError(f"unsupported dtype {arr.dtype}")
-
-
-def ptr(arr):
-    """address of a C-contiguous numpy array (the caller keeps it alive), or None."""
-    if arr is None:
-        return None
-    if not arr.flags["C_CONTIGUOUS"]:
-        raise ValueError("array must be C-contiguous")
-    return arr.ctypes.data
-
-
-def _c(arr, dtype=None):
-    """C-contiguous view/copy with the given dtype (None keeps the dtype)."""
-    if arr is None:
-        return None
-    return np.ascontiguousarray(arr, dtype=dtype)
+    code = {np.dtype(np.float32): RIP_F32, np.dtype(np.float64): RIP_F64, np.dtype(np.uint16): RIP_U16}.get(arr.dtype)
+    if code is None:
+        raise TypeError(f"unsupported dtype {arr.dtype}")
+    return code
 
 
 class Context:
@@ -287,18 +204,24 @@ class Context:
     def __init__(self, device=0):
         self.lib = load_library()
         h = C.c_void_p()
-        rc = self.lib.rip_ctx_create(int(device), C.byref(h))
-        if rc != 0:
+        rc = self.lib.rip_ctx_create(*marshal("rip_ctx_create", (device, C.byref(h))))
+        if rc != 0:   # no context to ask: the message of the last failed create
             msg = self.lib.rip_last_error(None)
             raise RuntimeError(f"rip_ctx_create(device={device}) failed: {msg.decode() if msg else rc}")
         self.h = h
         self.device = int(device)
-        self._keep = {}
         self.caldir_dtypes = {}   # slot -> (Legendre planes, ipc4d dtype, gain dtype) of the set uploaded there
+        # what every pipeline.Calibrator on this context shares
+        self.shapes = {}          # slot -> (ny, nx) of the set uploaded there
+        self.caldir_owner = {}    # slot -> the owner tag given to Calibrator.load_caldir
+        self.plans = {}           # plan configuration -> (plan id, meta)
+        self.result_pool = None   # the pipeline.ResultPool of result arrays (made by the first Calibrator)
+        self.area_cache = {}      # (WCS digest, ny, nx, on the device) -> pixel-area map, at most two
+        self.refread_count = None   # the device word the last asynchronous decode_reference_read adds to: kept alive here
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.rip_ctx_destroy(self.h)
+            self.lib.rip_ctx_destroy(self.h)   # direct: this also runs at interpreter exit, when the module's globals may be gone
             self.h = None
 
     def __del__(self):
@@ -307,48 +230,53 @@ class Context:
         except Exception:
             pass
 
+    def call(self, name, *args):
+        """Entry ``name`` on this context: the handle goes in front where the entry's first parameter is ``rip_ctx *``, the
+        arguments through ``marshal``.  A negative return of an ``int`` entry raises as ``check`` does; a non-negative one is
+        returned as int, other return types as they are."""
+        return call(name, self.h, *args) if _takes_ctx(name) else call(name, *args)
+
     def check(self, rc, exc=RuntimeError):
+        """for raw callers of ``ctx.lib``: raise on a non-zero status with the library's message"""
         if rc != 0:
-            msg = self.lib.rip_last_error(self.h)
-            text = msg.decode() if msg else f"status {rc}"
-            raise (ValueError if rc == -1 else exc)(f"libromanhip: {text}")
+            _fail(self.lib, self.h, rc, exc)
 
     def synchronize(self):
-        self.check(self.lib.rip_synchronize(self.h))
+        self.call("rip_synchronize")
 
     def pinned_empty(self, shape, dtype):
         """A numpy array in page-locked host memory (``rip_host_alloc``), freed with the array."""
         import weakref
 
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        p = self.lib.rip_host_alloc(self.h, nbytes)
+        p = self.call("rip_host_alloc", nbytes)
         if not p:
-            self.check(-2, MemoryError)
+            self.check(RIP_ENOMEM, MemoryError)
         buf = (C.c_ubyte * max(nbytes, 1)).from_address(p)
         arr = np.frombuffer(buf, dtype=np.uint8, count=nbytes).view(dtype).reshape(shape)
-        weakref.finalize(buf, self.lib.rip_host_free, self.h, p).atexit = False   # at exit the process returns it
+        weakref.finalize(buf, call, "rip_host_free", self.h, p).atexit = False   # at exit the process returns it
         return arr
 
     def set_option(self, name, value):
-        self.check(self.lib.rip_set_option(self.h, name.encode(), int(value)))
+        self.call("rip_set_option", name, value)
 
     def set_option_f64(self, name, value):
         """floating-point options of this context ("guard_band")"""
-        self.check(self.lib.rip_set_option_f64(self.h, name.encode(), float(value)))
+        self.call("rip_set_option_f64", name, value)
 
     def get_option(self, name):
         v = C.c_int()
-        self.check(self.lib.rip_get_option(self.h, name.encode(), C.byref(v)))
+        self.call("rip_get_option", name, C.byref(v))
         return v.value
 
     def get_option_f64(self, name):
         v = C.c_double()
-        self.check(self.lib.rip_get_option_f64(self.h, name.encode(), C.byref(v)))
+        self.call("rip_get_option_f64", name, C.byref(v))
         return v.value
 
     def reset_options(self):
         """every option back to the library's default (``option_table``)"""
-        self.check(self.lib.rip_reset_options(self.h))
+        self.call("rip_reset_options")
 
     @contextlib.contextmanager
     def options(self, **values):
@@ -370,60 +298,51 @@ class Context:
 
     def last_chain_form(self):
         """0 = stage kernels, 2 = the fused kernel (last calibrate call; 1 and 3 were the general and wave-private fused kernels of rounds 1-2)."""
-        return int(self.lib.rip_last_chain_form(self.h))
+        return self.call("rip_last_chain_form")
 
     def last_chain_first_group(self):
         """1 = the fused launch of the last calibrate call skipped group 0 (option "skip_first"), 0 = it did not (or stage kernels)."""
-        return int(self.lib.rip_last_chain_first_group(self.h))
+        return self.call("rip_last_chain_first_group")
 
     def last_prepass_gate(self):
         """(state, give-ups) of the gate in front of the last calibrate call's overlapped pre-pass (option "prepass_gate"): state 0 =
         none queued, 1 = released by the fused kernel's workgroup count, 2 = gave up at its bound; give-ups of this context so far.
         Waits for the context's streams."""
         n = C.c_int(0)
-        rc = int(self.lib.rip_last_prepass_gate(self.h, C.byref(n)))
-        if rc < 0:
-            self.check(rc)
-        return rc, int(n.value)
+        return self.call("rip_last_prepass_gate", C.byref(n)), n.value
 
     def caldir_first_group_safe(self, slot):
         """True where the set in ``slot`` passed the upload screen that lets the fused kernel skip an excluded first group."""
-        rc = int(self.lib.rip_caldir_first_group_safe(self.h, int(slot)))
-        if rc < 0:
-            self.check(rc)
-        return rc == 1
+        return self.call("rip_caldir_first_group_safe", slot) == 1
 
     def caldir_bias_state(self, slot):
         """``BIAS_ABSENT`` (no biascorr in the set of ``slot``), ``BIAS_PRESENT`` (subtracted by every call with ``STAGE_BIAS``) or
         ``BIAS_DROPPED`` (given, every word +0: no device copy is kept and calls subtract nothing)"""
-        rc = int(self.lib.rip_caldir_bias_state(self.h, int(slot)))
-        if rc < 0:
-            self.check(rc)
-        return rc
+        return self.call("rip_caldir_bias_state", slot)
 
     def last_chain_bias_stream(self):
         """1 = the fused launch of the last calibrate call streamed the biascorr planes, 0 = it ran without them (or stage kernels)."""
-        return int(self.lib.rip_last_chain_bias_stream(self.h))
+        return self.call("rip_last_chain_bias_stream")
 
     def last_chain_geometry(self):
         """launch geometry of the last calibrate call's fused kernel (keys ``GEOMETRY_FIELDS``); all zeros after a stage-kernel run"""
         out = (C.c_int * 8)()
-        self.check(self.lib.rip_last_chain_geometry(self.h, out))
+        self.call("rip_last_chain_geometry", out)
         return dict(zip(GEOMETRY_FIELDS, out))
 
     def profile(self, on=True):
-        self.check(self.lib.rip_profile_enable(self.h, int(bool(on))))
+        self.call("rip_profile_enable", bool(on))
 
     def profile_read(self):
         """(ms per stage [refpix pre-pass, cube stage, ipc, ramp fit], number of calls) since the last read."""
         ms = (C.c_double * 4)()
         n = C.c_int(0)
-        self.check(self.lib.rip_profile_read(self.h, ms, C.byref(n)))
+        self.call("rip_profile_read", ms, C.byref(n))
         return list(ms), n.value
 
     @property
     def stream(self):
-        return self.lib.rip_stream(self.h)
+        return self.call("rip_stream")
 
     # ---- CALDIR ------------------------------------------------------------------------
     def upload_caldir(self, slot, cal, nborder=4, refout_slope=None):
@@ -431,82 +350,75 @@ class Context:
         d = CaldirDesc()
         keep = []
 
-        def P(a, dt, ptype):
+        def P(a, dt):
+            """address of ``a`` converted to ``dt`` (the copy is kept until the upload is done), None for None"""
             if a is None:
                 return None
-            a = _c(a, dt)
-            keep.append(a)
-            return a.ctypes.data_as(ptype)
+            keep.append(np.ascontiguousarray(a, dtype=dt))
+            return keep[-1].ctypes.data
 
-        gain = _c(cal["gain"]["data"])
-        if gain.dtype not in (np.float32, np.float64):
-            gain = gain.astype(np.float64)
-        keep.append(gain)
+        gain = float_array(cal["gain"]["data"])
         ny, nx = gain.shape
         d.ny, d.nx, d.nborder = ny, nx, nborder
         dark = cal.get("dark")
         if dark is not None:
             if "data" in dark and dark["data"] is not None:
                 d.ngrp_dark = dark["data"].shape[0]
-                d.dark_data = P(dark["data"], np.float32, c_float_p)
-            d.dark_slope = P(dark.get("dark_slope"), np.float32, c_float_p)
-            d.dark_dq = P(dark.get("dq"), np.uint32, c_u32_p)
+                d.dark_data = P(dark["data"], np.float32)
+            d.dark_slope = P(dark.get("dark_slope"), np.float32)
+            d.dark_dq = P(dark.get("dq"), np.uint32)
         rd = cal["read"]
-        d.read_noise = P(rd["data"], np.float32, c_float_p)
+        d.read_noise = P(rd["data"], np.float32)
         a33 = rd.get("amp33")
         if a33 is not None:
-            d.amp33_med = P(a33["med"], np.float32, c_float_p)
+            d.amp33_med = P(a33["med"], np.float32)
             d.refout_slope = float(refout_slope)
         d.gain = gain.ctypes.data
         d.gain_dtype = dtype_code(gain)
         lin = cal.get("linearitylegendre")
         if lin is not None:
             d.lin_nplanes = lin["data"].shape[0]
-            d.lin_coefs = P(lin["data"], np.float32, c_float_p)
-            d.lin_smin = P(lin["Smin"], np.float32, c_float_p)
-            d.lin_smax = P(lin["Smax"], np.float32, c_float_p)
-            d.lin_sref = P(lin["Sref"], np.float32, c_float_p)
-            d.lin_dq = P(lin["dq"], np.uint32, c_u32_p)
+            d.lin_coefs = P(lin["data"], np.float32)
+            d.lin_smin = P(lin["Smin"], np.float32)
+            d.lin_smax = P(lin["Smax"], np.float32)
+            d.lin_sref = P(lin["Sref"], np.float32)
+            d.lin_dq = P(lin["dq"], np.uint32)
         if cal.get("ipc4d") is not None:
-            k = _c(cal["ipc4d"]["data"])
-            if k.dtype not in (np.float32, np.float64):
-                k = k.astype(np.float64)
+            k = float_array(cal["ipc4d"]["data"])
             if k.shape != (3, 3, ny - 2 * nborder, nx - 2 * nborder):
                 raise ValueError(f"ipc4d shape {k.shape} does not match frame {ny}x{nx} with border {nborder}")
-            keep.append(k)
             d.ipc4d = k.ctypes.data
             d.ipc_dtype = dtype_code(k)
         if cal.get("flat") is not None:
-            d.flat = P(cal["flat"]["data"], np.float32, c_float_p)
+            d.flat = P(cal["flat"]["data"], np.float32)
         if cal.get("biascorr") is not None:
             b = cal["biascorr"]["data"]
             d.ngrp_bias = b.shape[0]
-            d.biascorr = P(b, np.float32, c_float_p)
+            d.biascorr = P(b, np.float32)
         if cal.get("saturation") is not None:  # only needed for flag_saturation (device dq-init + saturation flagging)
-            d.saturation = P(cal["saturation"]["data"], np.float32, c_float_p)
-            if cal["saturation"].get("dq") is not None:
-                d.saturation_dq = P(cal["saturation"]["dq"], np.uint32, c_u32_p)
-        self.check(self.lib.rip_caldir_upload(self.h, int(slot), C.byref(d)))
+            d.saturation = P(cal["saturation"]["data"], np.float32)
+            d.saturation_dq = P(cal["saturation"].get("dq"), np.uint32)
+        self.call("rip_caldir_upload", slot, d)
         # what rip_chain_form_for asks about (Calibrator.chain_form_for)
         self.caldir_dtypes[int(slot)] = (int(d.lin_nplanes), int(d.ipc_dtype), int(d.gain_dtype))
         return (ny, nx)
 
     def drop_caldir(self, slot):
-        self.check(self.lib.rip_caldir_drop(self.h, int(slot)))
+        self.call("rip_caldir_drop", slot)
         self.caldir_dtypes.pop(int(slot), None)
 
     # ---- plans -------------------------------------------------------------------------
     def create_plan(self, desc):
         pid = C.c_int(-1)
-        self.check(self.lib.rip_plan_create(self.h, C.byref(desc), C.byref(pid)))
+        self.call("rip_plan_create", desc, C.byref(pid))
         return pid.value
 
     def destroy_plan(self, pid):
-        self.check(self.lib.rip_plan_destroy(self.h, int(pid)))
+        self.call("rip_plan_destroy", pid)
 
     # ---- the chain ---------------------------------------------------------------------
     def calibrate_raw(self, slot, plan, stages, ramp_desc, outputs):
-        self.check(self.lib.rip_calibrate(self.h, int(slot), int(plan), int(stages), C.byref(ramp_desc), C.byref(outputs)))
+        self.call("rip_calibrate", slot, plan, stages, ramp_desc, outputs)
 
 
 _default = {}

@@ -91,9 +91,8 @@ def derive_biascorr(dark_slope, dark_data, lin_data, smin, smax, reads, tframe=T
     out = _empty(shape, np.float32, dev, ctx)
     pred = _empty(shape, np.float32, dev, ctx) if want_pred else None
     t0 = _native.C.c_double(0.0)
-    ctx.check(ctx.lib.rip_cal_biascorr(ctx.h, ds.ctypes.data, dd.ctypes.data, dd.shape[0], ny, nx, nb, co.shape[0], co.ctypes.data,
-                                       lo.ctypes.data, hi.ctypes.data, r.ctypes.data, ngrp, float(tframe), int(bframe),
-                                       out.ctypes.data, None if pred is None else pred.ctypes.data, _native.C.byref(t0)))
+    ctx.call("rip_cal_biascorr", ds, dd, dd.shape[0], ny, nx, nb, co.shape[0], co, lo, hi, r, ngrp, tframe, bframe, out, pred,
+             _native.C.byref(t0))
     return (out, t0.value, pred) if want_pred else (out, t0.value)
 
 
@@ -113,8 +112,7 @@ def derive_pflat(pflat0, gain, N=6, order=2, g_ideal=pars.g_ideal, ctx=None):
         scale = np.float32(g_ideal) / sky.median(g, ctx=ctx)   # Python float / np.float32: a float32 division under numpy >= 2 (:34)
     dev = is_dev(p)
     data, dq = _empty((ny, nx), np.float32, dev, ctx), _empty((ny, nx), np.uint32, dev, ctx)
-    ctx.check(ctx.lib.rip_cal_pflat(ctx.h, p.ctypes.data, ny, nx, int(order), LPX.ctypes.data, LPY.ctypes.data, c.ctypes.data,
-                                    float(scale), data.ctypes.data, dq.ctypes.data))
+    ctx.call("rip_cal_pflat", p, ny, nx, order, LPX, LPY, c, scale, data, dq)
     return data, dq, coef
 
 
@@ -127,7 +125,7 @@ def derive_saturation(smax, sref, ctx=None):
     _sync(a, b)
     dev = is_dev(a) or is_dev(b)
     data, dq = _empty(a.shape, np.float32, dev, ctx), _empty(a.shape, np.uint32, dev, ctx)
-    ctx.check(ctx.lib.rip_cal_saturation(ctx.h, a.ctypes.data, b.ctypes.data, a.shape[0], a.shape[1], data.ctypes.data, dq.ctypes.data))
+    ctx.call("rip_cal_saturation", a, b, a.shape[0], a.shape[1], data, dq)
     return data, dq
 
 
@@ -143,8 +141,7 @@ def derive_mask(lin_dq, pflat0, dark_slope, gain_dq, nb=NBORDER, ctx=None):
     ny, nx = p.shape
     med = sky.median(p, ctx=ctx)
     dq = _empty((ny, nx), np.uint32, any(is_dev(a) for a in (l, g, p, d)), ctx)
-    ctx.check(ctx.lib.rip_cal_mask(ctx.h, ny, nx, int(nb), l.ctypes.data, p.ctypes.data, float(med), d.ctypes.data, g.ctypes.data,
-                                   dq.ctypes.data))
+    ctx.call("rip_cal_mask", ny, nx, nb, l, p, med, d, g, dq)
     return dq
 
 SUMMARY_COLS = {"X": 0, "Y": 1, "N": 2, "g": 5, "aH": 6, "aV": 7, "aD": 10}   # solid-waffle output columns (make_gain_file.py:21)
@@ -204,10 +201,8 @@ def derive_gain_ipc4d(means, good, shape=(pars.nside, pars.nside), nb=NBORDER, i
              "kernel_dq": (active, np.uint32)}
     # a dtype the library has no code for is refused there, by name, like the other arguments: nothing is allocated for it
     out = {o: _empty(*specs[o], on_device, ctx) if o in outputs and code >= 0 and min(ny, nx) > 0 else None for o in GAIN_OUTPUTS}
-    p = {o: None if a is None else a.ctypes.data for o, a in out.items()}
-    ctx.check(ctx.lib.rip_cal_gain_ipc4d(ctx.h, t.ctypes.data, gd.ctypes.data, nsy, nsx, ny, nx, nb,
-                                         _native.RIP_DEVICE if on_device else _native.RIP_HOST, p["gain"], p["gain_dq"], p["kernel"],
-                                         code, p["kernel_dq"]))
+    ctx.call("rip_cal_gain_ipc4d", t, gd, nsy, nsx, ny, nx, nb, _native.RIP_DEVICE if on_device else _native.RIP_HOST,
+             out["gain"], out["gain_dq"], out["kernel"], code, out["kernel_dq"])
     return tuple(out[o] for o in GAIN_OUTPUTS)
 
 

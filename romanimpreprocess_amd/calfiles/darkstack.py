@@ -58,8 +58,8 @@ def sigma_clip_mean(stack, sigma=3, maxiters=5, want_count=False, *, sigma_lower
         s = np.ascontiguousarray(s)
         mean = np.empty(shape, np.float32)
         count = np.empty(shape, np.int32) if want_count else None
-    ctx.check(ctx.lib.rip_cal_sigma_clip_mean(ctx.h, s.ctypes.data, _native.RIP_DEVICE if dev else _native.RIP_HOST, n, npix, npix, lo, hi,
-                                              int(maxiters), mean.ctypes.data, None if count is None else count.ctypes.data))
+    ctx.call("rip_cal_sigma_clip_mean", s, _native.RIP_DEVICE if dev else _native.RIP_HOST, n, npix, npix, lo, hi, maxiters, mean,
+             count)
     return (mean, count) if want_count else mean
 
 
@@ -84,8 +84,7 @@ def derive_dark_planes(dark1, dark2, dark1_err, dark2_err, cds, nside=None, ctx=
     else:
         planes = [np.ascontiguousarray(a) for a in planes]
         out = [np.empty((ny, nx), np.float32) for _ in range(3)]
-    ctx.check(ctx.lib.rip_cal_dark_planes(ctx.h, *(a.ctypes.data for a in planes), _native.RIP_DEVICE if dev[0] else _native.RIP_HOST,
-                                          ny, nx, width, *(o.ctypes.data for o in out)))
+    ctx.call("rip_cal_dark_planes", *planes, _native.RIP_DEVICE if dev[0] else _native.RIP_HOST, ny, nx, width, *out)
     return tuple(out)
 
 
@@ -140,10 +139,10 @@ class DarkStack:
         elif not cube.flags.c_contiguous:
             cube = np.ascontiguousarray(cube)
         nreads, _, width = cube.shape
-        ctx = self.ctx
-        ctx.check(ctx.lib.rip_cal_group_means(ctx.h, cube.ctypes.data, _native.RIP_DEVICE if dev else _native.RIP_HOST, nreads, self.ny,
-                                              width, self.y0, self.y1 - self.y0, self.nx, self.reads.ctypes.data, self.ng,
-                                              int(bool(fits_be16)), self.stack.ctypes.data, self.capacity, self.n))
+        if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
+            cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
+        self.ctx.call("rip_cal_group_means", cube, _native.RIP_DEVICE if dev else _native.RIP_HOST, nreads, self.ny, width, self.y0,
+                      self.y1 - self.y0, self.nx, self.reads, self.ng, bool(fits_be16), self.stack, self.capacity, self.n)
         self.n += 1
 
     def finish(self, sigma=3, maxiters=5, want_count=False, *, sigma_lower=None, sigma_upper=None):
@@ -159,9 +158,8 @@ class DarkStack:
         lo = float(sigma if sigma_lower is None else sigma_lower)
         hi = float(sigma if sigma_upper is None else sigma_upper)
         for g in range(self.ng):
-            ctx.check(ctx.lib.rip_cal_sigma_clip_mean(ctx.h, self.stack.ctypes.data + 4 * g * self.capacity * npix, _native.RIP_DEVICE,
-                                                      self.n, npix, npix, lo, hi, int(maxiters), mean.ctypes.data + 4 * g * npix,
-                                                      None if count is None else count.ctypes.data + 4 * g * npix))
+            ctx.call("rip_cal_sigma_clip_mean", self.stack.t[g], _native.RIP_DEVICE, self.n, npix, npix, lo, hi, maxiters, mean.t[g],
+                     None if count is None else count.t[g])
         if not self._dev:
             mean, count = mean.numpy(), None if count is None else count.numpy()
         return (mean, count) if want_count else mean

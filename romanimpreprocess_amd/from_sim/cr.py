@@ -7,8 +7,6 @@ Within the model the arithmetic is exact given the deviates; the deviates come f
 ``L1Synth.cosmic_rays`` (``sim_to_isim``) is the device-tensor way in; the two functions here take and return numpy arrays.
 """
 
-import ctypes as C
-
 import numpy as np
 
 from .. import _native
@@ -57,9 +55,7 @@ def _tracks(ctx, par, nreads, read_time, n_i, n_j, seed, counts, capacity):
     offsets = torch.zeros((nreads + 1,), dtype=torch.int32, device=dev)
     cnt = None if counts is None else torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int32)).to(dev)
     torch.cuda.current_stream(dev).synchronize()   # torch's fills and copies are not on the context's stream
-    ctx.check(ctx.lib.rip_synth_cr_tracks(ctx.h, C.byref(par), nreads, float(read_time), int(n_i), int(n_j), seed,
-                                          None if cnt is None else cnt.data_ptr(), None, capacity, tracks.data_ptr(),
-                                          offsets.data_ptr()))
+    ctx.call("rip_synth_cr_tracks", par, nreads, read_time, n_i, n_j, seed, cnt, None, capacity, tracks, offsets)
     ctx.synchronize()
     return tracks, offsets
 
@@ -94,8 +90,7 @@ def simulate_crs(image, time, flux=8, area=16.8, conversion_factor=0.5, pixel_si
     added = torch.zeros((1, n_i, n_j), dtype=torch.int32, device=dev)
     first = torch.empty((n_i, n_j), dtype=torch.int32, device=dev)
     torch.cuda.current_stream(dev).synchronize()
-    ctx.check(ctx.lib.rip_synth_cr_deposit(ctx.h, C.byref(par), 1, n_i, n_j, tracks.data_ptr(), offsets.data_ptr(), 1, sd,
-                                           added.data_ptr(), first.data_ptr(), None))
+    ctx.call("rip_synth_cr_deposit", par, 1, n_i, n_j, tracks, offsets, 1, sd, added, first, None)
     ctx.synchronize()
     image += added[0].cpu().numpy().astype(image.dtype)
     return image

@@ -23,8 +23,6 @@ DESIGN.md section 7): romanisim is absent from the reference tree, parity with i
 Persistence (``romanisim.persistence``) is not modelled: passing ``persistence`` raises.
 """
 
-import ctypes as C
-
 import numpy as np
 
 from .. import _native, calio, dqflags, pars
@@ -85,9 +83,7 @@ class L1Synth:
         self.nreads = sum(len(g) for g in self.rp)
         self.t_reads = np.ascontiguousarray(np.concatenate(read_pattern_to_tij(self.rp, self.read_time)), dtype=np.float64)
         self.group_count = np.array([len(g) for g in self.rp], dtype=np.int32)
-        gain = np.ascontiguousarray(cal["gain"]["data"])
-        if gain.dtype not in (np.float32, np.float64):
-            gain = gain.astype(np.float64)
+        gain = _native.float_array(cal["gain"]["data"])
         self.ny, self.nx = gain.shape
         self.nb = nb
         self.nya, self.nxa = self.ny - 2 * nb, self.nx - 2 * nb
@@ -121,9 +117,7 @@ class L1Synth:
             d.lin_coefs, d.smin, d.smax = up(lin["data"], np.float32), up(lin["Smin"], np.float32), up(lin["Smax"], np.float32)
             self.lin_dq = np.array(lin["dq"], dtype=np.uint32)
         if cal.get("ipc4d") is not None:
-            k = np.ascontiguousarray(cal["ipc4d"]["data"])
-            if k.dtype not in (np.float32, np.float64):
-                k = k.astype(np.float64)
+            k = _native.float_array(cal["ipc4d"]["data"])
             if k.shape != (3, 3, self.nya, self.nxa):
                 raise ValueError(f"ipc4d shape {k.shape} does not match frame {self.ny}x{self.nx} with border {nb}")
             d.ipc4d, d.ipc_dtype = up(k), _native.dtype_code(k)
@@ -149,10 +143,6 @@ class L1Synth:
             return a
         return self.torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.dev)
 
-    @staticmethod
-    def _p(t):
-        return None if t is None else t.data_ptr()
-
     def apportion(self, counts, seed, poisson=False):
         """(nreads, nya, nxa) int32 tensor: electrons collected up to every read.  ``counts`` (nya, nxa) f32: integers, or with
         ``poisson`` the mean of a Poisson draw made first."""
@@ -161,8 +151,7 @@ class L1Synth:
         if tuple(c.shape) != (self.nya, self.nxa) or c.dtype != torch.float32:
             raise ValueError(f"counts must be float32 of shape {(self.nya, self.nxa)}")
         out = torch.empty((self.nreads, self.nya, self.nxa), dtype=torch.int32, device=self.dev)
-        self.ctx.check(self.ctx.lib.rip_synth_apportion(self.ctx.h, c.data_ptr(), self.nya, self.nxa, int(bool(poisson)), self.nreads,
-                                                        self.t_reads.ctypes.data, int(seed), out.data_ptr()))
+        self.ctx.call("rip_synth_apportion", c, self.nya, self.nxa, bool(poisson), self.nreads, self.t_reads, seed, out)
         self._hold = c
         return out
 
@@ -180,18 +169,15 @@ class L1Synth:
             out["cube"] = torch.empty((self.ngrp, self.ny, self.nx), dtype=torch.int16, device=self.dev)
         if want_start:
             out["start_e"] = torch.empty((self.nya, self.nxa), dtype=torch.float32, device=self.dev)
-        self.ctx.check(self.ctx.lib.rip_synth_resultants(
-            self.ctx.h, C.byref(self.desc), self.ngrp, self.group_count.ctypes.data, reads_e.data_ptr(), self._p(nr), self._p(nd),
-            int(seed), self._p(out.get("start_e")), self._p(out.get("resultants")), self._p(out.get("cube"))))
+        self.ctx.call("rip_synth_resultants", self.desc, self.ngrp, self.group_count, reads_e, nr, nd, seed, out.get("start_e"),
+                      out.get("resultants"), out.get("cube"))
         self._hold2 = (nr, nd, reads_e)
         return out
 
     def fill(self, cube, amp33, seed, banding=True, normals=None, frames=None, white33=None):
         """``fill_in_refdata_and_1f`` in place on ``cube`` (ngrp, ny, nx) and ``amp33`` (ngrp, ny, cw) int16 tensors (u16 bits)."""
         n, f, w = self._t(normals, np.float32), self._t(frames, np.float32), self._t(white33, np.float32)
-        self.ctx.check(self.ctx.lib.rip_synth_fill(self.ctx.h, C.byref(self.desc), self.ngrp, self.group_count.ctypes.data,
-                                                   int(bool(banding)), self._p(n), self._p(f), self._p(w), int(seed), cube.data_ptr(),
-                                                   self._p(amp33)))
+        self.ctx.call("rip_synth_fill", self.desc, self.ngrp, self.group_count, bool(banding), n, f, w, seed, cube, amp33)
         self._hold3 = (n, f, w)
 
     def cosmic_rays(self, reads_e, seed, crparam=None, tracks=None, poisson=True, want_lambda=False):
@@ -213,9 +199,8 @@ class L1Synth:
             cap = cr.capacity_for(par, self.nreads, self.read_time)
             out["tracks"] = torch.empty((cap, 6), dtype=torch.float64, device=self.dev)
             out["offsets"] = torch.empty((self.nreads + 1,), dtype=torch.int32, device=self.dev)
-            self.ctx.check(self.ctx.lib.rip_synth_cr_tracks(self.ctx.h, C.byref(par), self.nreads, self.read_time, self.nya, self.nxa,
-                                                            int(seed), None, None, cap, out["tracks"].data_ptr(),
-                                                            out["offsets"].data_ptr()))
+            self.ctx.call("rip_synth_cr_tracks", par, self.nreads, self.read_time, self.nya, self.nxa, seed, None, None, cap,
+                          out["tracks"], out["offsets"])
         else:
             t = np.ascontiguousarray(tracks.cpu().numpy() if torch.is_tensor(tracks) else tracks, dtype=np.float64).reshape(-1, 6)
             t = t[np.argsort(t[:, 0], kind="stable")]
@@ -225,10 +210,8 @@ class L1Synth:
             out["tracks"] = torch.from_numpy(np.concatenate([t, np.zeros((1, 6))])).to(self.dev)   # (never empty)
             out["offsets"] = torch.from_numpy(offsets).to(self.dev)
             torch.cuda.current_stream(self.dev).synchronize()   # torch's copies are not on the context's stream
-        self.ctx.check(self.ctx.lib.rip_synth_cr_deposit(self.ctx.h, C.byref(par), self.nreads, self.nya, self.nxa,
-                                                         out["tracks"].data_ptr(), out["offsets"].data_ptr(), int(bool(poisson)),
-                                                         int(seed), reads_e.data_ptr(), out["first_read"].data_ptr(),
-                                                         self._p(out.get("lam"))))
+        self.ctx.call("rip_synth_cr_deposit", par, self.nreads, self.nya, self.nxa, out["tracks"], out["offsets"], bool(poisson),
+                      seed, reads_e, out["first_read"], out.get("lam"))
         self._hold_cr = (out, reads_e)
         return out
 
@@ -248,8 +231,7 @@ class L1Synth:
         reads_e = self.apportion(counts, seed, poisson)
         if banding:   # the 1/f frames of this exposure's fill: on the second stream beside the resultants (f64 arithmetic), behind
             # the apportioning (bound by HBM like the transforms)
-            self.ctx.check(self.ctx.lib.rip_synth_frames_ahead(self.ctx.h, self.ny, self.cw, self.ngrp * (self.nx // self.cw + 2),
-                                                               int(seed)))
+            self.ctx.call("rip_synth_frames_ahead", self.ny, self.cw, self.ngrp * (self.nx // self.cw + 2), seed)
         self.last_first_read = None
         if crparam is not None:
             self.last_first_read = self.cosmic_rays(reads_e, seed, crparam)["first_read"]
@@ -263,8 +245,7 @@ class L1Synth:
     def extract_ref(self, data, offset=0):
         """``EXTRACT_REF`` on a device tensor (ngrp, ...) int16: (reference read, data[1:]) -- ``data`` is modified in place."""
         ref = self.torch.empty_like(data[0])
-        self.ctx.check(self.ctx.lib.rip_synth_extract_ref(self.ctx.h, data.data_ptr(), int(data.shape[0]), int(data[0].numel()),
-                                                          int(offset), ref.data_ptr()))
+        self.ctx.call("rip_synth_extract_ref", data, data.shape[0], data[0].numel(), offset, ref)
         return ref, data[1:]
 
 
@@ -300,7 +281,7 @@ def noise_1f_frame(rng, ctx=None):
     """One (4096, 128) f32 block of 1/f noise, unit variance per logarithmic frequency range."""
     ctx = ctx or _native.default_context()
     out = np.empty((pars.nside, pars.channelwidth), dtype=np.float32)
-    ctx.check(ctx.lib.rip_stage_noise_1f(ctx.h, pars.nside, pars.channelwidth, 1, None, _seed_of(rng), 0, out.ctypes.data))
+    ctx.call("rip_stage_noise_1f", pars.nside, pars.channelwidth, 1, None, _seed_of(rng), 0, out)
     return out
 
 

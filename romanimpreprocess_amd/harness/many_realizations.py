@@ -44,10 +44,9 @@ class SeedStacks:
         (``many_realizations.py:69-77``)."""
         c, ny, nx = self.ctx, self.ny, self.nx
         ngrp = cube.shape[0]
-        c.check(c.lib.rip_stats_l1_diff(c.h, cube.data_ptr(), ngrp, ny, nx, ngrp - 1, 1, self.diffs[k].data_ptr()))
-        c.check(c.lib.rip_stats_l2_pack(c.h, slope.data_ptr(), err_read.data_ptr(), err_poisson.data_ptr(), pixeldq.data_ptr(),
-                                        ny, nx, self.nb, self.grow.ctypes.data, self.images[k].data_ptr(),
-                                        self.err[k].data_ptr(), self.good[k].data_ptr()))
+        c.call("rip_stats_l1_diff", cube, ngrp, ny, nx, ngrp - 1, 1, self.diffs[k])
+        c.call("rip_stats_l2_pack", slope, err_read, err_poisson, pixeldq, ny, nx, self.nb, self.grow, self.images[k], self.err[k],
+               self.good[k])
 
 
 def reduce_rows(diffs, images, err, good, ideal_rows, y0, ny, nb=pars.nborder, reference_alias=True, ctx=None):
@@ -61,9 +60,7 @@ def reduce_rows(diffs, images, err, good, ideal_rows, y0, ny, nb=pars.nborder, r
         assert t.is_contiguous() and t.device == diffs.device
     out = torch.empty((NPLANES, nrows, nx), dtype=torch.float32, device=diffs.device)
     torch.cuda.synchronize(diffs.device)
-    ctx.check(ctx.lib.rip_stats_reduce(ctx.h, nseeds, diffs.data_ptr(), images.data_ptr(), err.data_ptr(), good.data_ptr(),
-                                       ideal_rows.data_ptr(), y0, nrows, ny, nx, nb, 1 if reference_alias else 0,
-                                       out.data_ptr()))
+    ctx.call("rip_stats_reduce", nseeds, diffs, images, err, good, ideal_rows, y0, nrows, ny, nx, nb, bool(reference_alias), out)
     ctx.synchronize()
     return out
 

@@ -62,10 +62,10 @@ class ResultPool:
 class Calibrator:
     def __init__(self, device=None, ctx=None):
         self.ctx = ctx if ctx is not None else _native.default_context(device)
-        # CALDIR slots and plans belong to the context: every Calibrator on it sees them
-        self.shapes = self.ctx.__dict__.setdefault("_caldir_shapes", {})
-        self._plans = self.ctx.__dict__.setdefault("_plan_cache", {})
-        self._results = self.ctx.__dict__.setdefault("_result_pool", ResultPool())
+        # CALDIR slots, plans and the pool of result arrays belong to the context: every Calibrator on it sees them
+        self.shapes = self.ctx.shapes
+        if self.ctx.result_pool is None:
+            self.ctx.result_pool = ResultPool()
 
     # ---- CALDIR ---------------------------------------------------------------------------
     def load_caldir(self, slot, cal, nborder=pars.nborder, owner=None):
@@ -73,14 +73,14 @@ class Calibrator:
         with the slot (``slot_owner``) so that a cache of file-based CALDIR sets can tell when its slot was reused."""
         rslope = planmod.refout_slope(cal["read"])
         self.shapes[slot] = self.ctx.upload_caldir(slot, cal, nborder=nborder, refout_slope=rslope)
-        self.ctx.__dict__.setdefault("_caldir_owner", {})[slot] = owner
+        self.ctx.caldir_owner[slot] = owner
         return self.shapes[slot]
 
     def drop_caldir(self, slot):
         """Free ``slot`` on the device and forget its frame shape and owner: a later call on it raises KeyError."""
         self.ctx.drop_caldir(slot)
         self.shapes.pop(slot, None)
-        self.ctx.__dict__.get("_caldir_owner", {}).pop(slot, None)
+        self.ctx.caldir_owner.pop(slot, None)
 
     def bias_state(self, slot):
         """``_native.BIAS_ABSENT`` / ``BIAS_PRESENT`` / ``BIAS_DROPPED`` for the CALDIR set of ``slot`` (``rip_caldir_bias_state``): a
@@ -88,7 +88,7 @@ class Calibrator:
         return self.ctx.caldir_bias_state(slot)
 
     def slot_owner(self, slot):
-        return self.ctx.__dict__.get("_caldir_owner", {}).get(slot)
+        return self.ctx.caldir_owner.get(slot)
 
     def chain_form_for(self, slot, ngroups):
         """2 where a ramp of ``ngroups`` groups on the CALDIR set of ``slot`` has a fused-kernel form (Legendre order, ipc4d and
@@ -113,8 +113,8 @@ class Calibrator:
     def plan_for(self, read_pattern, frame_time, exclude_first=True, ramp_opt_pars=None, jump_pars=None):
         """(plan id, meta) for an MA table; cached per configuration."""
         key = (repr(read_pattern), float(frame_time), bool(exclude_first), repr(ramp_opt_pars), repr(jump_pars))
-        if key in self._plans:
-            return self._plans[key]
+        if key in self.ctx.plans:
+            return self.ctx.plans[key]
         meta = planmod.exposure_meta(read_pattern, frame_time)
         meta["nborder"] = pars.nborder
         meta["K"] = planmod.construct_weights(planmod.ramp_opt_u(ramp_opt_pars), meta, exclude_first)
@@ -122,7 +122,7 @@ class Calibrator:
             meta["jump_detect_pars"] = jump_pars
         desc = planmod.plan_desc(meta, meta["K"], exclude_first, list(read_pattern[0]) == [0], jump_pars)
         pid = self.ctx.create_plan(desc)
-        self._plans[key] = (pid, meta)
+        self.ctx.plans[key] = (pid, meta)
         return pid, meta
 
     # ---- host arrays in, host arrays out --------------------------------------------------
@@ -218,7 +218,7 @@ class Calibrator:
         def result(name, shape, dtype):
             a = None if given is None else given.get(name)
             if a is None:
-                return self._results.empty(shape, dtype)
+                return self.ctx.result_pool.empty(shape, dtype)
             if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
                 where = "out" if i is None else f"out[{i}]"
                 raise ValueError(f"{where}[{name!r}] must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
@@ -271,7 +271,7 @@ class Calibrator:
             keep.append(arrays)
             res["K"], res["meta"] = meta["K"], meta
             results.append(res)
-        self.ctx.check(self.ctx.lib.rip_calibrate_batch(self.ctx.h, int(slot), int(pid), int(STAGE_ALL), n, descs, outs))
+        self.ctx.call("rip_calibrate_batch", slot, pid, STAGE_ALL, n, descs, outs)
         del keep
         return results
 
@@ -315,11 +315,10 @@ class Calibrator:
 
         count = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", self.ctx.device))
         torch.cuda.current_stream(count.device).synchronize()   # torch's fill runs on torch's stream, the entry on the context's
-        self.ctx.check(self.ctx.lib.rip_stage_decode_reference_read(
-            self.ctx.h, data_ptr, int(ngrp), int(n), ref_ptr, int(offset), _native.RIP_DEVICE,
-            data_ptr if out_ptr is None else out_ptr, count.data_ptr()))
+        self.ctx.call("rip_stage_decode_reference_read", data_ptr, ngrp, n, ref_ptr, offset, _native.RIP_DEVICE,
+                      data_ptr if out_ptr is None else out_ptr, count)
         if not want_count:
-            self.ctx.__dict__["_refread_count"] = count   # the kernel adds to it: alive until the next call replaces it
+            self.ctx.refread_count = count   # the kernel adds to it: alive until the next call replaces it
             return None
         self.ctx.synchronize()
         return int(count.item())
@@ -333,7 +332,7 @@ class Calibrator:
         from .utils import coordutils
 
         key = (wcs.digest(), int(ny), int(nx), bool(device))
-        cache = self.ctx.__dict__.setdefault("_area_cache", {})
+        cache = self.ctx.area_cache
         if key in cache:
             cache[key] = cache.pop(key)   # most recently used last
             return cache[key]

@@ -183,11 +183,11 @@ def pixelarea_map(inwcs, ny, nx, scale=1.0, device=False, ctx=None):
         dev = torch.device("cuda", ctx.device)
         out = torch.empty((int(ny), int(nx)), dtype=torch.float64, device=dev)
         torch.cuda.current_stream(dev).synchronize()   # the library writes on its own stream
-        ctx.check(ctx.lib.rip_stage_pixel_area(ctx.h, d, int(ny), int(nx), float(scale), _native.RIP_DEVICE, out.data_ptr()))
+        ctx.call("rip_stage_pixel_area", d, ny, nx, scale, _native.RIP_DEVICE, out)
         ctx.synchronize()
         return out
     out = np.empty((int(ny), int(nx)), dtype=np.float64)
-    ctx.check(ctx.lib.rip_stage_pixel_area(ctx.h, d, int(ny), int(nx), float(scale), _native.RIP_HOST, out.ctypes.data))
+    ctx.call("rip_stage_pixel_area", d, ny, nx, scale, _native.RIP_HOST, out)
     return out
 
 

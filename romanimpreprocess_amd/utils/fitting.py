@@ -29,21 +29,17 @@ def ramp_fit(data, rdq, pdq, meta, caldir, mylog, exclude_first=True, ctx=None):
     if rdq.dtype != np.uint8 or pdq.dtype != np.uint32 or not rdq.flags.c_contiguous or not pdq.flags.c_contiguous:
         raise TypeError("rdq must be a C-contiguous uint8 cube and pdq a C-contiguous uint32 plane (updated in place)")
     with calio.open_tree(caldir["gain"]) as f:
-        gain = np.ascontiguousarray(f["roman"]["data"])
+        gain = _native.float_array(f["roman"]["data"])
     with calio.open_tree(caldir["read"]) as f:
         read = np.ascontiguousarray(f["roman"]["data"], dtype=np.float32)
-    if gain.dtype not in (np.float32, np.float64):
-        gain = gain.astype(np.float64)
     desc = planmod.plan_desc(meta, meta["K"], exclude_first, True, meta.get("jump_detect_pars"))
     pid = ctx.create_plan(desc)
     try:
         slope = np.empty((ny, nx), np.float32)
         er = np.empty((ny, nx), np.float32)
         ep = np.empty((ny, nx), np.float32)
-        ctx.check(ctx.lib.rip_stage_ramp_fit(
-            ctx.h, pid, data.ctypes.data, rdq.ctypes.data, pdq.ctypes.data, ny, nx, int(meta["nborder"]),
-            gain.ctypes.data, _native.dtype_code(gain), read.ctypes.data, slope.ctypes.data, er.ctypes.data,
-            ep.ctypes.data))
+        ctx.call("rip_stage_ramp_fit", pid, data, rdq, pdq, ny, nx, meta["nborder"], gain, _native.dtype_code(gain), read,
+                 slope, er, ep)
     finally:
         ctx.destroy_plan(pid)
     if mylog is not None:
@@ -75,11 +71,9 @@ def jump_detect(data, rdq, pdq, meta, caldir, mylog, exclude_first=True, truncat
         K[start] = -K[-1]
     sub = {"ngrp": g, "tbar": np.asarray(meta["tbar"])[:g], "tau": np.asarray(meta["tau"])[:g], "N": np.asarray(meta["N"])[:g]}
     with calio.open_tree(caldir["gain"]) as f:
-        gain = np.ascontiguousarray(f["roman"]["data"])
+        gain = _native.float_array(f["roman"]["data"])
     with calio.open_tree(caldir["read"]) as f:
         read = np.ascontiguousarray(f["roman"]["data"], dtype=np.float32)
-    if gain.dtype not in (np.float32, np.float64):
-        gain = gain.astype(np.float64)
     desc = planmod.plan_desc(sub, K, exclude_first, True, meta.get("jump_detect_pars"))
     pid = ctx.create_plan(desc)
     try:
@@ -88,9 +82,8 @@ def jump_detect(data, rdq, pdq, meta, caldir, mylog, exclude_first=True, truncat
         flags = np.ascontiguousarray(rdq[:g], dtype=np.uint8) if rdq.dtype == np.uint8 else (rdq[:g] & np.uint32(0xFF)).astype(np.uint8)
         slope, er, ep = (np.empty((ny, nx), np.float32) for _ in range(3))
         smap = np.zeros((2 * (g - start) - 3, ny, nx), np.float32)
-        ctx.check(ctx.lib.rip_stage_jump_detect(
-            ctx.h, pid, cube.ctypes.data, flags.ctypes.data, ny, nx, int(meta["nborder"]), gain.ctypes.data,
-            _native.dtype_code(gain), read.ctypes.data, slope.ctypes.data, er.ctypes.data, ep.ctypes.data, smap.ctypes.data))
+        ctx.call("rip_stage_jump_detect", pid, cube, flags, ny, nx, meta["nborder"], gain, _native.dtype_code(gain), read,
+                 slope, er, ep, smap)
         if rdq.dtype == np.uint8:
             rdq[:g] = flags
         else:

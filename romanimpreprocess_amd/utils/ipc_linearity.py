@@ -10,11 +10,7 @@ import numpy as np
 from .. import _native, calio
 
 
-def _float_array(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype not in (np.float32, np.float64):
-        a = a.astype(np.float64)
-    return a
+_float_array = _native.float_array
 
 
 def _ipc_image(reverse, order, image, kernel, gain, ctx):
@@ -27,10 +23,8 @@ def _ipc_image(reverse, order, image, kernel, gain, ctx):
     g = None if gain is None else _float_array(np.broadcast_to(gain, image.shape))
     t64 = any(a is not None and a.dtype == np.float64 for a in (image, kernel, g))
     out = np.empty((ny, nx), np.float64 if t64 else np.float32)
-    ctx.check(ctx.lib.rip_stage_ipc_image(
-        ctx.h, int(reverse), int(order), image.ctypes.data, _native.dtype_code(image), ny, nx, kernel.ctypes.data,
-        _native.dtype_code(kernel), None if g is None else g.ctypes.data, 0 if g is None else _native.dtype_code(g),
-        out.ctypes.data))
+    ctx.call("rip_stage_ipc_image", reverse, order, image, _native.dtype_code(image), ny, nx, kernel,
+             _native.dtype_code(kernel), g, 0 if g is None else _native.dtype_code(g), out)
     return out
 
 
@@ -66,9 +60,8 @@ def correct_cube(data, ipc_file, mylog, gain_file=None, ctx=None):
     if gain_file is not None:
         with calio.open_tree(gain_file) as G:
             g = _float_array(G["roman"]["data"])
-    ctx.check(ctx.lib.rip_stage_correct_cube(
-        ctx.h, data.ctypes.data, ngrp, ny, nx, nb, kernel.ctypes.data, _native.dtype_code(kernel),
-        None if g is None else g.ctypes.data, 0 if g is None else _native.dtype_code(g)))
+    ctx.call("rip_stage_correct_cube", data, ngrp, ny, nx, nb, kernel, _native.dtype_code(kernel), g,
+             0 if g is None else _native.dtype_code(g))
 
 
 def multilin(S, linearity_file, origin=(0, 0), do_not_flag_first=True, attempt_corr=None, ctx=None):
@@ -90,10 +83,8 @@ def multilin(S, linearity_file, origin=(0, 0), do_not_flag_first=True, attempt_c
         ac = np.ascontiguousarray(np.asarray(attempt_corr) != 0, dtype=np.uint8)
     phi = np.empty(S.shape, np.float32)
     dq = np.empty((dy, dx), np.uint32)
-    ctx.check(ctx.lib.rip_stage_multilin(
-        ctx.h, S.ctypes.data, ngrp, dy, dx, coefs.shape[0], coefs.ctypes.data, smin.ctypes.data, smax.ctypes.data,
-        sref.ctypes.data, dq0.ctypes.data, int(bool(do_not_flag_first)), None if ac is None else ac.ctypes.data,
-        phi.ctypes.data, dq.ctypes.data))
+    ctx.call("rip_stage_multilin", S, ngrp, dy, dx, coefs.shape[0], coefs, smin, smax, sref, dq0, bool(do_not_flag_first), ac,
+             phi, dq)
     return phi, dq
 
 
@@ -114,9 +105,7 @@ def linearity(S, linearity_file, origin=(0, 0), ctx=None):
     nodq = np.zeros((dy, dx), np.uint32)   # the cube entry substitutes S - Sref where the file's dq says so: not here
     phi = np.empty((1, dy, dx), np.float32)
     dq = np.empty((dy, dx), np.uint32)
-    ctx.check(ctx.lib.rip_stage_multilin(
-        ctx.h, S.ctypes.data, 1, dy, dx, coefs.shape[0], coefs.ctypes.data, smin.ctypes.data, smax.ctypes.data,
-        smin.ctypes.data, nodq.ctypes.data, 0, None, phi.ctypes.data, dq.ctypes.data))
+    ctx.call("rip_stage_multilin", S, 1, dy, dx, coefs.shape[0], coefs, smin, smax, smin, nodq, 0, None, phi, dq)
     return phi[0], dq0 | dq
 
 
@@ -137,9 +126,7 @@ def invlinearity(Slin, linearity_file, origin=(0, 0), ctx=None):
         raise ValueError(f"block {Slin.shape} at origin {origin} leaves the linearity file's frame")
     S = np.empty_like(Slin)
     ex = np.empty((dy, dx), np.uint8)
-    ctx.check(ctx.lib.rip_stage_invlinearity(ctx.h, Slin.ctypes.data, _native.dtype_code(Slin), dy, dx, coefs.shape[0],
-                                             coefs.ctypes.data, smin.ctypes.data, smax.ctypes.data, S.ctypes.data,
-                                             ex.ctypes.data))
+    ctx.call("rip_stage_invlinearity", Slin, _native.dtype_code(Slin), dy, dx, coefs.shape[0], coefs, smin, smax, S, ex)
     return S, ex.astype(bool)
 
 

@@ -26,7 +26,7 @@ class CombinedMask:
         dq = np.ascontiguousarray(dq, dtype=np.uint32)
         ny, nx = dq.shape
         out = np.empty((ny, nx), np.uint8)
-        ctx.check(ctx.lib.rip_stage_build_mask(ctx.h, dq.ctypes.data, ny, nx, self.array.ctypes.data, out.ctypes.data))
+        ctx.call("rip_stage_build_mask", dq, ny, nx, self.array, out)
         return out.astype(bool)
 
 

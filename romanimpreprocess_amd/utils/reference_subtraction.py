@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import _native
 
-ROW_MEDIANS_ONLY, ROW_SLOPE_F64, ROW_SLOPE_F32 = 0, 1, 2
+ROW_MEDIANS_ONLY, ROW_SLOPE_F64, ROW_SLOPE_F32 = _native.RIP_ROW_MEDIANS_ONLY, _native.RIP_ROW_SLOPE_F64, _native.RIP_ROW_SLOPE_F32
 
 
 def _check(image):
@@ -48,8 +48,7 @@ def row_medians(image, use_ref_channel=False, nside=None, science=True, ctx=None
     ref = np.empty(ny, np.float32)
     sci = np.empty(ny, np.float32) if science else None
     ctr = np.empty(1, np.float32)
-    ctx.check(ctx.lib.rip_stage_refpix_row(ctx.h, image.ctypes.data, ny, w, ns, int(bool(use_ref_channel)), ROW_MEDIANS_ONLY, 0.0,
-                                           ref.ctypes.data, None if sci is None else sci.ctypes.data, ctr.ctypes.data))
+    ctx.call("rip_stage_refpix_row", image, ny, w, ns, bool(use_ref_channel), ROW_MEDIANS_ONLY, 0.0, ref, sci, ctr)
     return ref, sci, ctr[0]
 
 
@@ -65,8 +64,7 @@ def ref_subtraction_row(image, use_ref_channel=False, slope=None, ctx=None, nsid
         ref, sci, _ctr = row_medians(image, use_ref_channel, ns, True, ctx)
         slope, _ = np.polyfit(ref, sci, 1)          # reference_subtraction.py:114, on float32 medians
     mode = ROW_SLOPE_F64 if _is_f64_scalar(slope) else ROW_SLOPE_F32
-    ctx.check(ctx.lib.rip_stage_refpix_row(ctx.h, image.ctypes.data, ny, w, ns, int(bool(use_ref_channel)), mode, float(slope),
-                                           None, None, None))
+    ctx.call("rip_stage_refpix_row", image, ny, w, ns, bool(use_ref_channel), mode, float(slope), None, None, None)
     return image
 
 
@@ -83,8 +81,7 @@ def ref_subtraction_channel(image, channel_start=0, channel_end=128, use_ref_cha
     ln = None if lines is None else np.ascontiguousarray(lines, dtype=np.float64)
     if ln is not None and ln.shape != (nchan, 2):
         raise ValueError(f"lines must be ({nchan}, 2)")
-    ctx.check(ctx.lib.rip_stage_refpix_channel(ctx.h, image.ctypes.data, ny, w, int(channel_start), int(channel_end), nchan,
-                                               None if ln is None else ln.ctypes.data, None))
+    ctx.call("rip_stage_refpix_channel", image, ny, w, channel_start, channel_end, nchan, ln, None)
     return image
 
 
@@ -108,7 +105,6 @@ def refpix_tables(data, dark, amp33, amp33_med, slope, form=-1, ctx=None):
     rowcorr = np.empty((G, ny), np.float64)
     lines = np.empty((G, nx // 128, 2), np.float64)
     status = ctypes.c_int(0)
-    ctx.check(ctx.lib.rip_stage_refpix_tables(ctx.h, data.ctypes.data, _native.dtype_code(data), dark.ctypes.data, amp33.ctypes.data,
-                                              med.ctypes.data, float(slope), G, ny, nx, int(form), rowcorr.ctypes.data,
-                                              lines.ctypes.data, ctypes.addressof(status)))
+    ctx.call("rip_stage_refpix_tables", data, _native.dtype_code(data), dark, amp33, med, slope, G, ny, nx, form, rowcorr, lines,
+             ctypes.byref(status))
     return rowcorr, lines, status.value

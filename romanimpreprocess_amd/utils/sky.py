@@ -27,8 +27,7 @@ def binkxk(arr, k, mask=None, ctx=None):
     ny, nx = a.shape
     m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
     out = np.empty((ny // k, nx // k), np.float32)
-    ctx.check(ctx.lib.rip_stage_bin_mean(ctx.h, a.ctypes.data, None if m is None else m.ctypes.data, ny, nx, int(k),
-                                         out.ctypes.data))
+    ctx.call("rip_stage_bin_mean", a, m, ny, nx, k, out)
     return out
 
 
@@ -37,14 +36,9 @@ def _select(ctx, a, y0, x0, ky, kx, nby, nbx, ranks):
     ny, nx = a.shape
     nblk = nby * nbx
     counts = np.zeros(nblk, np.int64)
-    if ranks is None:
-        ctx.check(ctx.lib.rip_stage_select_ranks(ctx.h, a.ctypes.data, ny, nx, y0, x0, ky, kx, nby, nbx, 0, None,
-                                                 counts.ctypes.data, None))
-        return counts, None
-    r = np.ascontiguousarray(ranks, dtype=np.int64).reshape(nblk, -1)
-    vals = np.empty(r.shape, np.float32)
-    ctx.check(ctx.lib.rip_stage_select_ranks(ctx.h, a.ctypes.data, ny, nx, y0, x0, ky, kx, nby, nbx, r.shape[1],
-                                             r.ctypes.data, counts.ctypes.data, vals.ctypes.data))
+    r = None if ranks is None else np.ascontiguousarray(ranks, dtype=np.int64).reshape(nblk, -1)
+    vals = None if r is None else np.empty(r.shape, np.float32)
+    ctx.call("rip_stage_select_ranks", a, ny, nx, y0, x0, ky, kx, nby, nbx, 0 if r is None else r.shape[1], r, counts, vals)
     return counts, vals
 
 
@@ -112,8 +106,7 @@ def smooth_mode(arr, pc=25.0, pksmooth=0.5, niter=3, ctx=None):
         inner = np.ascontiguousarray(grid[1:nodes - 1], dtype=np.float64)
         dens = np.zeros(nodes)
         got = np.zeros(nodes - 2, np.float64)
-        ctx.check(ctx.lib.rip_stage_gauss_hist(ctx.h, img.ctypes.data, img.size, inner.ctypes.data, nodes - 2,
-                                               float(pksmooth * sigma), got.ctypes.data))
+        ctx.call("rip_stage_gauss_hist", img, img.size, inner, nodes - 2, pksmooth * sigma, got)
         dens[1:nodes - 1] = got
         top = np.argmax(dens)
         slope_ = (dens[top + 1] - dens[top - 1]) / 2.0
@@ -152,9 +145,7 @@ def medfit(arr, N=8, order=2, subtract=False, ctx=None, want_model=True):
     x, LPX, LPY = medfit_tables(a, N, order, ctx)
     model = np.empty((ny, nx), np.float32) if want_model else None
     coef = np.ascontiguousarray(x, dtype=np.float64)
-    ctx.check(ctx.lib.rip_stage_legendre2d(ctx.h, a.ctypes.data if subtract else None, ny, nx, int(order), LPX.ctypes.data,
-                                           LPY.ctypes.data, coef.ctypes.data, int(bool(subtract)),
-                                           None if model is None else model.ctypes.data))
+    ctx.call("rip_stage_legendre2d", a if subtract else None, ny, nx, order, LPX, LPY, coef, bool(subtract), model)
     return x, model
 
 
@@ -215,5 +206,5 @@ def endslice(rdq, nborder, ctx=None):
     if G >= 128:
         raise ValueError("too many groups")
     out = np.empty((ny - 2 * nborder, nx - 2 * nborder), np.int8)
-    ctx.check(ctx.lib.rip_stage_endslice(ctx.h, r.ctypes.data, G, ny, nx, int(nborder), out.ctypes.data))
+    ctx.call("rip_stage_endslice", r, G, ny, nx, nborder, out)
     return out

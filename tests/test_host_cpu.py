@@ -27,30 +27,27 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_structs_match_the_header(tmp_path):
-    """sizeof/offsetof of the ABI structs as gcc sees them == the ctypes mirrors."""
+    """sizeof of every ABI struct, offsetof and sizeof of every field of it, as gcc sees them == the ctypes mirrors."""
     src = tmp_path / "abi.c"
-    fields = {
-        "rip_caldir_desc": ["ny", "dark_data", "refout_slope", "gain", "lin_coefs", "ipc4d", "flat", "biascorr", "saturation",
-                            "saturation_dq"],
-        "rip_plan_desc": ["ngrp", "tbar", "nreads", "K", "nvariants", "variant_coef", "sthresh_a", "ithresh_b"],
-        "rip_ramp_desc": ["location", "data", "data_dtype", "amp33", "area_factor", "channel_lines", "flag_saturation",
-                          "sat_skip_firstn", "sat_dilution", "inputs_ready", "ready_event", "or_first_group"],
-        "rip_outputs": ["location", "slope", "pixeldq", "groupdq", "cube"],
-        "rip_synth_cal": ["ny", "channelwidth", "amp33_valid", "gain", "dark", "smax", "ipc4d", "biascorr", "tbias", "amp33_std",
-                          "m_pink", "c_pink"],
-    }
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "romanhip.h")).read(), flags=re.S)
+    in_header = re.findall(r"typedef\s+struct\s*\w*\s*\{[^{}]*\}\s*(\w+)\s*;", hdr)   # the struct bodies hold no braces
+    mirror = _native.HEADER.structs
+    assert len(in_header) == 7 and set(in_header) == set(mirror), set(in_header) ^ set(mirror)
+    fields = {s: [f for f, _ in mirror[s]._fields_] for s in in_header}
+    assert fields["rip_ramp_desc"][-3:] == ["reference_read", "reference_amp33", "data_encoding_offset"]
     body = "".join(f'printf("{s} %zu\\n", sizeof({s}));\n' + "".join(
-        f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));\n' for f in fl) for s, fl in fields.items())
+        f'printf("{s}.{f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s} *)0)->{f}));\n' for f in fl) for s, fl in fields.items())
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "romanhip.h"\nint main(void){\n' + body + "return 0;}\n")
     exe = tmp_path / "abi"
     subprocess.check_call(["gcc", "-I", os.path.join(REPO, "include"), str(src), "-o", str(exe)])
-    got = dict(line.split() for line in subprocess.check_output([str(exe)], text=True).splitlines())
-    mirror = {"rip_caldir_desc": _native.CaldirDesc, "rip_plan_desc": _native.PlanDesc,
-              "rip_ramp_desc": _native.RampDesc, "rip_outputs": _native.Outputs, "rip_synth_cal": _native.SynthCal}
+    got = {k: [int(v) for v in rest] for k, *rest in map(str.split, subprocess.check_output([str(exe)], text=True).splitlines())}
+    assert mirror == {"rip_caldir_desc": _native.CaldirDesc, "rip_plan_desc": _native.PlanDesc, "rip_ramp_desc": _native.RampDesc,
+                      "rip_outputs": _native.Outputs, "rip_synth_cal": _native.SynthCal, "rip_cr_params": _native.CrParams,
+                      "rip_wcs_desc": _native.WcsDesc}
     for s, fl in fields.items():
-        assert int(got[s]) == C.sizeof(mirror[s]), s
+        assert got[s] == [C.sizeof(mirror[s])], s
         for f in fl:
-            assert int(got[f"{s}.{f}"]) == getattr(mirror[s], f).offset, f"{s}.{f}"
+            assert got[f"{s}.{f}"] == [getattr(mirror[s], f).offset, getattr(mirror[s], f).size], f"{s}.{f}"
 
 
 def test_no_gpu_means_loud_failure():
