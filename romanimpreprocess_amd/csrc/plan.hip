@@ -119,7 +119,10 @@ int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
         for (int k = 0; k < v0.ndiff; ++k) {
             const RipDiff &df = p->diffs[v0.diff_ofs + k];
             const int i = df.i, di = df.j - df.i, ps = 2 * (i / 2) + (di - 1), e = i & 1;
-            dn.valid |= 1u << (2 * ps + e);
+            // the mask holds the differences of up to 16 groups, the most a fused form fits (highest bit 28: i = 14, di = 1); a
+            // longer ramp (ps up to 63) keeps valid = 0, which is no form's mask (rip_full_valid_of is non-zero for every
+            // count), so no shift by 32 or more is ever formed
+            if (G <= 16) dn.valid |= 1u << (2 * ps + e);
             dn.kidx[2 * ps + e] = k;
             dn.pairs[ps].inv_dt[e] = df.inv_dt;
             dn.pairs[ps].A[e] = df.A;

@@ -56,9 +56,9 @@ def ipc_case(seed, gain_dtype, ipc_dtype, G=3):
     return {"cube": cube, "K": cal["ipc4d"]["data"], "gain": cal["gain"]["data"]}
 
 
-def rampfit_case(read_pattern, seed, exclude_first=True, gain_dtype=np.float32, cr_frac=0.03):
+def rampfit_case(read_pattern, seed, exclude_first=True, gain_dtype=np.float32, cr_frac=0.03, shape=SMALL):
     """A linearised, IPC-corrected-looking f32 cube + DQ arrays exercising every branch of ramp_fit."""
-    cal = small_cal(read_pattern, 3, seed, gain_dtype=gain_dtype)
+    cal = small_cal(read_pattern, 3, seed, gain_dtype=gain_dtype, shape=shape)
     ramp = synth.make_ramp(cal, read_pattern=read_pattern, seed=seed + 1, cr_frac=cr_frac,
                            exclude_first=exclude_first)
     G, ny, nx = ramp["data"].shape
