@@ -279,7 +279,10 @@ int rip_stage_refpix_image(rip_ctx *ctx, float *image, int ny, int nx, double sl
      RIP_ROW_SLOPE_F64     image = f32(f64(image) - slope * f64(f32(ref_med - ctr)))   (slope a numpy f64 scalar, :123)
      RIP_ROW_SLOPE_F32     image = image - f32(slope) * (ref_med - ctr), every operation f32 (slope a Python float or a numpy
                            f32 scalar, as np.polyfit returns it for f32 medians: numpy's promotion rules)
-   ref_med, sci_med (ny) f32 and ctr (1) f32 out, each may be NULL (sci_med costs a 4088-value selection per row). */
+   ref_med, sci_med (ny) f32 and ctr (1) f32 out, each may be NULL (sci_med costs a 4088-value selection per row).
+   Every median is np.median's: NaN where a value is NaN (one NaN in a reference pixel makes ctr, and so the image, NaN), never
+   -0.  Limits (RIP_EINVAL beyond them): 16 <= nside <= 32776 and 1 <= ny <= 32768 -- a median is one sort of at most 32768
+   values in 128 KiB of LDS, which gfx950 grants a workgroup. */
 enum { RIP_ROW_MEDIANS_ONLY = 0, RIP_ROW_SLOPE_F64 = 1, RIP_ROW_SLOPE_F32 = 2 };
 int rip_stage_refpix_row(rip_ctx *ctx, float *image, int ny, int width, int nside, int use_ref_channel, int mode, double slope,
                          float *ref_med, float *sci_med, float *ctr);
@@ -288,7 +291,9 @@ int rip_stage_refpix_row(rip_ctx *ctx, float *image, int ny, int width, int nsid
    [channel_start + 128 k, channel_end + 128 k), k = 0 .. nchan-1 (32, or 33 with use_ref_channel), handled one after the
    other as the reference's loop does (windows wider than 128 columns overlap and see each other's updates); per window
    the medians of rows 0:4 and ny-4:ny, the line through (1.5, b), (ny-2.5, t) -- or lines (nchan,2) f64 (m,c) from the
-   caller's LAPACK -- subtracted from every row.  bottom_top (nchan,2) f32 out or NULL. */
+   caller's LAPACK -- subtracted from every row.  bottom_top (nchan,2) f32 out or NULL.  Medians as above (a NaN in a bottom
+   or top reference row makes its window NaN).  Limits (RIP_EINVAL beyond them): ny >= 8, 1 <= channel_end - channel_start
+   <= 8192 (4 x 8192 values a median), every window inside the image. */
 int rip_stage_refpix_channel(rip_ctx *ctx, float *image, int ny, int width, int channel_start, int channel_end, int nchan,
                              const double *lines, float *bottom_top);
 

@@ -75,13 +75,14 @@ def channel_line(bottom_med, top_med, nrows):
     return m_cor, c_cor
 
 
-def channel_step(image, nside, use_ref_channel, channel_start=0, channel_end=CHANNEL_WIDTH):
+def channel_step(image, nside, use_ref_channel, channel_start=0, channel_end=CHANNEL_WIDTH, n_channels=None):
     """Channel-wise correction, in place (``reference_subtraction.py:44-74``): windows of columns
-    ``[channel_start + 128 k, channel_end + 128 k)``, one after the other.
+    ``[channel_start + 128 k, channel_end + 128 k)``, one after the other.  ``n_channels``: the number of science windows
+    (default ``nside // 128``; the reference hard-codes 32), one more with ``use_ref_channel``.
 
     Returns (image, table) with table[ch] = (bottom_med, top_med, m, c).
     """
-    nch = nside // CHANNEL_WIDTH + (1 if use_ref_channel else 0)
+    nch = (nside // CHANNEL_WIDTH if n_channels is None else int(n_channels)) + (1 if use_ref_channel else 0)
     nrows = image.shape[0]
     rows = np.arange(nrows, dtype=np.float64)
     table = np.zeros((nch, 4), dtype=np.float64)

@@ -24,9 +24,16 @@
 // np.median of vals[0..n) in LDS by an in-place bitonic sort; the buffer must hold npow2 >= n floats
 // (entries n.. are overwritten with +inf).  All threads of the block must call it.  The median of the image drop-ins; the
 // pre-pass's rowcorr_kernel takes block_median_select, whose key order can pick the other of two tied -0 / +0.
+// As np.median forms it: NaN where any of the n values is NaN (the network's `x > y` would sort past one); the middle element
+// of an odd count as it is (not (v + v) / 2, which overflows above FLT_MAX / 2); the mean of the two middle elements of an even
+// count; and never -0 -- numpy's mean adds to +0, so a median of -0 comes out +0 (the `+ 0.0f`, kept by -ffp-contract=off
+// without fast-math).
 __device__ float block_median_sorted(float *vals, int n, int npow2) {
     for (int i = n + threadIdx.x; i < npow2; i += blockDim.x) vals[i] = INFINITY;
     __syncthreads();
+    int nan = 0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) nan |= vals[i] != vals[i];
+    nan = __syncthreads_or(nan);
     for (int k = 2; k <= npow2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = threadIdx.x; i < npow2; i += blockDim.x) {
@@ -42,8 +49,9 @@ __device__ float block_median_sorted(float *vals, int n, int npow2) {
             }
             __syncthreads();
         }
-    const int k_hi = n / 2, k_lo = (n & 1) ? n / 2 : n / 2 - 1;
-    return (vals[k_lo] + vals[k_hi]) * 0.5f;
+    const int k_hi = n / 2;
+    const float mid = (n & 1) ? vals[k_hi] : (vals[k_hi - 1] + vals[k_hi]) * 0.5f;
+    return nan ? NAN : mid + 0.0f;
 }
 
 // ---- 1. per (group,row): rank-63 / rank-64 elements of v = f32(amp33) - med -----------------------
