@@ -642,6 +642,21 @@ int rip_synth_extract_ref(rip_ctx *ctx, uint16_t *data, int ngrp, size_t n, int 
 int rip_stage_decode_reference_read(rip_ctx *ctx, const uint16_t *data, int ngrp, size_t n, const uint16_t *reference_read,
                                     int offset, int location, uint16_t *out, uint64_t *n_out_of_range);
 
+/* A FITS data unit from native samples (what astropy's writeto does to the arrays of gen_cal_image.py:725-736, gen_noise_image.py:
+   387-391, maskhandling.py:145-149): src holds n little-endian samples of |bitpix| / 8 bytes, bitpix one of 8, 16, 32, -32, -64;
+   dst receives n * |bitpix| / 8 bytes in FITS storage order, the bytes of each sample reversed.  flip_sign != 0 (bitpix 8, 16, 32
+   only) also inverts the most significant bit of each sample: the BZERO convention of uint16 (BZERO 32768), uint32 (2147483648)
+   and int8 (-128).  mask (NULL, or with bitpix -32 one byte per sample, living where src lives): sample i is replaced by `fill`
+   where (mask[i] != 0) == (mask_sense != 0), before the reversal -- where(mask, fill, data) with sense 1, where(good, data, fill)
+   with sense 0.  src_location and dst_location are independent (RIP_HOST / RIP_DEVICE): a host side goes through a scoped
+   device buffer and the call is complete on return; with both on the device it is asynchronous on rip_stream().  dst may equal
+   src (in place, same location).
+   RIP_EINVAL, before anything is copied or launched: an unknown bitpix, flip_sign with a float bitpix, mask with a bitpix other
+   than -32, n == 0, NULL src or dst, an unknown location, dst overlapping src without being equal to it, dst overlapping mask,
+   a DEVICE pointer that is not aligned to the sample (device memory is used where it is).  Exact. */
+int rip_stage_fits_encode(rip_ctx *ctx, const void *src, int bitpix, int flip_sign, size_t n, int src_location,
+                          const uint8_t *mask, int mask_sense, float fill, void *dst, int dst_location);
+
 /* Cosmic-ray hits (the model of romanisim's cr module, restated in DESIGN.md 7: romanisim is absent from the reference tree, so
    parity is unpinned and every constant is a parameter).  Defaults in brackets. */
 typedef struct rip_cr_params {

@@ -19,7 +19,9 @@ What runs where
     full frame, border included, as the reference's ``N=np.shape(slope)[-1]``.  The repository's own ``AREAFACTOR`` key (a
     file with an (N,N) f64 array) takes precedence when both are given; with neither, AreaFactor = 1;
   * not done here (outside the hot path): the gwcs object of the L2 tree (:660), dark decay, WFI18 transient,
-    romancal likelihood ramp fit, FITS output.  Asking for one of those raises NotImplementedError.
+    romancal likelihood ramp fit.  Asking for one of those raises NotImplementedError;
+  * ``FITSOUT`` (:725-736): the three-HDU ``_asdf_to.fits`` beside the L2 file, through ``calio.write_fits`` -- the data units are
+    put into FITS byte order, and the masked image is made, on the device (``rip_stage_fits_encode``).
 """
 
 import sys
@@ -27,6 +29,7 @@ import sys
 import numpy as np
 
 from .. import calio, pars, pipeline, plan as planmod
+from ..devarray import to_device
 from ..dqflags import group
 from ..utils import coordutils, flatutils, maskhandling, processlog, sky
 
@@ -136,8 +139,6 @@ def calibrateimage(config, verbose=True, calibrator=None):
     for unsupported in ("romancal_ramp_fit", "correct_wfi18_transient"):
         if config.get(unsupported):
             raise NotImplementedError(f"{unsupported} is outside the GPU L1->L2 path of this package")
-    if config.get("FITSOUT"):
-        raise NotImplementedError("FITSOUT needs astropy, which this package does not depend on")
     mylog = processlog.ProcessLog()
     caldir = config["CALDIR"]
     if "dark_decay" in caldir:
@@ -242,6 +243,13 @@ def calibrateimage(config, verbose=True, calibrator=None):
     if config.get("OUT") is None:   # in-memory use (the noise-layer driver): the L2 tree instead of a file
         return {"roman": im2, "processinfo": processinfo}
     calio.write_asdf(config["OUT"], {"roman": im2, "processinfo": processinfo})
+    if config.get("FITSOUT"):
+        # the image, its flags and the image with -1000 outside the grown mask of the ACTIVE-region flags (gen_cal_image.py:
+        # 725-736; saturated pixels are accepted there too): mask and substitution on the device
+        bad = maskhandling.PixelMask1.build_device(im2["dq"], ctx=cb.ctx)
+        calio.write_fits(config["OUT"][:-5] + "_asdf_to.fits",
+                         [{"data": im2["data"]}, {"data": im2["dq"]},
+                          {"data": to_device(im2["data"], cb.ctx.device), "mask": bad, "mask_sense": 1, "fill": -1000.0}], ctx=cb.ctx)
     return
 
 

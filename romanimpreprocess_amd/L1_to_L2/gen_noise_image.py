@@ -498,7 +498,8 @@ def generate_all_noise(config):
             raise ValueError("Unsupported noise precision.")
     calio.write_asdf(config["NOISE"]["OUT"], {"config": config, "noise": noiseimage})
     if config.get("FITSOUT", False):
-        raise NotImplementedError("FITS output needs astropy")
+        # FITS has no float16: such a cube is widened first (gen_noise_image.py:387-391); the byte order is made on the device
+        calio.write_fits(config["NOISE"]["OUT"][:-5] + "_asdf_to.fits", [np.ascontiguousarray(noiseimage, dtype=np.float32)])
 
 
 if __name__ == "__main__":

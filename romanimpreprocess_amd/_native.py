@@ -218,6 +218,7 @@ class Context:
         self.result_pool = None   # the pipeline.ResultPool of result arrays (made by the first Calibrator)
         self.area_cache = {}      # (WCS digest, ny, nx, on the device) -> pixel-area map, at most two
         self.refread_count = None   # the device word the last asynchronous decode_reference_read adds to: kept alive here
+        self.fits_staging = None    # the two page-locked chunk buffers of calio.write_fits, kept from call to call
 
     def close(self):
         if getattr(self, "h", None):

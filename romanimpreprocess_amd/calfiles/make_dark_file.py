@@ -9,8 +9,8 @@ file>`` with its ``001.fits`` counted up until a file is missing (500 at most), 
 ``dark_slope_err``; ``data``, ``resetnoise``, ``anc``, ``amp33`` with the script's placeholder where the summary has no ``AMP33``
 extension).  Every exposure is read ONCE (the script opens each once per group): its samples go to the device as stored and
 ``DarkStack`` keeps the group means of all exposures in HBM; where they do not fit, the frame is worked in row bands and the
-exposures are read once per band.  The ``_asdf_data.fits`` dumps of the script are NOT written: astropy is not a dependency of
-this package.  The clipped mean follows the rule of ``rip_cal_sigma_clip_mean``; parity with astropy is unpinned.
+exposures are read once per band.  The two ``_asdf_data.fits`` display dumps of the script are written too (``calio.write_fits``:
+an empty primary HDU and the planes of each tree, byte order made on the device).  The clipped mean follows the rule of ``rip_cal_sigma_clip_mean``; parity with astropy is unpinned.
 """
 
 import sys
@@ -122,10 +122,13 @@ def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, ba
         amp33 = {"valid": False, "med": np.zeros((4096, 128), dtype=np.float32), "std": np.zeros((4096, 128), dtype=np.float32),
                  "M_PINK": 0.0, "RU_PINK": 0.0}
 
+    dq = np.zeros((nside, nside), np.uint32)
     calio.write_asdf(outfile, {
-        "roman": {"meta": _meta(pattern, sca, ng, "DARK"), "data": darkave, "dq": np.zeros((nside, nside), np.uint32),
+        "roman": {"meta": _meta(pattern, sca, ng, "DARK"), "data": darkave, "dq": dq,
                   "dark_slope": dark_slope, "dark_slope_err": dark_slope_err},
         "notes": {"noise_header": header.text}})
+    # this stuff is just so that we can also display the images in ds9 (make_dark_file.py:143-151, 208-210)
+    calio.write_fits(outfile[:-5] + "_asdf_data.fits", [None, darkave, dq, dark_slope, dark_slope_err], ctx=ctx)
     head, tail = pathsplit(outfile)
     outfile2 = head + "/" + tail.replace("_dark_", "_read_")
     calio.write_asdf(outfile2, {
@@ -134,6 +137,7 @@ def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, ba
                   "anc": {"ACN": header["ACN"], "C_PINK": header["C_PINK"], "U_PINK": header["U_PINK"], "UNIT": "DN"},
                   "amp33": amp33},
         "notes": {"noise_header": header.text}})
+    calio.write_fits(outfile2[:-5] + "_asdf_data.fits", [None, read_noise, reset_noise], ctx=ctx)
     return outfile, outfile2
 
 

@@ -9,7 +9,8 @@ each behind a ``# <name>`` line; the ipc4d file's name is ``outfile``'s with ``_
 directory); the two trees have the script's layout and metadata keys (``reftype`` ``GAIN`` and ``IPC4D``) and the script's lines
 are printed.  The ipc4d flags are all zero, as the script's are.  ``ipc_dtype=np.float32`` writes the
 kernel rounded once to float32, which the fused chain reads in its faster form; float64 is what the script writes.
-The two ``_asdf_data.fits`` dumps of the script are NOT written: astropy is not a dependency of this package.
+The two ``_asdf_data.fits`` display dumps of the script are written too (``calio.write_fits``): the gain plane, and ipc4d laid out as
+a (3 ny, 3 nx) image by the script's transpose (made on the host: it is a display file), each behind an empty primary HDU.
 """
 
 import sys
@@ -74,9 +75,12 @@ def run(summaries, sca, outfile, *, ipc_dtype=np.float64, shape=None, ctx=None):
     gain, gain_dq, kernel, kernel_dq = derive_gain_ipc4d(means, good, shape=(ny, nx), nb=NBORDER, ipc_dtype=ipc_dtype, ctx=ctx)
     calio.write_asdf(outfile, {"roman": {"meta": _meta(sca, "GAIN"), "data": gain, "dq": gain_dq},
                                "notes": {"solid_waffle_config": config_lines}})
+    calio.write_fits(outfile[:-5] + "_asdf_data.fits", [None, gain], ctx=ctx)   # (make_gain_file.py:114-119)
     outfile2 = ipc4d_path(outfile)
     calio.write_asdf(outfile2, {"roman": {"meta": _meta(sca, "IPC4D"), "data": kernel, "dq": kernel_dq},
                                 "notes": {"solid_waffle_config": config_lines}})
+    tiled = np.ascontiguousarray(np.transpose(kernel, axes=(0, 2, 1, 3))).reshape(3 * kernel.shape[2], 3 * kernel.shape[3])
+    calio.write_fits(outfile2[:-5] + "_asdf_data.fits", [None, tiled], ctx=ctx)   # (make_gain_file.py:202-209)
     return outfile, outfile2
 
 

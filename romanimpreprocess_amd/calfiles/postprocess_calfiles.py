@@ -6,8 +6,8 @@
 Same conventions: the siblings and the outputs are found by replacing ``_linearitylegendre_`` in the file name,
 ``settings_<read pattern name>.yaml`` (``READS``) and ``linearity_pars_<sca>.json`` (``TFRAME``, ``BIAS/SLICE``) are read from the
 working directory, the three trees have the script's layout and metadata keys (``t0`` and ``t0_comment`` included) and the same
-lines are printed.  The script's last statements, which dump biascorr and the predicted dark to ``<biascorr>_asdf_to.fits``, are
-NOT mirrored: astropy is not a dependency of this package.
+lines are printed.  The script's last statements, which dump biascorr and the predicted dark as one (2 ngrp, ny, nx) float32 cube
+to ``<biascorr>_asdf_to.fits``, are mirrored through ``calio.write_fits``.
 """
 
 import json
@@ -90,6 +90,8 @@ def run(infile, sca, readpatternname=None, *, reads=None, lpars=None, ctx=None):
     calio.write_asdf(outfile_biascorr, {"roman": {
         "meta": _meta(sca, "BIASCORR"), "data": bias_corr, "t0": t0,
         "t0_comment": "number of seconds after reset used to define Sref, corresponding to 0 DN_lin"}})
+    # (postprocess_calfiles.py:169-172)
+    calio.write_fits(outfile_biascorr[:-5] + "_asdf_to.fits", [np.concatenate([bias_corr, pred]).astype(np.float32, copy=False)], ctx=ctx)
     return outfile_flat, outfile_sat, outfile_biascorr
 
 

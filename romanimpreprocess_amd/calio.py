@@ -11,7 +11,9 @@ same mapping for
 ``write_asdf`` writes such files (uncompressed blocks) so that synthetic CALDIR sets and L2 products
 can be exchanged with the reference tooling.  ``parse_fits_header`` reads the FITS header text of an exposure's WCS
 (``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy; ``read_fits_image`` maps the image of one HDU of a FITS file
-(the dark exposures and noise summaries of ``calfiles/make_dark_file.py``).
+(the dark exposures and noise summaries of ``calfiles/make_dark_file.py``).  ``fits_header`` and ``write_fits`` write image HDUs
+(the mask files, ``FITSOUT`` and the display dumps of the calibration-file scripts): the header on the host, the data units put
+into FITS storage order on the GPU (``rip_stage_fits_encode``).
 """
 
 import bz2
@@ -373,3 +375,171 @@ def read_fits_image(path, hdu=0):
             pos = start + (nbytes + _FITS_BLOCK - 1) // _FITS_BLOCK * _FITS_BLOCK
             index += 1
     raise KeyError(f"{path}: no HDU {hdu!r}")
+
+
+# ------------------------------------------------------------------------------- FITS output
+# numpy dtype name -> (BITPIX, BZERO or None).  A BZERO type is stored with its most significant bit inverted.
+_FITS_OUT = {"uint8": (8, None), "int8": (8, -128), "int16": (16, None), "uint16": (16, 32768), "int32": (32, None),
+             "uint32": (32, 2147483648), "float32": (-32, None), "float64": (-64, None)}
+
+
+def _fits_out_type(dtype):
+    dtype = np.dtype(dtype)
+    if dtype.name not in _FITS_OUT or not dtype.isnative:
+        order = "" if dtype.isnative else " in non-native byte order"
+        raise TypeError(f"FITS output: dtype {dtype.name}{order} is not supported ({', '.join(_FITS_OUT)}): cast the array first")
+    return _FITS_OUT[dtype.name]
+
+
+def _fits_card(key, value):
+    """one fixed-format card without a comment: logicals, integers and floats right-justified to column 30, strings quoted,
+    padded to eight characters, ``'`` doubled"""
+    key = str(key)
+    if not re.fullmatch(r"[A-Z0-9_-]{1,8}", key):
+        raise ValueError(f"FITS output: {key!r} is not a keyword (1 to 8 of A-Z, 0-9, _ and -)")
+    if isinstance(value, (bool, np.bool_)):
+        text = f"{'T' if value else 'F':>20}"
+    elif isinstance(value, (int, np.integer)):
+        text = f"{int(value):>20d}"
+    elif isinstance(value, (float, np.floating)):
+        if not np.isfinite(value):
+            raise ValueError(f"FITS output: {key} = {value!r} cannot be written as a number")
+        text = f"{float(value)!r:>20}"
+    elif isinstance(value, str):
+        if not value.isascii() or not value.isprintable():
+            raise ValueError(f"FITS output: the string of {key} is not printable ASCII")
+        text = "'" + value.replace("'", "''").ljust(8) + "'"
+    else:
+        raise TypeError(f"FITS output: {key} = {value!r} is not a logical, an integer, a float or a string")
+    card = f"{key:<8}= {text}"
+    if len(card) > 80:
+        raise ValueError(f"FITS output: the value of {key} does not fit into one card")
+    return card.ljust(80)
+
+
+def fits_header(shape, dtype, extension=False, extname=None, cards=()):
+    """The header of one image HDU as bytes, a multiple of 2880: fixed-format cards without comments, so that the bytes are
+    determined by the arguments -- SIMPLE (or XTENSION = 'IMAGE   '), BITPIX, NAXIS, NAXISn (NAXIS1 is the LAST numpy axis), EXTEND
+    (primary) or PCOUNT and GCOUNT (extension), BSCALE = 1 and BZERO for uint16 / uint32 / int8, EXTNAME, then ``cards`` ((keyword,
+    value) pairs: bool, int, float or str), END, blanks.  ``shape`` None: an HDU without data (BITPIX 8, NAXIS 0; ``dtype`` is not
+    looked at).  Supported dtypes: uint8, int8, int16, uint16, int32, uint32, float32, float64 in native byte order; anything else
+    (bool, float16, int64, ...) raises TypeError naming it -- the caller casts, as the reference's callers do.  Needs no GPU."""
+    if shape is None:
+        bitpix, bzero, shape = 8, None, ()
+    else:
+        bitpix, bzero = _fits_out_type(dtype)
+        shape = tuple(int(s) for s in shape)
+        if any(s < 0 for s in shape) or len(shape) > 999:
+            raise ValueError(f"FITS output: shape {shape}")
+    out = [_fits_card("XTENSION", "IMAGE") if extension else _fits_card("SIMPLE", True), _fits_card("BITPIX", bitpix),
+           _fits_card("NAXIS", len(shape))]
+    out += [_fits_card(f"NAXIS{i + 1}", s) for i, s in enumerate(shape[::-1])]
+    out += [_fits_card("PCOUNT", 0), _fits_card("GCOUNT", 1)] if extension else [_fits_card("EXTEND", True)]
+    if bzero is not None:
+        out += [_fits_card("BSCALE", 1), _fits_card("BZERO", bzero)]
+    if extname is not None:
+        out.append(_fits_card("EXTNAME", str(extname)))
+    out += [_fits_card(k, v) for k, v in cards]
+    out.append("END".ljust(80))
+    text = "".join(out)
+    return (text + " " * (-len(text) % _FITS_BLOCK)).encode("ascii")
+
+
+def _fits_unit(item, index):
+    """one entry of ``write_fits``'s list -> (header bytes, data or None, on the device, mask or None, sense, fill)"""
+    if item is None or hasattr(item, "dtype"):
+        item = {"data": item}
+    unknown = set(item) - {"data", "extname", "cards", "mask", "mask_sense", "fill"}
+    if unknown:
+        raise TypeError(f"write_fits: HDU {index}: unknown keys {sorted(unknown)}")
+    data, mask = item.get("data"), item.get("mask")
+    head = dict(extension=index > 0, extname=item.get("extname"), cards=item.get("cards", ()))
+    if data is None:
+        if mask is not None:
+            raise ValueError(f"write_fits: HDU {index} has a mask and no data")
+        return fits_header(None, None, **head), None, False, None, 0, 0.0
+    on_device = not isinstance(data, np.ndarray)
+    if not (hasattr(data, "ctypes") and hasattr(data, "shape")) or not data.flags.c_contiguous:
+        raise ValueError(f"write_fits: HDU {index}: data must be a C-contiguous numpy array or a DevArray")
+    header = fits_header(data.shape, data.dtype, **head)
+    if mask is not None:
+        if data.dtype != np.float32:
+            raise TypeError(f"write_fits: HDU {index}: a mask goes with float32 data, not {data.dtype.name}")
+        if (not isinstance(mask, np.ndarray)) != on_device:
+            raise ValueError(f"write_fits: HDU {index}: data and mask must both be numpy arrays or both DevArrays")
+        if mask.dtype not in (np.uint8, np.bool_) or tuple(mask.shape) != tuple(data.shape) or not mask.flags.c_contiguous:
+            raise ValueError(f"write_fits: HDU {index}: the mask must be a C-contiguous uint8 or bool array of the data's shape")
+    return header, data, on_device, mask, int(bool(item.get("mask_sense", 1))), float(item.get("fill", 0.0))
+
+
+def write_fits(path, hdus, ctx=None, chunk_bytes=64 << 20):
+    """Write a FITS file of image HDUs, replacing an existing one.  ``hdus``: a list whose entries are mappings with ``data``
+    (None: no data unit; a numpy array; a ``DevArray``) and optionally ``extname``, ``cards`` (see ``fits_header``) and, for
+    float32 data, ``mask`` (uint8 / bool, of the data's shape, living where the data live), ``mask_sense`` (default 1) and ``fill``:
+    the sample is written as ``fill`` where ``(mask != 0) == bool(mask_sense)``.  A bare array or None stands for ``{"data": ...}``.
+    The first entry is the primary HDU, the others are IMAGE extensions.
+
+    Every data unit is put into FITS storage order on the GPU (``rip_stage_fits_encode``; there is no host fallback) in chunks of
+    at most ``chunk_bytes``, each into one of two page-locked staging buffers; a writer thread puts chunk k into the file while
+    chunk k + 1 is encoded and downloaded.  An array is therefore never held a second time in host memory, and an array in HBM
+    comes to the host once, as the bytes of the file."""
+    import queue
+    import threading
+
+    from . import _native
+
+    units = [_fits_unit(item, i) for i, item in enumerate(hdus)]
+    if not units:
+        raise ValueError("write_fits: a FITS file has a primary HDU at least")
+    ctx = ctx or _native.default_context()
+    chunk = max(16, int(chunk_bytes) // 16 * 16)   # seams on 16-byte boundaries: the next chunk is as aligned as the array
+    need = min(chunk, max([u[1].size * u[1].dtype.itemsize for u in units if u[1] is not None] + [16]))
+    if ctx.fits_staging is None or ctx.fits_staging[0].nbytes < need:
+        ctx.fits_staging = None   # (the old pair is returned before the new one is taken)
+        ctx.fits_staging = [ctx.pinned_empty((need,), np.uint8) for _ in range(2)]
+    staging = ctx.fits_staging
+    todo, free, failed = queue.Queue(maxsize=4), queue.Queue(), []
+    free.put(0)
+    free.put(1)
+
+    def writer(f):
+        while True:
+            job = todo.get()
+            if job is None:
+                return
+            try:
+                if not failed:
+                    f.write(job if isinstance(job, bytes) else memoryview(staging[job[0]])[:job[1]])
+            except Exception as e:   # noqa: BLE001 (handed to the caller; the queue is drained so that nobody waits for ever)
+                failed.append(e)
+            if not isinstance(job, bytes):
+                free.put(job[0])
+
+    with open(path, "wb") as f:
+        thread = threading.Thread(target=writer, args=(f,), name="write_fits")
+        thread.start()
+        try:
+            for header, data, on_device, mask, sense, fill in units:
+                todo.put(header)
+                if data is None or data.size == 0:
+                    continue
+                if on_device:
+                    data.sync()
+                bitpix, bzero = _fits_out_type(data.dtype)
+                width = data.dtype.itemsize
+                where = _native.RIP_DEVICE if on_device else _native.RIP_HOST
+                step = chunk // width
+                for first in range(0, data.size, step):
+                    if failed:
+                        break
+                    n = min(step, data.size - first)
+                    slot = free.get()
+                    ctx.call("rip_stage_fits_encode", data.ctypes.data + first * width, bitpix, bzero is not None, n, where,
+                             None if mask is None else mask.ctypes.data + first, sense, fill, staging[slot], _native.RIP_HOST)
+                    todo.put((slot, n * width))
+                todo.put(b"\0" * (-(data.size * width) % _FITS_BLOCK))
+        finally:
+            todo.put(None)
+            thread.join()
+    if failed:
+        raise failed[0]

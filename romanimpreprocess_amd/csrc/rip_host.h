@@ -10,7 +10,8 @@
 //                                    _mask).  The noise-layer driver (L1_to_L2/gen_noise_image.py) hands them planes that live in HBM.
 //   host arrays OR device pointers,  the dark-file entries of darkstack.hip (rip_cal_group_means, _sigma_clip_mean, _dark_planes):
 //   told by a `location` argument    RIP_DEVICE arrays are used where they are -- the stack of group means is too large to copy;
-//                                    the OUTPUTS of rip_cal_gain_ipc4d (gainfile.hip), whose inputs are small host tables
+//                                    the OUTPUTS of rip_cal_gain_ipc4d (gainfile.hip), whose inputs are small host tables;
+//                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)

@@ -68,5 +68,19 @@ class DevArray:
         return a.view(self.dtype) if a.dtype != self.dtype else a
 
 
+def to_device(a, device=0):
+    """a numpy array as a ``DevArray`` on GPU ``device`` (one upload); unsigned 16- and 32-bit samples travel in signed tensors"""
+    import warnings
+
+    import torch
+
+    a = np.ascontiguousarray(a)
+    carrier = {"uint16": np.int16, "uint32": np.int32, "bool": np.uint8}.get(a.dtype.name)
+    with warnings.catch_warnings():   # a read-only array (a file's block) is only read from
+        warnings.simplefilter("ignore", UserWarning)
+        t = torch.from_numpy(a.view(carrier) if carrier is not None else a).to(torch.device("cuda", int(device)))
+    return DevArray(t, np.uint8 if a.dtype == np.bool_ else a.dtype).sync()
+
+
 def is_dev(a):
     return isinstance(a, DevArray)

@@ -1,9 +1,11 @@
 """Grown pixel masks on the GPU -- same call surface as the reference's ``utils/maskhandling.py`` (``CombinedMask``,
-``PixelMask1``).  ``build`` runs ``rip_stage_build_mask`` (bit-exact with the reference's per-bit convolutions)."""
+``PixelMask1``).  ``build`` runs ``rip_stage_build_mask`` (bit-exact with the reference's per-bit convolutions);
+``convert_file`` writes the mask file of an L2 file, the FITS form encoded on the device from the mask in HBM."""
 
 import numpy as np
 
-from .. import _native
+from .. import _native, calio
+from ..devarray import DevArray, to_device
 from ..dqflags import pixel
 
 
@@ -28,6 +30,36 @@ class CombinedMask:
         out = np.empty((ny, nx), np.uint8)
         ctx.call("rip_stage_build_mask", dq, ny, nx, self.array, out)
         return out.astype(bool)
+
+    def build_device(self, dq, ctx=None):
+        """``build`` with the result left in HBM: a uint8 ``DevArray`` of 0 / 1.  ``dq`` (2-D uint32, a numpy array) is uploaded."""
+        import torch
+
+        ctx = ctx or _native.default_context()
+        dq = np.ascontiguousarray(dq, dtype=np.uint32)
+        ny, nx = dq.shape
+        mask = DevArray(torch.empty((ny, nx), dtype=torch.uint8, device=torch.device("cuda", ctx.device))).sync()
+        ctx.call("rip_stage_build_mask", to_device(dq, ctx.device), ny, nx, self.array, mask)
+        return mask
+
+    def convert_file(self, file_in, file_mask, ctx=None):
+        """Make a mask file from an L2 file (``maskhandling.py:119-149``).  ``file_mask`` ending in ``.asdf``: ``{"mask": boolean
+        array}``; in ``.fits``: the image with -1000 in the masked pixels as float32 (primary HDU, for display) and the mask as
+        int8 0 / 1 (extension ``MASK``); any other ending writes nothing.  ``dq`` is uploaded once; for the FITS file the mask
+        stays in HBM and is handed to the encoder of the data units (``calio.write_fits``), it does not come to the host."""
+        kind = file_mask[-5:]
+        if kind not in (".asdf", ".fits"):
+            return
+        ctx = ctx or _native.default_context()
+        with calio.open_tree(file_in) as f_in:
+            dq = np.asarray(f_in["roman"]["dq"])
+            data = np.ascontiguousarray(f_in["roman"]["data"], dtype=np.float32) if kind == ".fits" else None
+        locmask = self.build_device(dq, ctx=ctx)
+        if kind == ".asdf":
+            calio.write_asdf(file_mask, {"mask": locmask.numpy().astype(bool)})
+            return
+        calio.write_fits(file_mask, [{"data": to_device(data, ctx.device), "mask": locmask, "mask_sense": 1, "fill": -1000.0},
+                                     {"data": DevArray(locmask.t, np.int8), "extname": "MASK"}], ctx=ctx)
 
 
 # the reference's standard choice (maskhandling.py:152-180)
