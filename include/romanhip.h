@@ -45,7 +45,7 @@ extern "C" {
 typedef struct rip_ctx rip_ctx;
 
 typedef enum { RIP_OK = 0, RIP_EINVAL = -1, RIP_ENOMEM = -2, RIP_EHIP = -3, RIP_ESTATE = -4 } rip_status;
-typedef enum { RIP_F32 = 0, RIP_F64 = 1, RIP_U16 = 2 } rip_dtype;
+typedef enum { RIP_F32 = 0, RIP_F64 = 1, RIP_U16 = 2, RIP_F16 = 3 } rip_dtype;
 typedef enum { RIP_HOST = 0, RIP_DEVICE = 1 } rip_location;
 /* rip_ramp_desc::inputs_ready: what the library may assume about DEVICE-resident inputs when rip_calibrate is called */
 typedef enum { RIP_INPUTS_STREAM_ORDERED = 0, RIP_INPUTS_COMPLETE = 1 } rip_inputs_ready;
@@ -656,6 +656,32 @@ int rip_stage_decode_reference_read(rip_ctx *ctx, const uint16_t *data, int ngrp
    a DEVICE pointer that is not aligned to the sample (device memory is used where it is).  Exact. */
 int rip_stage_fits_encode(rip_ctx *ctx, const void *src, int bitpix, int flip_sign, size_t n, int src_location,
                           const uint8_t *mask, int mask_sense, float fill, void *dst, int dst_location);
+
+/* The planes of the L2 tree from the chain's results (gen_cal_image.py:653-662 with romanisim's make_asdf, oututils.py:52-55,
+   typefix.py:38-56): slope, err_read, err_poisson f32 and pixeldq u32 are (ny,nx) frames; over the active region (ny-2nb,
+   nx-2nb)   data = slope,  dq = pixeldq,  var_rnoise = err_read * err_read,  var_poisson = err_poisson * err_poisson (f32
+   products),  err = sqrt(var_rnoise + var_poisson) (f32 sum, correctly rounded f32 square root).  var_dtype RIP_F32: the three
+   are stored as computed; RIP_F16: each f32 value is then rounded to nearest-even float16 (numpy's astype(float16): overflow to
+   infinity, float16 subnormals kept, NaN stays NaN).  The flag strips are full rows and columns of pixeldq, corners in both:
+   dq_left (ny,nb) = pixeldq[:, :nb], dq_right (ny,nb) = pixeldq[:, nx-nb:], dq_top (nb,nx) = pixeldq[ny-nb:, :], dq_bottom (nb,nx)
+   = pixeldq[:nb, :] (empty with nb = 0).  Any output may be NULL and is then not made.  `location` holds for every pointer:
+   RIP_HOST: through scoped device buffers, complete on return; RIP_DEVICE: asynchronous on rip_stream().
+   RIP_EINVAL, before anything is copied or launched: a NULL input, ny or nx < 1, nb < 0, 2 nb >= ny or 2 nb >= nx, a var_dtype
+   other than RIP_F32 / RIP_F16, an unknown location, a DEVICE pointer that is not aligned to its element, an output overlapping
+   an input.  Exact. */
+int rip_stage_l2_planes(rip_ctx *ctx, const float *slope, const float *err_read, const float *err_poisson, const uint32_t *pixeldq,
+                        int ny, int nx, int nb, int var_dtype, int location, float *data, uint32_t *dq, void *var_rnoise,
+                        void *var_poisson, void *err, uint32_t *dq_left, uint32_t *dq_right, uint32_t *dq_top, uint32_t *dq_bottom);
+
+/* The reference-pixel strips of a Level-1 cube (oututils.py:46-49): cube (ngrp,ny,nx) of cube_dtype RIP_U16 or RIP_F32; as f32
+   left (ngrp,ny,nb) = cube[:, :, :nb], right (ngrp,ny,nb) = cube[:, :, nx-nb:], top (ngrp,nb,nx) = cube[:, ny-nb:, :], bottom
+   (ngrp,nb,nx) = cube[:, :nb, :] (empty with nb = 0; f32 samples are moved as bits).  Any output may be NULL.  `location` as for
+   rip_stage_l2_planes.
+   RIP_EINVAL, before anything is copied or launched: a NULL cube, ngrp, ny or nx < 1, nb < 0, nb > ny or nb > nx, a cube_dtype
+   other than RIP_U16 / RIP_F32, an unknown location, a DEVICE pointer that is not aligned to its element, an output overlapping
+   the cube.  Exact. */
+int rip_stage_l2_refpix_strips(rip_ctx *ctx, const void *cube, int cube_dtype, int ngrp, int ny, int nx, int nb, int location,
+                               float *left, float *right, float *top, float *bottom);
 
 /* Cosmic-ray hits (the model of romanisim's cr module, restated in DESIGN.md 7: romanisim is absent from the reference tree, so
    parity is unpinned and every constant is a parameter).  Defaults in brackets. */

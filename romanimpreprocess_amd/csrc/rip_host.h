@@ -11,7 +11,8 @@
 //   host arrays OR device pointers,  the dark-file entries of darkstack.hip (rip_cal_group_means, _sigma_clip_mean, _dark_planes):
 //   told by a `location` argument    RIP_DEVICE arrays are used where they are -- the stack of group means is too large to copy;
 //                                    the OUTPUTS of rip_cal_gain_ipc4d (gainfile.hip), whose inputs are small host tables;
-//                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst
+//                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst;
+//                                    rip_stage_l2_planes, rip_stage_l2_refpix_strips (l2out.hip): one location for every pointer
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
@@ -22,7 +23,7 @@
 
 #define RIP_SHARED __attribute__((visibility("hidden")))   // shared between translation units, not part of the interface
 
-inline size_t dsize(int dtype) { return dtype == RIP_F64 ? 8 : (dtype == RIP_U16 ? 2 : 4); }
+inline size_t dsize(int dtype) { return dtype == RIP_F64 ? 8 : ((dtype == RIP_U16 || dtype == RIP_F16) ? 2 : 4); }
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 // Scoped device allocation of n elements of T for one call of an entry point (`who`: its name, for the error text).

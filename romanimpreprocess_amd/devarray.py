@@ -4,7 +4,7 @@ The stage-level entry points of ``libromanhip`` that the post-path and the noise
 ``rip_stage_legendre2d``, ``rip_stage_gauss_hist``, ``rip_stage_bin_mean``, ``rip_stage_build_mask``, ``rip_stage_endslice``,
 ``rip_stage_noise_inject``, ``rip_stage_poisson_resample``, ``rip_stage_pearson``) copy their array arguments with
 ``hipMemcpyDefault``: a pointer may be a host array or device memory (so may those of the calibration-file entries
-``rip_cal_*``, which take a ``location``).  ``Context.call`` takes a ``DevArray`` wherever it takes a numpy array and checks
+``rip_cal_*`` and of the L2-output entries ``rip_stage_l2_planes`` / ``rip_stage_l2_refpix_strips``, which take a ``location``).  ``Context.call`` takes a ``DevArray`` wherever it takes a numpy array and checks
 its ``dtype`` against the element type the header declares for the parameter.  ``DevArray`` wraps a torch tensor on the GPU so that the
 mirrors written for numpy arrays (``utils/sky.py``, ``L1_to_L2/gen_noise_image.py``) can be handed a plane that never leaves
 HBM: it offers what those functions ask of an array -- ``shape``, ``dtype`` (numpy's), ``ndim``, ``size``,
@@ -24,7 +24,7 @@ def _dtype_of(t):
         import torch
 
         _TORCH_TO_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int16: np.int16,
-                        torch.uint8: np.uint8, torch.int8: np.int8, torch.int64: np.int64}
+                        torch.uint8: np.uint8, torch.int8: np.int8, torch.int64: np.int64, torch.float16: np.float16}
     return np.dtype(_TORCH_TO_NP[t.dtype])
 
 

@@ -5,7 +5,7 @@
 import numpy as np
 
 from .. import _native, calio
-from ..devarray import DevArray, to_device
+from ..devarray import DevArray, is_dev, to_device
 from ..dqflags import pixel
 
 
@@ -32,14 +32,16 @@ class CombinedMask:
         return out.astype(bool)
 
     def build_device(self, dq, ctx=None):
-        """``build`` with the result left in HBM: a uint8 ``DevArray`` of 0 / 1.  ``dq`` (2-D uint32, a numpy array) is uploaded."""
+        """``build`` with the result left in HBM: a uint8 ``DevArray`` of 0 / 1.  ``dq`` (2-D uint32): a numpy array, which is
+        uploaded, or a ``DevArray``, used where it is."""
         import torch
 
         ctx = ctx or _native.default_context()
-        dq = np.ascontiguousarray(dq, dtype=np.uint32)
+        if not (is_dev(dq) and dq.dtype == np.uint32):
+            dq = to_device(np.ascontiguousarray(dq, dtype=np.uint32), ctx.device)
         ny, nx = dq.shape
         mask = DevArray(torch.empty((ny, nx), dtype=torch.uint8, device=torch.device("cuda", ctx.device))).sync()
-        ctx.call("rip_stage_build_mask", to_device(dq, ctx.device), ny, nx, self.array, mask)
+        ctx.call("rip_stage_build_mask", dq, ny, nx, self.array, mask)
         return mask
 
     def convert_file(self, file_in, file_mask, ctx=None):

@@ -25,7 +25,7 @@ def binkxk(arr, k, mask=None, ctx=None):
     ctx = ctx or _native.default_context()
     a = _f32(arr)
     ny, nx = a.shape
-    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+    m = mask if mask is None or (is_dev(mask) and mask.dtype == np.uint8) else np.ascontiguousarray(mask, dtype=np.uint8)
     out = np.empty((ny // k, nx // k), np.float32)
     ctx.call("rip_stage_bin_mean", a, m, ny, nx, k, out)
     return out
@@ -199,9 +199,10 @@ def medfit_tables(a, N, order, ctx):
 
 
 def endslice(rdq, nborder, ctx=None):
-    """SLICEOUT plane (``gen_cal_image.py:697-712``): int8 (ny-2nb, nx-2nb), index of the last unsaturated group - 1."""
+    """SLICEOUT plane (``gen_cal_image.py:697-712``): int8 (ny-2nb, nx-2nb), index of the last unsaturated group - 1.  ``rdq``
+    may be a uint8 ``DevArray``: the group flags then never leave HBM."""
     ctx = ctx or _native.default_context()
-    r = np.ascontiguousarray(rdq, dtype=np.uint8)
+    r = rdq if (is_dev(rdq) and rdq.dtype == np.uint8) else np.ascontiguousarray(rdq, dtype=np.uint8)
     G, ny, nx = r.shape
     if G >= 128:
         raise ValueError("too many groups")
