@@ -809,6 +809,39 @@ int rip_cal_dark_planes(rip_ctx *ctx, const float *dark1, const float *dark2, co
 int rip_cal_gain_ipc4d(rip_ctx *ctx, const double *means, const uint8_t *good, int nsy, int nsx, int ny, int nx, int nb, int location,
                        float *gain, uint32_t *gain_dq, void *kernel, int kernel_dtype, uint32_t *kernel_dq);
 
+/* ---- raw detector frames to exposure cubes ------------------------------------------------- */
+/* What runs/summer2025run/convert_dark.py, convert_flt.py and convert_loflt.py of the reference do between reading the
+   single-frame files of an exposure and writing its cube (line numbers: convert_flt.py).  Both entries return when their kernels
+   and copies are done.  Exact: bytes are moved, and the slope arithmetic has no rounding but the script's own two. */
+
+/* One frame into its plane of the cube (:53-63).  frame (ny,nx) 16-bit samples as `stored` says -- 0: native u16; 1: FITS
+   storage, big-endian int16 with BZERO 32768 (the unsigned sample: bytes swapped, top bit inverted); 2: FITS storage, big-endian
+   int16 without BZERO, its bits kept (numpy's cast to uint16 wraps) -- living where `location` says: RIP_HOST (it goes through a
+   scoped device buffer) or RIP_DEVICE (read where it is).  dst: ny * nx u16, ALWAYS a device pointer (plane k of a cube in HBM),
+   receives the decoded frame in the science frame: orient 0 as it is; 1 (sca % 3 == 0, :61) the columns 0 .. nflip-1 of every
+   row reversed, the columns nflip .. nx-1 (the reference output) in place; 2 (:63) the rows reversed, whole rows moving.
+   nflip is looked at with orient 1 only, and checked always.  With nx and nflip multiples of 8 and both pointers 16-byte aligned
+   a lane moves 8 samples; otherwise one.  The two forms give the same bytes.
+   RIP_EINVAL, before anything is launched or copied: ny or nx < 1, nflip outside 0..nx, an unknown orient, stored or location, a
+   NULL pointer, a device pointer that is not aligned to the 2-byte sample, dst overlapping frame. */
+int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny, int nx, int orient, int nflip, int stored,
+                      uint16_t *dst);
+
+/* The two unweighted slope images of a cube (:65-79; convert_dark.py:65-76 with nc = n).  cube (n,npix) u16, a DEVICE pointer;
+   the planes 1 .. nc-1 are read, each once.  w0[nc], w1[nc] HOST arrays of f64 weights and de0, de1 their denominators, formed by
+   the caller as the script forms them (w0[k] = k - nc / 2.0 for k = 1 .. nc-1, w1[k] = k - (nc / 2) / 2.0 for k = 1 .. nc/2 - 1,
+   de the running sum of their squares in k order); w0[0] and w1[k] outside 1 .. nc/2 - 1 are not read.  slp (2,npix) f32, where
+   out_location says (RIP_HOST: through a scoped device buffer):
+     slp[0][p] = f32((sum over k = 1 .. nc-1   of f64(cube[k][p]) * w0[k]) / de0)
+     slp[1][p] = f32((sum over k = 1 .. nc/2-1 of f64(cube[k][p]) * w1[k]) / de1)
+   Every product and partial sum is a multiple of 0.5 far below 2^53: the numerators are exact in any order and start at +0.0;
+   the only roundings are the f64 division and the conversion to f32, so the result is numpy's in every bit.  A denominator of
+   zero meets a numerator of zero (nc 1, 2: both images; nc 3, 4, 5: the second): 0 / 0 = NaN, never an infinity.
+   RIP_EINVAL, before anything is launched or copied: n or npix < 1, nc outside 1..n, a NULL pointer, an unknown out_location, a
+   device pointer that is not aligned to its sample, slp overlapping the cube. */
+int rip_cal_frame_slopes(rip_ctx *ctx, const uint16_t *cube, int n, int nc, size_t npix, const double *w0, double de0, const double *w1,
+                         double de1, float *slp, int out_location);
+
 #ifdef __cplusplus
 }
 #endif

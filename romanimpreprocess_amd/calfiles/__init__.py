@@ -4,7 +4,9 @@ GPU (``csrc/calfiles.hip``).  The array-level functions below take numpy arrays 
 HBM as ``DevArray`` too) and reproduce the scripts' numpy arithmetic bit for bit (numpy >= 2 promotion rules, float32 planes);
 ``postprocess_calfiles.run`` and ``makemask.run`` are the scripts' file-level drop-ins.  The step in front of them, the ``dark`` and
 ``read`` files of ``make_dark_file.py``, is ``darkstack.py`` (``DarkStack``, ``sigma_clip_mean``, ``derive_dark_planes``) and the
-drop-in ``make_dark_file.run``.  The ``gain`` and ``ipc4d`` files that all of them read come from ``summary_means`` (numpy, on
+drop-in ``make_dark_file.run``; in front of that, the exposure cubes and slope images that the three converters of
+``runs/summer2025run`` make of the raw test-stand frames are ``convert_frames.py`` (``frames_to_cube``, ``cube_slopes``, ``convert``,
+``csrc/rawframes.hip``) with the drop-ins ``convert_dark``, ``convert_flt`` and ``convert_loflt``.  The ``gain`` and ``ipc4d`` files that all of them read come from ``summary_means`` (numpy, on
 the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hip``), with the drop-in ``make_gain_file.run``.
 """
 
@@ -207,3 +209,4 @@ def derive_gain_ipc4d(means, good, shape=(pars.nside, pars.nside), nb=NBORDER, i
 
 
 from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E402, F401
+from .convert_frames import convert, cube_slopes, find_frames, frames_to_cube  # noqa: E402, F401

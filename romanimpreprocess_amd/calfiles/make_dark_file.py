@@ -22,6 +22,7 @@ import numpy as np
 import yaml
 
 from .. import _native, calio
+from ..devarray import DevArray, is_dev
 from .darkstack import DarkStack, derive_dark_planes
 
 NSIDE = 4096   # dimension of H4RG (make_dark_file.py:26)
@@ -54,26 +55,46 @@ def noise_files(target):
     return out
 
 
-def _open_dark(path):
-    hdr, data = calio.read_fits_image(path, 0)
+LAYOUTS = ("2026_July", "summer2025")
+
+
+def _open_dark(path, layout="2026_July"):
+    """the (nreads, ny, width) samples of one dark exposure as stored.  ``2026_July``: the primary HDU; ``summer2025``
+    (``runs/summer2025run/make_dark_file.py:60-66``, the files of ``convert_dark``): element 0 of the (1, N, ny, nx) cube of HDU 1"""
+    summer = layout == "summer2025"
+    hdr, data = calio.read_fits_image(path, 1 if summer else 0)
+    if summer and data is not None and data.ndim == 4 and data.shape[0] >= 1:
+        data = data[0]
     if data is None or data.ndim != 3 or hdr.get("BITPIX") != 16 or hdr.get("BZERO", 0) != 32768 or hdr.get("BSCALE", 1) != 1:
         raise ValueError(f"{path}: a cube of unsigned 16-bit samples (BITPIX 16, BZERO 32768) is needed")
     return data
 
 
-def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None):
+def _dev_cube(cube):
+    """an exposure that is in HBM already (``convert_frames.frames_to_cube``): uint16 (1, N, ny, nx) or (N, ny, nx)"""
+    if cube.dtype != np.dtype(np.uint16) or cube.ndim not in (3, 4) or (cube.ndim == 4 and cube.shape[0] != 1):
+        raise TypeError(f"a uint16 DevArray cube (1, N, ny, nx) or (N, ny, nx) is needed, not {cube.dtype.name} {tuple(cube.shape)}")
+    return DevArray(cube.t[0], np.uint16) if cube.ndim == 4 else cube
+
+
+def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July"):
     """The clipped mean of the group means of ``files``, float32 (ng, ny, min(nside, width)): one pass over the files, or one
-    per band of ``band_rows`` rows (default: as many rows as fit into four fifths of the free device memory)."""
+    per band of ``band_rows`` rows (default: as many rows as fit into four fifths of the free device memory).  ``layout``: where
+    an exposure sits in its file (``_open_dark``).  ``files`` may also be a list of ``DevArray`` cubes, uint16 (1, N, ny, nx) or
+    (N, ny, nx) in native samples: they are read where they are and no file is opened."""
     import torch
 
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r} is not one of {', '.join(LAYOUTS)}")
     ctx = ctx or _native.default_context()
-    first = _open_dark(files[0])
+    resident = len(files) > 0 and all(is_dev(f) for f in files)
+    first = _dev_cube(files[0]) if resident else _open_dark(files[0], layout)
     _, ny, width = first.shape
     nx = min(int(nside), width)
     ng = len(reads) // 2
     if band_rows is None:
         free = int(torch.cuda.mem_get_info(ctx.device)[0])
-        nreads_bytes = first.shape[0] * width * 2   # the staged samples of one exposure, per row
+        nreads_bytes = 0 if resident else first.shape[0] * width * 2   # the staged samples of one exposure, per row
         band_rows = max(1, min(ny, int(0.8 * free) // (4 * ng * len(files) * nx + nreads_bytes)))
     del first
     out = np.empty((ng, ny, nx), np.float32)
@@ -84,15 +105,20 @@ def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None):
             if j % 10 == 0:
                 print("loading groups", y0, j)
                 sys.stdout.flush()
-            stack.add(_open_dark(name), fits_be16=True)
-        out[:, y0:y1, :] = stack.finish(sigma=3)
+            if resident:
+                stack.add(_dev_cube(name))
+            else:
+                stack.add(_open_dark(name, layout), fits_be16=True)
+        mean = stack.finish(sigma=3)
+        out[:, y0:y1, :] = mean.numpy() if is_dev(mean) else mean
         del stack
     return out
 
 
-def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, band_rows=None, ctx=None):
+def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July"):
     """Write the dark file ``outfile`` and its read-noise sibling; returns their two paths.  ``reads`` (the flat ``READS`` list)
-    replaces the yaml of the working directory; ``nside`` is the script's constant (smaller frames: for tests)."""
+    replaces the yaml of the working directory; ``nside`` is the script's constant (smaller frames: for tests); ``layout``
+    ``"summer2025"`` reads the exposures as ``convert_dark`` writes them (``dark_data``)."""
     sca, nside = int(sca), int(nside)
     if reads is None:
         with open("settings_" + pattern + ".yaml") as f:
@@ -103,7 +129,7 @@ def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, ba
     print(files)
     if not files:
         raise FileNotFoundError(f"no noise file {target[:-8]}001.fits")
-    darkave = dark_data(files, reads, nside=nside, band_rows=band_rows, ctx=ctx)
+    darkave = dark_data(files, reads, nside=nside, band_rows=band_rows, ctx=ctx, layout=layout)
 
     # the dark current maps, read noise and reset noise of the summary
     header, summary = calio.read_fits_image(noise_out, 1)

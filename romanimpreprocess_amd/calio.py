@@ -332,12 +332,13 @@ class FitsHeader(dict):
     text = ""
 
 
-def read_fits_image(path, hdu=0):
+def read_fits_image(path, hdu=0, header_only=False):
     """``(header, data)`` of one HDU of a FITS file: the primary HDU (0) or an image extension, by index or by ``EXTNAME``.
     ``header`` is a dict (``FitsHeader``); ``data`` is a read-only memory map of the samples AS STORED -- big-endian int16,
     float32 or float64 (BITPIX 16 / -32 / -64), shape (NAXISn, ..., NAXIS1), ``BZERO`` / ``BSCALE`` not applied -- so that a 2 GB
     cube is not copied on the host; None for an HDU without data.  A last data block that is not padded to 2880 bytes is
-    accepted.  Nothing else of FITS (tables, other BITPIX, compression, checksums) is read."""
+    accepted.  Nothing else of FITS (tables, other BITPIX, compression, checksums) is read.  ``header_only``: ``(header, None)``
+    whatever the HDU holds (a caller that wants to name what it refuses)."""
     path = os.fspath(path)
     size = os.path.getsize(path)
     want_name = hdu.strip().upper() if isinstance(hdu, str) else None
@@ -363,7 +364,7 @@ def read_fits_image(path, hdu=0):
             nbytes = abs(bitpix) // 8 * (int(header.get("PCOUNT", 0)) + int(np.prod(shape, dtype=np.int64))) * int(header.get("GCOUNT", 1)) \
                 if naxis else 0
             if index == hdu if want_name is None else str(header.get("EXTNAME", "")).strip().upper() == want_name:
-                if not naxis or not nbytes:
+                if header_only or not naxis or not nbytes:
                     return header, None
                 if index and header.get("XTENSION", "").strip() != "IMAGE":
                     raise ValueError(f"{path}: HDU {index} is not an image extension")

@@ -12,7 +12,9 @@
 //   told by a `location` argument    RIP_DEVICE arrays are used where they are -- the stack of group means is too large to copy;
 //                                    the OUTPUTS of rip_cal_gain_ipc4d (gainfile.hip), whose inputs are small host tables;
 //                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst;
-//                                    rip_stage_l2_planes, rip_stage_l2_refpix_strips (l2out.hip): one location for every pointer
+//                                    rip_stage_l2_planes, rip_stage_l2_refpix_strips (l2out.hip): one location for every pointer;
+//                                    rip_cal_raw_frame (rawframes.hip): the frame by its location, the cube plane always in HBM;
+//                                    rip_cal_frame_slopes: the cube always in HBM, the slopes by out_location
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
