@@ -15,13 +15,13 @@
 // 9 of 10 ... 15 of 16, and 10, 12, 14 are the 16-group form with fewer ring planes (narrow, columns, waves per SIMD, cache
 // policy and ring set inherited from it unchanged; none of these was chosen by a timing run of its own).  Per form, from the
 // compiler's resource report (VGPRs: range over the three Legendre orders and both starts; no form spills a vector register
-// or uses scratch) and C2Form::lds_bytes:
+// or uses scratch; 5 to 8 groups of f32 ipc4d: both the instantiation with and the one without a bias stream) and C2Form::lds_bytes:
 //   G      f32 ipc4d: VGPRs  LDS bytes  pb      f64 ipc4d: VGPRs  LDS bytes  pb / pbc / nbo
-//   5      102               67872      1       134-135           157056     1 / 1 / 2
-//   6      104-109           67872      1       137               157056     1 / 1 / 2
-//   7      111-124           80256      2       147               160256     2 / 1 / 2
-//   8      119-128           80256      2       153               160256     2 / 1 / 2
-//   9      120-128           97408      1       171               95712      1 / 1 / 2
+//   5      101-103           68448      1       134-135           157056     1 / 1 / 2
+//   6      104-111           68448      1       137               157056     1 / 1 / 2
+//   7      111-124           81024      2       147               160256     2 / 1 / 2
+//   8      115-128           81024      2       153               160256     2 / 1 / 2
+//   9      120-124           97408      1       171               95712      1 / 1 / 2
 //   10     122-128           97408      1       179               95712      1 / 1 / 2
 //   11     131               115968     1       221               114240     3 / 2 / 4
 //   12     139               115968     1       227               114240     3 / 2 / 4
@@ -123,7 +123,20 @@ struct C2Form {
     // re-read (traffic 1.33 -> 1.18 x), five loads fewer per step in flight in the fit role.  The 16-group forms have no K ring.
     static constexpr int krn_room = (160 * 1024 - kr_ofs) / (2 * cols * ks);
     static constexpr int krn = narrow == 2 ? 0 : (krn_room < 9 ? krn_room : 9);
-    static constexpr int lds_bytes = kr_ofs + 2 * krn * cols * ks;
+    // The LEAN pieces of the 256-column form (f32 ipc4d, 5 to 8 groups), which is bound by the instructions it issues:
+    //   - nobias: a second instantiation WITHOUT the biascorr stream (template parameter BIAS of the kernel) runs where the call
+    //     has none (ChainArgs::bias_records == 0): no biascorr loads, no S - bs, no registers for them.  Every other form keeps
+    //     the one instantiation, whose zero-record descriptor drops the loads in hardware.
+    //   - lt: the channel-line values m * y + c of a row are computed once per (ingest wave, channel, group) and read from a
+    //     table by the lanes, [cols / 64][nlc][G] doubles (a table per ingest wave: in quad mode every wave column marches down
+    //     a row range of its own): 768 bytes at 8 groups, 81024 in all, still two workgroups per CU.  The narrow forms (f64
+    //     ipc4d, and 9 to 16 groups) keep the per-lane evaluation: f64 ipc4d x 5 to 8 groups sizes its K ring from what the rest
+    //     of the layout leaves of the CU's 160 KB (3.5 to 6.6 KB stay free), the forms of 9 to 16 groups have room; none of
+    //     them was measured with a table, so none was changed.
+    static constexpr bool nobias = narrow == 0;
+    static constexpr bool lt = narrow == 0;
+    static constexpr int lt_ofs = kr_ofs + 2 * krn * cols * ks;               // [cols / 64][nlc][G] double: line values of the row
+    static constexpr int lds_bytes = lt_ofs + (lt ? (cols / 64) * nlc * G * 8 : 0);
     static_assert(lds_bytes <= (narrow == 0 ? 80 : 160) * 1024, "the 256-column form runs two workgroups per CU, the others one");
 
     // Cache policy of the ONCE-read arrays (aux bits of the buffer loads; 2 = nt: stream through the caches).  The narrow forms' fit

@@ -23,6 +23,9 @@
 // ingest thread of a column to its fit thread (merged flag word, packed groupdq bytes, gain); and the K ring (2 rows): the nine
 // IPC coefficients of a pixel are loaded ONCE, by its ingest thread, and handed to its fit thread.  Saturated pixels are
 // refitted from registers (trunc_layers), so no per-pixel ramp staging in LDS.
+// The 256-column form is bound by the instructions it issues, not by its bytes, and has two LEAN pieces of its own (C2Form::nobias,
+// C2Form::lt): an instantiation without any biascorr load or subtraction (BIAS = false) for calls without a bias stream, and the
+// channel-line values m * y + c of a row from a small per-wave LDS table instead of two f64 operations per lane and group.
 #pragma once
 #include "chain_common.h"
 #include "chain2_form.h"
@@ -175,7 +178,7 @@ struct C2Legendre {
     __device__ __forceinline__ float chf(int L) const { return chfs[L]; }
 };
 
-template <int NP, int G, int START, typename KT, bool SKIP0 = false>
+template <int NP, int G, int START, typename KT, bool SKIP0 = false, bool BIAS = true>
 __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C2Form<G + (G & 1), sizeof(KT) == 8>::wps)) void chain2_kernel(
     ChainArgs a, const RipPlanHeader *__restrict__ h, const RipVariant *__restrict__ vars, const float *__restrict__ kvals,
     const RipDiff *__restrict__ diffs, double guard) {
@@ -186,6 +189,9 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     // odd G: GE = G + 1 register / ring slots, the last one DEAD (see the note above C2Form); g < G guards are compile-time
     constexpr int GE = G + (G & 1);
     using F = C2Form<GE, sizeof(KT) == 8>;
+    // BIAS = false: no biascorr stream at all (the launcher takes it where ChainArgs::bias_records == 0; C2Form::nobias)
+    static_assert(BIAS || F::nobias, "only the forms the table names have an instantiation without a bias stream");
+    constexpr bool LT = F::lt;   // line values from the per-wave table instead of two f64 operations per lane and group
     constexpr int COLS = F::cols;
     constexpr int KRN = F::krn;
     // narrow forms: the fit role requests the coefficients the K ring does not carry itself (k >= KRN: none at f64 ipc4d x 6
@@ -210,6 +216,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     uint32_t *QS = reinterpret_cast<uint32_t *>(lds_raw + F::qs_ofs);   // [3][QW][COLS] groupdq bytes, packed
     float *GN = reinterpret_cast<float *>(lds_raw + F::gn_ofs);         // [3][COLS] gain
     double *LN = reinterpret_cast<double *>(lds_raw + F::ln_ofs);       // [NLC][G][2]
+    double *LTB = reinterpret_cast<double *>(lds_raw + F::lt_ofs);      // [COLS / 64][NLC][GE] (C2Form::lt): m * y + c of the row A ingests
     // K ring: the nine IPC coefficients of destination (row, col), loaded ONCE by the ingest thread of the column and handed to
     // its fit thread (two rows live: C of row y runs two steps before O2 of row y)
     constexpr int NLC = F::nlc;
@@ -357,12 +364,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     if (!fit_role) {
         // =========================================================================== ingest waves
         // plane p of the calibration slab at row yl: scalar offset p*pl4 + yl*row4; groups likewise in their arrays
-        auto fetch_groups = [&](const RIP_K ChainArgs *ka, int y, int g0, int g1, RowRegs<NP, GE> &rr) {
+        auto fetch_groups = [&](const RIP_K ChainArgs *ka, int y, int g0, int g1, RowRegs<NP, GE, BIAS> &rr) {
             if ((dbg & 64) && y > R0 - 2) return;   // timing experiment: every row works on the first row's (valid) values
             __builtin_amdgcn_sched_barrier(0);
             const unsigned yl = (unsigned)min(max(y, ylo), yhi);
             const __amdgpu_buffer_rsrc_t rs = c2_rsrc(ka->data), rq = c2_rsrc(ka->gdq), rd = c2_rsrc(ka->dark_data),
-                                         rb = c2_rsrc(ka->bias, ka->bias_records);
+                                         rb = c2_rsrc(ka->bias, ka->bias_records);   // (BIAS = false: unused, no code)
             unsigned o4 = yl * row4 + (unsigned)g0 * pl4, o2 = yl * (row4 >> 1) + (unsigned)g0 * (pl4 >> 1),
                      o1 = yl * (row4 >> 2) + (unsigned)g0 * npix;
 #pragma unroll
@@ -375,7 +382,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                 rr.q[g] = c2_ld_u8<F::wring ? SA : 0>(rq, cc1, o1);   // (16 groups: the fit role reads these bytes again)
                 if (!flags_only) {
                     rr.dk[g] = c2_ld_f32<SA>(rd, cc4, o4);
-                    rr.bs[g] = c2_ld_f32<SA>(rb, cc4, o4);
+                    if constexpr (BIAS) rr.bs[g] = c2_ld_f32<SA>(rb, cc4, o4);
                 }
                 o4 += pl4;
                 o2 += pl4 >> 1;
@@ -384,7 +391,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             __builtin_amdgcn_sched_barrier(0);
         };
         // planes i0..i1-1 of [cf[0..NP-1], Smin, Smax, Sref, dq, gain]
-        auto fetch_coefs = [&](const RIP_K ChainArgs *ka, int y, int i0, int i1, RowRegs<NP, GE> &rr) {
+        auto fetch_coefs = [&](const RIP_K ChainArgs *ka, int y, int i0, int i1, RowRegs<NP, GE, BIAS> &rr) {
             if ((dbg & 64) && y > R0 - 2) return;
             __builtin_amdgcn_sched_barrier(0);
             const unsigned yl = (unsigned)min(max(y, ylo), yhi);
@@ -408,17 +415,39 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             }
             __builtin_amdgcn_sched_barrier(0);
         };
-        auto fetch_row = [&](int y, RowRegs<NP, GE> &rr) {  // prologue: the whole first row at once
+        auto fetch_row = [&](int y, RowRegs<NP, GE, BIAS> &rr) {  // prologue: the whole first row at once
             const RIP_K ChainArgs *ka = &kargs->a;
             fetch_coefs(ka, y, 0, NP + 5, rr);
             fetch_groups(ka, y, 0, G, rr);
         };
         constexpr int NCO = NP + 5;                 // coefficient-type planes per pixel
         constexpr int CO_STEP = (NCO + GP - 1) / GP;  // issued per pair of C
-        RowRegs<NP, GE> rr;
-        if constexpr (GE > G) rr.S[G] = rr.q[G] = 0u, rr.dk[G] = rr.bs[G] = 0.0f;
-        if constexpr (SKIP0) rr.S[0] = 0u, rr.dk[0] = rr.bs[0] = 0.0f;
+        RowRegs<NP, GE, BIAS> rr;
+        if constexpr (GE > G) rr.S[G] = rr.q[G] = 0u, rr.dk[G] = 0.0f;
+        if constexpr (SKIP0) rr.S[0] = 0u, rr.dk[0] = 0.0f;
+        if constexpr (BIAS) {
+            if constexpr (GE > G) rr.bs[G] = 0.0f;
+            if constexpr (SKIP0) rr.bs[0] = 0.0f;
+        }
         fetch_row(R0 - 2, rr);
+        // The line values of a row, one per (channel of the window, group): lanes 0 .. NLC * GE - 1 of every ingest wave evaluate
+        // them for the row ITS wave ingests next (quad mode: the wave columns are at different rows) into the wave's own table --
+        // here for the first row, then in S2 of every step for row r + 4, which A reads in S1 of the step after.  Written and read
+        // by the same wave, with a workgroup barrier between the two besides, so one buffer does.  Entries of a dead group are
+        // never read (a skipped first group's lines are zeros in LN).
+        const int lt_lane = tid & 63;
+        double *lt_w = LTB + (tid >> 6) * (NLC * GE);
+        auto line_values = [&](int y) {
+            if constexpr (LT) {
+                static_assert(NLC * GE <= 64, "one lane per (channel, group) of the wave's table");
+                if (lt_lane < NLC * GE) {
+                    const int ch = lt_lane / GE, g = lt_lane % GE;
+                    const double *ln = LN + (ch * G + (g < G ? g : 0)) * 2;
+                    lt_w[lt_lane] = rip_refpix_line(ln[0], ln[1], (double)y);
+                }
+            }
+        };
+        line_values(R0 - 2);
         int so_c = (R0 - 5 + 2 + 3000) % 3;  // O1 ring slot of row yc = r + 2
         double rcn[G];  // row corrections of the row the next step ingests
         {
@@ -486,9 +515,16 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
                                     continue;
                                 }
                             }
-                            const double *ln = LN + (chr * G + g) * 2;
-                            float S = rip_refpix_apply((float)rr.S[g], rr.dk[g], rc[g], ln[0], ln[1], yd);
-                            if (act) S = S - rr.bs[g];   // gen_cal_image.py:559-565
+                            float S;
+                            if constexpr (LT) {
+                                S = rip_refpix_apply_iel((float)rr.S[g], rr.dk[g], rc[g], lt_w[chr * GE + g]);
+                            } else {
+                                const double *ln = LN + (chr * G + g) * 2;
+                                S = rip_refpix_apply((float)rr.S[g], rr.dk[g], rc[g], ln[0], ln[1], yd);
+                            }
+                            if constexpr (BIAS) {
+                                if (act) S = S - rr.bs[g];   // gen_cal_image.py:559-565
+                            }
                             Sv[e] = S;
                             w[g / 4] |= (rr.q[g] & 0xffu) << (8 * (g & 3));
                         }
@@ -634,6 +670,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             auto fetch_coefs_beside = [&](int p) { fetch_coefs(kb2, r + 4, p * CO_STEP, min(p * CO_STEP + CO_STEP, NCO), rr); };
             // ---- S2: issue the raw loads of row r+4 (consumed in S1 of the next step), then C of row yc
             CH_T(4)
+            line_values(r + 4);   // the line values A of the next step subtracts
             {
                 // every lane evaluates (lanes without valid terms produce values nobody reads); the coefficient planes of
                 // the next row are requested between the pairs, unconditionally (see above)
@@ -1056,7 +1093,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
 #endif
 }
 
-template <int NP, int G, int START, typename KT, bool SKIP0 = false>
+template <int NP, int G, int START, typename KT, bool SKIP0 = false, bool BIAS = true>
 static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a) {
     using F = C2Form<G + (G & 1), sizeof(KT) == 8>;
     const size_t lds = F::lds_bytes;
@@ -1065,11 +1102,11 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
     const long grid = c2_form_geometry<F>(ag, ctx->ncu, ctx->chain_reserve, ctx->chain_quad, ctx->last_geo);
     static bool lds_set[64] = {};   // per device, once per instantiation (contexts are used from one thread each)
     if (lds > 48 * 1024 && !lds_set[ctx->device & 63]) {
-        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT, SKIP0>),
+        RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(chain2_kernel<NP, G, START, KT, SKIP0, BIAS>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set[ctx->device & 63] = true;
     }
-    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT, SKIP0>), dim3((unsigned)grid), dim3(F::threads), lds, ctx->stream, ag,
+    hipLaunchKernelGGL((chain2_kernel<NP, G, START, KT, SKIP0, BIAS>), dim3((unsigned)grid), dim3(F::threads), lds, ctx->stream, ag,
                        reinterpret_cast<const RipPlanHeader *>(plan->dev), plan->d_variants, plan->d_k, plan->d_diffs,
                        ctx->guard_band);
     RIP_HIP(ctx, hipGetLastError());
@@ -1082,12 +1119,23 @@ static int launch_chain2_s(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a
 // reads (plan.hip builds it from the plan's differences) must test exactly the differences of the compile-time mask -- for odd G
 // too, where no tested difference may touch the dead half of the last pair
 // skip0: take the form that skips group 0 (the caller has established that it may: rip_chain_may_skip_first, chain.hip)
+// A call without a bias stream (bias_records == 0: calibrate.hip, from the screening of the set at upload, caldir.hip) takes the
+// instantiation that has no biascorr loads and no subtraction where the form table names one (C2Form::nobias); in every other
+// form the zero-record descriptor of the one instantiation drops the loads.
+template <int NP, int G, typename KT, bool BIAS>
+static int launch_chain2_b(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0) {
+    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>())
+        return skip0 ? 1 : launch_chain2_s<NP, G, 0, KT, false, BIAS>(ctx, plan, a);
+    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>())
+        return skip0 ? launch_chain2_s<NP, G, 1, KT, true, BIAS>(ctx, plan, a) : launch_chain2_s<NP, G, 1, KT, false, BIAS>(ctx, plan, a);
+    return 1;
+}
 template <int NP, int G, typename KT>
 static int launch_chain2(rip_ctx *ctx, const RipPlan *plan, const ChainArgs &a, bool skip0) {
-    if (plan->h.start == 0 && plan->dense.valid == rip_full_valid<G, 0>()) return skip0 ? 1 : launch_chain2_s<NP, G, 0, KT>(ctx, plan, a);
-    if (plan->h.start == 1 && plan->dense.valid == rip_full_valid<G, 1>())
-        return skip0 ? launch_chain2_s<NP, G, 1, KT, true>(ctx, plan, a) : launch_chain2_s<NP, G, 1, KT>(ctx, plan, a);
-    return 1;
+    if constexpr (C2Form<G + (G & 1), sizeof(KT) == 8>::nobias) {
+        if (a.bias_records == 0) return launch_chain2_b<NP, G, KT, false>(ctx, plan, a, skip0);
+    }
+    return launch_chain2_b<NP, G, KT, true>(ctx, plan, a, skip0);
 }
 
 // The fused kernel for NP Legendre planes and ipc4d coefficients of type KT, the group counts of part PART of the list

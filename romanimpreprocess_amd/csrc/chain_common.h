@@ -93,12 +93,19 @@ __device__ __forceinline__ void fwd_rows_batch(const f2 *const (&rm)[NB], const 
     }
 }
 
-// raw bits of one row position, fetched one phase ahead of their use (no arithmetic on them in P)
-template <int NP, int G>
-struct RowRegs {
+// raw bits of one row position, fetched one phase ahead of their use (no arithmetic on them in P); the biascorr samples only in
+// the instantiations that have a bias stream
+template <int G, bool BIAS>
+struct RowBias {
+    float bs[G];
+};
+template <int G>
+struct RowBias<G, false> {};
+template <int NP, int G, bool BIAS = true>
+struct RowRegs : RowBias<G, BIAS> {
     uint32_t S[G];
     uint32_t q[G];
-    float dk[G], bs[G];
+    float dk[G];
     float cf[NP], smin, smax, sref, gain;
     uint32_t dq;
 };

@@ -107,12 +107,17 @@ struct GainConst<double> {
 // ============================================================================================= 2. linearity
 // reference_subtraction.py:123 and :67-68 in f64, cast back to f32 after each step (gen_cal_image.py:534-535, 554-556:
 // image = data - dark ; row / channel subtraction ; + dark).  rc = row correction of (group, y); (m, c) = the channel's line.
-__device__ __forceinline__ float rip_refpix_apply(float S, float dk, double rc, double m, double c, double yd) {
+// The value of a channel's line at row yd depends on (row, group, channel) alone: the fused kernel's 256-column form evaluates
+// rip_refpix_line once per such triple and hands it to rip_refpix_apply_iel; everything else calls rip_refpix_apply.
+__device__ __forceinline__ double rip_refpix_line(double m, double c, double yd) { return m * yd + c; }
+__device__ __forceinline__ float rip_refpix_apply_iel(float S, float dk, double rc, double iel) {
     float v = S - dk;
     v = (float)((double)v - rc);
-    const double iel = m * yd + c;
     v = (float)((double)v - iel);
     return v + dk;
+}
+__device__ __forceinline__ float rip_refpix_apply(float S, float dk, double rc, double m, double c, double yd) {
+    return rip_refpix_apply_iel(S, dk, rc, rip_refpix_line(m, c, yd));
 }
 
 // constants of degree L: the Legendre recurrence P_{L+1} = c1 z P_L - c2 P_{L-1} and the end-point slope P_L'(1) = chf
@@ -505,6 +510,7 @@ __device__ __forceinline__ void rip_load_pair(RipDensePair &r, const RipDense *d
         r.A[e] = KLD(dn->pairs[ps].A[e]);
         r.B[e] = KLD(dn->pairs[ps].B[e]);
         r.k1[e] = KLD(dn->pairs[ps].k1[e]);
+        r.k2[e] = KLD(dn->pairs[ps].k2[e]);
     }
 }
 
@@ -587,6 +593,15 @@ __device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], cons
     //   t = 8e-7 |s| rs  (rounding of num*inv_dt and of q - s, using |q| <= |delta| + |s|);  the threshold itself is
     //   known to +-band0.  With thp + t > 0 and thm - t > 0 (checked per pixel through rsmax >= every rs):
     //   sm > (thp + t) k1  => sure hit,   sm < (thm - t) k2  => surely no hit,   anything else (NaN included) -> exact pass.
+    // The band is formed ONCE PER PIXEL from tmax = s8 * rsmax instead of per difference from t = s8 * rs.  t <= tmax in f32:
+    // every tested difference has var = B dv + A s2 >= amin s2 (B >= 0 and dv >= 0, else amin is 0 and every lane takes the
+    // exact pass), so its rs is at most the rsqrt of amin s2 but for the roundings of the fma, the product and the two rsqrt
+    // (a few 1e-7 relative: the factor 1.000001 of rsmax covers them), and multiplying both by the same s8 >= 0 keeps the
+    // order (rounding is monotone).  Monotone again through the add / subtract and the product with k1 > 0, k2:
+    //   (thp + tmax) k1 >= (thp + t) k1   and   (thm - tmax) k2 <= (thm - t) k2   (thm - tmax >= sth32 / 2 > 0 where `pass`),
+    // so every sure decision of this test is a sure decision of the per-difference band, which is right; the differences in
+    // between go to the exact pass, which decides them as the reference does.  The result cannot change.  k2 = 2 - k1 comes
+    // from the plan (RipDensePair::k2: the same f32 subtraction, made once on the host).
     const float band0 = 2e-6f * fabsf(sth32) + 4.5e-6f * fabsf(slope_th) + 1e-30f;  // 4e-6: __logf; 0.5e-6: its argument
     const float s2 = st.s2;
     const float s8 = fabsf(s) * 8.1e-7f;
@@ -594,6 +609,8 @@ __device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], cons
     const float rsmax = __frsqrt_rn(KLD(dn->amin) * s2) * 1.000001f;
     const bool pass = fmaf(s8, rsmax, band0) <= 0.5f * sth32;  // false for NaN, for amin == 0 and for sth32 <= 0
     const bool lane_exact = !(guard < 1e300) || !pass;
+    const float tmax = s8 * rsmax;
+    const float hp = thp + tmax, lm = thm - tmax;  // the two thresholds of the pixel, before the factors of a difference
     uint32_t jfast = 0, unsure_mask = 0;
     rf2 dB[GP];  // (d[2p+1], d[2p+2])
 #pragma unroll
@@ -614,10 +631,8 @@ __device__ __forceinline__ void fit_full_pk_a(const rf2 (&dA)[(G + 1) / 2], cons
         const rf2 var = __builtin_elementwise_fma(rf2{r.B[0], r.B[1]}, rf2{dv, dv}, as2);
         const rf2 rs = {__frsqrt_rn(var.x), __frsqrt_rn(var.y)};
         const rf2 sm = delta * rs;
-        const rf2 t = rs * s8;
-        const rf2 k1 = {r.k1[0], r.k1[1]};
-        const rf2 hiT = (t + thp) * k1;
-        const rf2 loT = (rf2{thm, thm} - t) * (rf2{2.0f, 2.0f} - k1);  // 2 - k1 <= 1 - r <= 1/(1+r)
+        const rf2 hiT = rf2{hp, hp} * rf2{r.k1[0], r.k1[1]};
+        const rf2 loT = rf2{lm, lm} * rf2{r.k2[0], r.k2[1]};  // k2 = 2 - k1 <= 1 - r <= 1/(1+r)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             if (!((vbits >> e) & 1u)) continue;  // plan-uniform

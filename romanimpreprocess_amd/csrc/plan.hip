@@ -143,6 +143,7 @@ int rip_plan_create(rip_ctx *ctx, const rip_plan_desc *d, int *plan_id) {
                 const int bit = 2 * ps + e;
                 const bool used = bit < 32 && ((dn.valid >> bit) & 1u);
                 if (!used) dn.pairs[ps].A[e] = 1.0f;  // keeps the approximate variance positive for unused slots
+                dn.pairs[ps].k2[e] = 2.0f - dn.pairs[ps].k1[e];  // the subtraction the kernels made per difference
             }
     }
     // group 0's weight in every variant: the one question, asked of the description the weights above were made from

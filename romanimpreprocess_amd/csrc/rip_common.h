@@ -55,6 +55,7 @@ struct RipPlanHeader {
 struct RipDensePair {
     float inv_dt[2], A[2], B[2];  // per element e: difference (i+e, i+e+di)
     float k1[2];                   // k1 >= 1/(1-r), r = relative error bound of the approximate significance (2 - k1 <= 1/(1+r))
+    float k2[2];                   // 2 - k1 (f32 subtraction, plan.hip): the factor of the lower threshold
 };
 struct RipDense {
     uint32_t valid;                    // bit 2*ps + e: that difference is tested (fitting.py:225-229)
