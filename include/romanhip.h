@@ -586,7 +586,10 @@ typedef struct rip_synth_cal {
    (nya,nxa) f32 holds integers, or -- poisson != 0 -- the MEAN, of which a Poisson deviate is drawn first (what
    Image2D.simulate :660-662 adds before it calls make_l1_fullcal).  t_reads: nreads times, HOST array, ascending.
    Deviates from the device generator (Philox; inversion / BTRS binomial, inversion / PTRS Poisson) keyed by (seed, read,
-   pixel).  The distribution is what is reproduced, not romanisim's numpy stream.  Asynchronous like the other rip_synth_*
+   pixel).  The distribution is what is reproduced, not romanisim's numpy stream.  Poisson means below 10 per read are inverted
+   in f32 against a 23-bit uniform: the count lies within 64 * 2^-24 in probability of the f64 quantile, and at the largest
+   uniforms, where the f32 sum of the probabilities saturates, the search ends at the count whose term no longer moves the sum
+   (tests/test_gpu_synth_deviates.py: never beyond the quantile of 1 - 2^-32 at 160 means of 0.05 .. 9.99).  Asynchronous like the other rip_synth_*
    entries when t_reads equals those of the previous call (the device copy of the share table is kept); a NEW table first
    waits for the work queued on the stream. */
 int rip_synth_apportion(rip_ctx *ctx, const float *counts, int nya, int nxa, int poisson, int nreads, const double *t_reads,

@@ -50,8 +50,11 @@ __device__ __forceinline__ void apportion_poisson_pixel(size_t i, double c, size
     bool small = false;
     riprng::PtrsPlan plan{};
     // small means: the cumulative probabilities of the first NT counts once per run of reads of one mean (registers), a deviate is
-    // then NT comparisons without a loop -- the sequential search of the same sums (cdf_j = cdf_(j-1) + p_j, p_j = p_(j-1) lam / j,
-    // stopped where p_j <= 1e-12 cannot move the sum any more: those entries are +inf), continued in a loop past the table
+    // then NT comparisons without a loop -- the sequential search of the same sums (cdf_j = cdf_(j-1) + p_j, p_j = p_(j-1) lam / j),
+    // continued in a loop past the table.  The f32 sum stops growing once p_j is below half an ulp of it (3e-8 near 1), and it may
+    // stop BELOW the two largest uniforms (1 - 2^-24 and 1 - 3 * 2^-24): the search ends at the first count whose term no longer
+    // moves the sum (that entry and the later ones are +inf) -- a count with a tail probability of a few 1e-8, as the uniform asks
+    // for.  p_j <= 1e-12 bounds the search besides.
     float cdf_tab[NT], p_end = 0.0f, cdf_end = 0.0f;
 #pragma unroll
     for (int j = 0; j < NT; ++j) cdf_tab[j] = 0.0f;
@@ -75,9 +78,11 @@ __device__ __forceinline__ void apportion_poisson_pixel(size_t i, double c, size
                         live = live && p_ > 1e-12f;
                         cdf_tab[j] = live ? cdf : __builtin_inff();
                         p_ *= lam32 * __builtin_amdgcn_rcpf((float)(j + 1));
-                        cdf += p_;
+                        const float next = cdf + p_;
+                        live = live && next > cdf;   // the term no longer moves the f32 sum: no later one will
+                        cdf = next;
                     }
-                    p_end = p_, cdf_end = cdf;
+                    p_end = live ? p_ : 0.0f, cdf_end = cdf;
                 }
                 if constexpr (BIG)
                     if (!small && lam > 0.0) plan = riprng::ptrs_plan(lam, sc * sw[r], lc + lw[r]);
@@ -90,10 +95,12 @@ __device__ __forceinline__ void apportion_poisson_pixel(size_t i, double c, size
                 for (int j = 0; j < NT; ++j) kk += (u > cdf_tab[j]) ? 1 : 0;
                 if (kk == NT) {
                     float p_ = p_end, cdf = cdf_end;
-                    while (u > cdf && p_ > 1e-12f && kk < 200) {   // (p below 1e-12: the sum cannot grow any more)
+                    while (u > cdf && p_ > 1e-12f && kk < 200) {
                         ++kk;
                         p_ *= lam32 * __builtin_amdgcn_rcpf((float)kk);
-                        cdf += p_;
+                        const float next = cdf + p_;
+                        if (!(next > cdf)) break;   // the sum has stopped below u: this count, not the one where the terms underflow
+                        cdf = next;
                     }
                 }
                 k = (double)kk;
@@ -128,7 +135,8 @@ __global__ __launch_bounds__(256) void apportion_kernel(const float *__restrict_
         // cumulative probability passes a 23-bit uniform deviate -- with the exponential once per run of reads of one share (equal read
         // spacings give equal shares up to the rounding of the time differences) and ONE Philox block for four reads; larger means
         // by transformed rejection, its constants once per run of reads too and its acceptance test in f32 first (riprng::
-        // poisson_ptrs).  Device deviates are unpinned by nature (tests: mean, variance, third moment, histogram, P(0)).
+        // poisson_ptrs).  Every deviate is a function of (seed, pixel, read) at the counters of DESIGN.md ("Shared device headers"):
+        // tests/synth_deviates_ref.py restates them and tests/test_gpu_synth_deviates.py holds each draw to it.
         c = c < 0.0 ? 0.0 : (c > 2.0e9 ? 2.0e9 : c);
         if (MODE == 2 && c * w_max >= defer_lam) {
             // two classes of lists -- means below 10 (sequential search) and above (transformed rejection) -- of DEFER_LISTS lists
