@@ -845,6 +845,52 @@ int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny,
 int rip_cal_frame_slopes(rip_ctx *ctx, const uint16_t *cube, int n, int nc, size_t npix, const double *w0, double de0, const double *w1,
                          double de1, float *slp, int out_location);
 
+/* ---- focal-plane overview of a calibration set (utils/fpaplot.py of the reference) ---------- */
+#define RIP_FPA_MAX_PLANES 8
+
+/* fpaplot.read_sca_image (:131-141) for up to 8 quantities of one SCA in one launch over the frame: the masked block means.
+   dq (nside,nside) u32 where dq_location says, NULL: nothing is masked; grow[32] as rip_stage_build_mask (host array).  The mask
+   is grown on the fly from dq (zero padded at the frame edge, the rule of rip_stage_build_mask) and never written to memory; dq
+   is read once plus a 2-pixel halo, each plane once.  n1 is a power of two that divides nside; a bin is s x s pixels, s =
+   nside / n1, any s from 1 to nside.  The planes come as four HOST tables of nplanes entries: plane i is (sides[i], sides[i])
+   elements of dtypes[i] (RIP_F32 or RIP_F64) at planes[i], living where locations[i] says (RIP_HOST: through a scoped device
+   buffer; RIP_DEVICE: read where it is).  A plane of side m < nside sits centred in the frame, zeros around it (np.pad(obj,
+   (nside - m) // 2)).  out (nplanes,n1,n1) f64 where out_location says:
+     out[i][by][bx] = sum / count over the pixels of the bin where the grown mask is 0 and the value is not NaN (padded zeros
+     count); NaN where count is 0; +-inf propagate as in numpy (inf + -inf = NaN).
+   Sums are f64 in a fixed order without floating-point atomics: two calls give the same bits.  The call returns when its kernels
+   and copies are done.
+   RIP_EINVAL, before anything is launched or copied: nside < 1; n1 not a power of two or not dividing nside; nplanes outside
+   1..8; a NULL plane or out; a dtype that is neither RIP_F32 nor RIP_F64; a plane with side < 1, side > nside or nside - side
+   odd; a growth that is not one of 0, 1, 5, 9, 25; an unknown location. */
+int rip_fpa_bin(rip_ctx *ctx, const uint32_t *dq, int dq_location, const uint8_t grow[32], int nside, int n1, int nplanes,
+                const void **planes, const int *dtypes, const int *sides, const int *locations, double *out, int out_location);
+
+/* fpaplot.make_big_image (:223-275) and multi_image (:345-358): the finished RGB picture in one store-only launch, every byte
+   written once by the thread that owns the pixel.  The picture is npanel panels of (ny,nx) pixels, nw abreast with `gap` pixels
+   between them; every panel shows the nsca SCAs as n1 x n1 maps.  All positions are the host's, computed with the reference's
+   integer arithmetic; the ticks are sc = max(n1, 64) / 64 pixels wide and 2 sc high.
+     maps     (npanel,nsca,n1,n1) f64, where maps_location says: the means of rip_fpa_bin
+   HOST tables:
+     present  (npanel,nsca) u8    0: the SCA's file is absent and it draws as an all-zero map (:114-117)
+     sca_pos  (nsca,2) i32        (posy, posx) of the SCA's first pixel in its panel; a later SCA overwrites an earlier one
+     vmin, vmax (npanel) f64;  scale (npanel) u8: non-zero draws the colour bar and its three ticks
+     table    (256,3) u8          the colour table;  glyphs (256,12,6) u8 or NULL (then nstamps must be 0)
+     stamps   (nstamps,6) i32     panel, y, x, size, value, character: one letter of write_text (:150-182), drawn in list order --
+              glyph rows reversed, every cell size x size pixels, only where the glyph is > 0, all three channels = value
+   Per SCA pixel: v = nan_to_num(mean) (NaN 0, +-inf +-DBL_MAX), x = clip((v - vmin) / (vmax - vmin), 0, 1) in f64, index =
+   min(int(x * 256), 255), colour = table[index].  The background is white; over the SCAs comes the bar -- rows ny - n1/8 .. ny-1,
+   columns nx/2 - n1 .. nx/2 + n1 - 1, linspace(0, 1, 2 n1) through the same index rule -- then the ticks, then the stamps.
+   out (nh * ny + (nh-1) * gap, nw * nx + (nw-1) * gap, 3) u8 where out_location says, nh = (npanel - 1) / nw + 1.
+   RIP_EINVAL, before anything is launched or copied: a NULL table; a count below 1 (nstamps below 0); a scale with n1 < 8 (there
+   the reference's arr[-(n1 // 8):] is the whole image) or with a bar or tick outside the panel; an SCA or a stamp that does not
+   start inside its panel, or reaches past it (the reference result there is numpy's negative-index slicing or an exception); a
+   stamp of a panel that does not exist, of size < 1, of a value or character outside 0..255; stamps without glyphs; a vmin or
+   vmax that is not finite, or vmax == vmin; an unknown location. */
+int rip_fpa_render(rip_ctx *ctx, int n1, int nsca, int npanel, int nw, int gap, int ny, int nx, const double *maps, int maps_location,
+                   const uint8_t *present, const int32_t *sca_pos, const double *vmin, const double *vmax, const uint8_t *scale,
+                   const uint8_t *table, const uint8_t *glyphs, int nstamps, const int32_t *stamps, uint8_t *out, int out_location);
+
 #ifdef __cplusplus
 }
 #endif

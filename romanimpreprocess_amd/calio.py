@@ -13,7 +13,7 @@ can be exchanged with the reference tooling.  ``parse_fits_header`` reads the FI
 (``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy; ``read_fits_image`` maps the image of one HDU of a FITS file
 (the dark exposures and noise summaries of ``calfiles/make_dark_file.py``).  ``fits_header`` and ``write_fits`` write image HDUs
 (the mask files, ``FITSOUT`` and the display dumps of the calibration-file scripts): the header on the host, the data units put
-into FITS storage order on the GPU (``rip_stage_fits_encode``).
+into FITS storage order on the GPU (``rip_stage_fits_encode``).  ``write_png`` writes an 8-bit RGB picture (``utils/fpaplot.py``).
 """
 
 import bz2
@@ -544,3 +544,22 @@ def write_fits(path, hdus, ctx=None, chunk_bytes=64 << 20):
             thread.join()
     if failed:
         raise failed[0]
+
+
+# ------------------------------------------------------------------------------- PNG
+def write_png(path, arr, level=6):
+    """An (ny, nx, 3) uint8 array as an 8-bit RGB PNG, rows in the order given (the picture of ``utils/fpaplot.py``; its script
+    hands the rows over upside-down).  Unfiltered scanlines, deflated with the standard library's ``zlib``."""
+    arr = np.asarray(arr)
+    if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
+        raise ValueError(f"write_png: expected a uint8 array (ny, nx, 3), got {arr.dtype}{arr.shape}")
+    ny, nx, _ = arr.shape
+    rows = np.zeros((ny, 1 + 3 * nx), np.uint8)   # every scanline starts with its filter type: 0, none
+    rows[:, 1:] = arr.reshape(ny, 3 * nx)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", nx, ny, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), level)) + chunk(b"IEND", b""))

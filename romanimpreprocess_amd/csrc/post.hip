@@ -11,6 +11,7 @@
 // holds, the noise-layer driver in HBM); the area map may also be written to device memory in place.
 #include <cmath>
 
+#include "rip_grow.h"
 #include "rip_host.h"
 #include "rip_select.h"
 
@@ -19,25 +20,16 @@ namespace {
 // ------------------------------------------------------------------------------------------ mask
 // layer(bit) grown by its kernel: 1 = copy, 5 = plus, 9 = 3x3, 25 = 5x5 (zero padded, scipy.signal.convolve mode="same")
 __global__ __launch_bounds__(256) void mask_build_kernel(const uint32_t *__restrict__ dq, uint8_t *__restrict__ out, int ny,
-                                                         int nx, uint32_t m1, uint32_t m5, uint32_t m9, uint32_t m25) {
+                                                         int nx, GrowMasks g) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= nx) return;
-    uint32_t hit = dq[(size_t)y * nx + x] & (m1 | m5 | m9 | m25);
-    const uint32_t grown = m5 | m9 | m25;
-    if (!hit && grown) {
-        for (int dy = -2; dy <= 2 && !hit; ++dy) {
-            const int yy = y + dy;
-            if (yy < 0 || yy >= ny) continue;
-            for (int dx = -2; dx <= 2; ++dx) {
-                const int xx = x + dx;
-                if (xx < 0 || xx >= nx) continue;
-                const int ay = dy < 0 ? -dy : dy, ax = dx < 0 ? -dx : dx;
-                uint32_t m = m25;
-                if (ay <= 1 && ax <= 1) m |= m9;
-                if (ay + ax <= 1) m |= m5;
-                hit |= dq[(size_t)yy * nx + xx] & m;
-            }
-        }
+    const auto at = [&](int yy, int xx) -> uint32_t { return (xx < 0 || xx >= nx) ? 0u : dq[(size_t)yy * nx + xx]; };
+    uint32_t hit = 0;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= ny) continue;
+        hit |= grow_row(g, dy < 0 ? -dy : dy, at(yy, x), at(yy, x - 1) | at(yy, x + 1), at(yy, x - 2) | at(yy, x + 2));
     }
     out[(size_t)y * nx + x] = hit ? 1 : 0;
 }
@@ -282,25 +274,16 @@ __global__ __launch_bounds__(256) void pixel_area_kernel(const rip_wcs_desc w, i
 
 int rip_stage_build_mask(rip_ctx *ctx, const uint32_t *dq, int ny, int nx, const uint8_t grow[32], uint8_t *mask) {
     if (!dq || !grow || !mask || ny < 1 || nx < 1) return rip_fail(ctx, RIP_EINVAL, "build_mask: bad arguments");
-    uint32_t m1 = 0, m5 = 0, m9 = 0, m25 = 0;
-    for (int b = 0; b < 32; ++b) {
-        const uint32_t bit = 1u << b;
-        switch (grow[b]) {
-            case 0: break;
-            case 1: m1 |= bit; break;
-            case 5: m5 |= bit; break;
-            case 9: m9 |= bit; break;
-            case 25: m25 |= bit; break;
-            default: return rip_fail(ctx, RIP_EINVAL, "build_mask: growth %d of bit %d is not one of 0, 1, 5, 9, 25", grow[b], b);
-        }
-    }
+    GrowMasks g;
+    const int bad = grow_masks(grow, &g);
+    if (bad >= 0) return rip_fail(ctx, RIP_EINVAL, "build_mask: growth %d of bit %d is not one of 0, 1, 5, 9, 25", grow[bad], bad);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)ny * nx;
     DevBuf<uint32_t> d(ctx);
     DevBuf<uint8_t> o(ctx);
     int rc;
     if ((rc = d.upload(dq, n)) || (rc = o.alloc(n))) return rc;
-    hipLaunchKernelGGL(mask_build_kernel, dim3((nx + 255) / 256, ny), dim3(256), 0, ctx->stream, d.p, o.p, ny, nx, m1, m5, m9, m25);
+    hipLaunchKernelGGL(mask_build_kernel, dim3((nx + 255) / 256, ny), dim3(256), 0, ctx->stream, d.p, o.p, ny, nx, g);
     RIP_HIP(ctx, hipGetLastError());
     if ((rc = o.download(mask, n))) return rc;
     return dev_sync(ctx);

@@ -14,7 +14,9 @@
 //                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst;
 //                                    rip_stage_l2_planes, rip_stage_l2_refpix_strips (l2out.hip): one location for every pointer;
 //                                    rip_cal_raw_frame (rawframes.hip): the frame by its location, the cube plane always in HBM;
-//                                    rip_cal_frame_slopes: the cube always in HBM, the slopes by out_location
+//                                    rip_cal_frame_slopes: the cube always in HBM, the slopes by out_location;
+//                                    rip_fpa_bin (fpaplot.hip): dq, every plane and out each by a location of its own;
+//                                    rip_fpa_render: the maps and the picture by theirs, its small tables host arrays
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
