@@ -845,6 +845,60 @@ int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny,
 int rip_cal_frame_slopes(rip_ctx *ctx, const uint16_t *cube, int n, int nc, size_t npix, const double *w0, double de0, const double *w1,
                          double de1, float *slp, int out_location);
 
+/* ---- the linearitylegendre file -------------------------------------------------------------- */
+/* The step of the reference's runs/2026_July/make_sca_files_2026Jul.job that calls solid-waffle's linearity_run on the JSON of
+   write_linearity_config.pl.  solid-waffle's source is not in the reference tree: the rule below IS the specification, parity
+   with solid-waffle is unpinned.  Pinned by the reference are the JSON, the file's schema and what its consumers expect of the
+   result: phi(Sref) = 0, dphi/dS(Sref) = 1, pflat[0] the bright flat's rate.  Both calls return when their kernels are done. */
+
+/* One exposure cube added to the per-frame sums of its ramp set.  cube (nreads,ny_file,nx_file) u16 where `location` says
+   (RIP_HOST: the frames and rows used are staged through a scoped device buffer); fits_be16 as for rip_cal_group_means.  sums
+   (nreads - f0, ny, nx) u32, ALWAYS a device pointer, zeroed by the caller before the first exposure:
+     sums[f - f0][y - y0][x] += cube[f][y][x]   for f = f0 .. nreads-1, y = y0 .. y0+ny-1, x = 0 .. nx-1
+   count: the number of exposures added so far.  The sums are integers: the result depends on no order and is the same on every
+   run.  With nx_file % 8 == 0 and a 16-byte aligned first sample a lane takes 8 pixels (and two 16-byte read-modify-writes of
+   sums where nx % 4 == 0 and sums is 16-byte aligned); otherwise one.  The forms give the same words.
+   RIP_EINVAL, before anything is launched or copied: count outside 0..65535 (65536 exposures of 65535 still fit in u32), nx >
+   nx_file, rows outside the frame, f0 outside [0, nreads), a NULL pointer, an unknown location. */
+int rip_cal_frame_sums(rip_ctx *ctx, const uint16_t *cube, int location, int nreads, int ny_file, int nx_file, int y0, int ny, int nx,
+                       int f0, int fits_be16, uint32_t *sums, int count);
+
+/* The fit, one lane per pixel.  HOST tables of nsets (1..8) entries: sums[k] the DEVICE pointer of set k's u32 (nframes[k],ny,nx)
+   sums, counts[k] its exposures, first[k] the first frame used (TSTART - 1).  sref (ny,nx) f32 and every output are DEVICE
+   pointers; the planes hold the rows y0 .. y0+ny-1 of a frame of ny_frame rows (a row band; the whole frame: 0, ny), which only the
+   border looks at.  bright: the set that defines the range; dark: the dark set, or -1.  All arithmetic is f64, one rounding per
+   operation (no contraction; / and sqrt correctly rounded), in the order of tests/linfit_ref.py; results are rounded once.
+   Per pixel, with M_k[i] = sums_k[i] / counts[k] and F_k = nframes[k] - first[k]:
+     range    Smin = f32(max(Sref - negativepad, 0)).  On the bright set, i0 = first: D0 = (M[i0+n0] - M[i0]) / n0 with n0 =
+              min(4, F-1); the cut c is the first i >= i0 with M[i+1] - M[i] < slopecut * D0, the last frame where there is none;
+              Smax = min(M[c], 65535) rounded UP to f32 (the sample at the cut stays in range).  The fit works on these two f32
+              values, so that the stored planes are the ones its basis was built on.
+     samples  frames first[k] .. of every set with Smin <= M <= Smax, on the bright set only i <= c; a set with fewer than two
+              takes no part.
+     model    phi(M_k[i]) = a_k + r_k u_i, u_i = 2 (i - first[k]) / (F_k - 1) - 1;  h = (Smax - Smin) / 2, z = (S - Smin) / h - 1,
+              phi(S) = (S - Sref) + sum over l = 2..p of q_l B_l(z), B_l(z) = P_l(z) - P_l(z_ref) - P_l'(z_ref) (z - z_ref): the
+              two constraints hold by construction.  Unweighted least squares for q, a_k, r_k: [1, u] is projected out per set,
+              the (p-1) x (p-1) normal equations are solved by Cholesky, a_k and r_k follow by regression of phi(M) on [1, u].
+     data     (p+1,ny,nx) f32, the series in P_l(z): c_l = q_l (l >= 2), c_1 = h - sum q_l P_l'(z_ref),
+              c_0 = -h z_ref - sum q_l (P_l(z_ref) - P_l'(z_ref) z_ref)
+     smin, smax (ny,nx) f32;  cut (ny,nx) i32: c, a frame index of the bright set's sums
+     pflat    (sets but the dark one, in their order; ny,nx) f32: rate_k - rate_dark in DN_lin/s, rate_k = 2 r_k / ((F_k - 1)
+              tframe); no subtraction without a dark set or where it took no part; 0 for a set that took no part
+     dark_rate (ny,nx) f32: rate_dark (0 without one);  ramperr (nsets,ny,nx) u16: the largest |phi(M) - a_k - r_k u| of the
+              set's used samples, rounded up, at most 65535
+     dq       (ny,nx) u32: REFERENCE_PIXEL (2^31) on the nb border rows and columns; elsewhere NO_LIN_CORR (2^20) where D0 <= 0,
+              Sref is not finite, Sref >= Smax, Smax <= Smin, the degrees of freedom sum (used_k - 2) are below p - 1, or a
+              Cholesky pivot is not positive and finite; else 0.  A flagged pixel carries the identity phi = S - Sref -- c_0 =
+              (Smin + Smax) / 2 - Sref (the quiet NaN 0x7FC00000 where Sref is not finite, Smin then 0), c_1 = h, the rest 0 --
+              and zeros in pflat, dark_rate and ramperr.
+   RIP_EINVAL, before anything is launched, naming the key of the JSON: P_ORDER outside 1..10, SIGN other than 1, SLOPECUT
+   outside (0, 1), more than 8 sets in RAMPS, DARK or the bright set outside the sets (or the same set), a TSTART that leaves
+   fewer than 2 frames, NRAMP outside 1..65536, TFRAME not positive, NEGATIVEPAD negative, rows outside the frame, a NULL pointer. */
+int rip_cal_linearity_fit(rip_ctx *ctx, int nsets, const uint32_t **sums, const int32_t *counts, const int32_t *first,
+                          const int32_t *nframes, const float *sref, int ny, int nx, int y0, int ny_frame, int nb, int p_order, int sign, double tframe,
+                          double slopecut, double negativepad, int bright, int dark, float *data, float *smin, float *smax, uint32_t *dq,
+                          float *pflat, float *dark_rate, uint16_t *ramperr, int32_t *cut);
+
 /* ---- focal-plane overview of a calibration set (utils/fpaplot.py of the reference) ---------- */
 #define RIP_FPA_MAX_PLANES 8
 

@@ -7,7 +7,9 @@ HBM as ``DevArray`` too) and reproduce the scripts' numpy arithmetic bit for bit
 drop-in ``make_dark_file.run``; in front of that, the exposure cubes and slope images that the three converters of
 ``runs/summer2025run`` make of the raw test-stand frames are ``convert_frames.py`` (``frames_to_cube``, ``cube_slopes``, ``convert``,
 ``csrc/rawframes.hip``) with the drop-ins ``convert_dark``, ``convert_flt`` and ``convert_loflt``.  The ``gain`` and ``ipc4d`` files that all of them read come from ``summary_means`` (numpy, on
-the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hip``), with the drop-in ``make_gain_file.run``.
+the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hip``), with the drop-in ``make_gain_file.run``.  The
+``linearitylegendre`` file itself -- the per-frame sums of the flat and dark ramps and the constrained Legendre fit to them -- is
+``linfit.py`` (``RampStack``, ``derive_linearity``, ``csrc/linfit.hip``) with the drop-in ``linearity_run.run``.
 """
 
 import warnings
@@ -210,3 +212,4 @@ def derive_gain_ipc4d(means, good, shape=(pars.nside, pars.nside), nb=NBORDER, i
 
 from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E402, F401
 from .convert_frames import convert, cube_slopes, find_frames, frames_to_cube  # noqa: E402, F401
+from .linfit import RampStack, derive_linearity  # noqa: E402, F401

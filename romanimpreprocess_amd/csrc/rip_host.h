@@ -17,6 +17,8 @@
 //                                    rip_cal_frame_slopes: the cube always in HBM, the slopes by out_location;
 //                                    rip_fpa_bin (fpaplot.hip): dq, every plane and out each by a location of its own;
 //                                    rip_fpa_render: the maps and the picture by theirs, its small tables host arrays
+//                                    rip_cal_frame_sums (linfit.hip): the cube by its location, the sums always in HBM
+//   device pointers                  rip_cal_linearity_fit: the sums of every set, Sref and all result planes (its tables are host arrays)
 //   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
 // Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
