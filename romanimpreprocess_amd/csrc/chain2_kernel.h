@@ -307,6 +307,12 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
     // warm-up and drain steps are clamped INTO that band, so that they touch lines the cell reads anyway instead of 3-5 rows of
     // its neighbours' (each such row costs HBM traffic and buys nothing)
     const int ylo = max(R0 - 2, 0), yhi = min(R1 + 1, ny - 1);
+    // Row steps of both roles: r = R0 - 5 .. R0 + rows_wg - 1, rows_wg + 5 of them for every wave of the workgroup (in quad mode the
+    // wave columns differ in R0 and R1, not in rows_wg), two barriers each.  The last does work: C of row yc = r + 2 <= R1 when
+    // R1 = R0 + rows_wg, and the fit of row R1 - 1.  A step r = R0 + rows_wg would do nothing in either role -- A wants
+    // r + 3 <= R1 + 1, C wants r + 2 <= R1, the fit role emits r < R1 -- and what the step before it reads from the rings at its
+    // end (xnext, dq_next, ...) feeds that step alone.
+    const int r_end = R0 + rows_wg + ((RIP_LEAN2 & 4) ? 0 : 1);
 
     // coefficient loader: raw loads at clamped source positions + validity mask for destination (y, c); `want` is wave-uniform.
     // The nine planes are walked in memory order (plane = 3*(1+dy) + (1+dx)) and land in the reference's term order
@@ -456,7 +462,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
             for (int g = SKIP0 ? 1 : 0; g < G; ++g) rcn[g] = rt[g];   // (SKIP0: group 0's corrections are neither made nor read)
             if constexpr (SKIP0) rcn[0] = 0.0;
         }
-        for (int r = R0 - 5; r <= R0 + rows_wg; ++r, so_c = (so_c == 2) ? 0 : so_c + 1) {
+        for (int r = R0 - 5; r < r_end; ++r, so_c = (so_c == 2) ? 0 : so_c + 1) {
             const RIP_K ChainArgs *ka = &c2_args(kargs)->a;  // S1 copy of the argument block
             const int yi = r + 3, yc = r + 2;
             const bool do_a = (yi >= R0 - 2) && (yi <= R1 + 1);
@@ -783,7 +789,7 @@ __global__ __launch_bounds__((C2Form<G + (G & 1), sizeof(KT) == 8>::threads), (C
         for (int i = 0; i < 5; ++i) kn[i] = f2{0.0f, 0.0f};
 #pragma unroll
         for (int k = 0; k < 9; ++k) kn_d[k] = 0.0;
-        for (int r = R0 - 5; r <= R0 + rows_wg; ++r, o0_r = (o0_r == 2) ? 0 : o0_r + 1) {
+        for (int r = R0 - 5; r < r_end; ++r, o0_r = (o0_r == 2) ? 0 : o0_r + 1) {
             const bool emit = (r >= R0) && (r < R1) && col_ok && (wcol >= 2 || c < 2) && (wcol < wl - 2 || c >= nx - 2);
             const RIP_K C2KernArgs *kf = c2_args(kargs);  // S1 copy of the argument block
             const unsigned rc_ = (unsigned)min(max(r, R0), yhi);   // (rows before R0 are warm-up steps: nothing is emitted there)

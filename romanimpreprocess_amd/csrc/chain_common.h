@@ -34,14 +34,18 @@
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// div_rcp (device_rampfit.h) on a pair of groups
+// div_rcp (device_rampfit.h) on a pair of groups: one correction (short_forms.h)
 __device__ __forceinline__ f2 div_rcp2(f2 a, float b, float rb) {
     const f2 nb = {-b, -b}, rr = {rb, rb};
     const f2 q0 = a * rr;
     const f2 r0 = __builtin_elementwise_fma(nb, q0, a);
     const f2 q1 = __builtin_elementwise_fma(r0, rr, q0);
-    const f2 r1 = __builtin_elementwise_fma(nb, q1, a);
-    return __builtin_elementwise_fma(r1, rr, q1);
+    if constexpr (RIP_LEAN2 & 1) {
+        return q1;
+    } else {
+        const f2 r1 = __builtin_elementwise_fma(nb, q1, a);
+        return __builtin_elementwise_fma(r1, rr, q1);
+    }
 }
 __device__ __forceinline__ bool rcp_safe(float b) {
     const float ab = fabsf(b);

@@ -10,6 +10,7 @@
 // Arithmetic recipes: oracle/refpix.py, oracle/linearity.py, oracle/ipc.py, oracle/rampfit.py, oracle/finish.py.
 #pragma once
 #include "rip_common.h"
+#include "short_forms.h"
 
 // Plan tables (header, variants, weights, difference tables) never change while a kernel runs.  Reading them
 // through the constant address space lets the compiler use scalar loads (s_load, lgkmcnt) for these wave-uniform
@@ -39,11 +40,23 @@ __device__ __forceinline__ float log_f32(float x) {
     return (float)log((double)x);
 }
 
-__device__ __forceinline__ float hypot_f32(float a, float b) {
-    // np.hypot on f32 = libm hypotf = (float)sqrt((double)a*a + (double)b*b)  (glibc flt-32/e_hypotf.c)
+// np.hypot on f32 = libm hypotf = (float)sqrt((double)a*a + (double)b*b)  (glibc flt-32/e_hypotf.c): the expression as it
+// stands, with the compiler's full f64 root (about 20 f64-rate instructions).  The fallback of hypot_f32 and its reference.
+__device__ __forceinline__ float hypot_f32_full(float a, float b) {
     if (isinf(a) || isinf(b)) return INFINITY;
     double da = (double)a, db = (double)b;
     return (float)sqrt(da * da + db * db);
+}
+// The same bits from the short form (short_forms.h: v_rsq_f64, six f64 operations, a guard band around the f32 rounding
+// midpoints) where every lane of the wave has a radicand in 2^-120 .. 2^120 and a root clear of the band; else the full form.
+__device__ __forceinline__ float hypot_f32(float a, float b) {
+    if constexpr (RIP_LEAN2 & 2) {
+        const double T = rip_hypot_radicand(a, b);
+        bool ok;
+        const float h = rip_hypot_short(T, __builtin_amdgcn_rsq(T), ok);
+        if (__all(ok)) return h;
+    }
+    return hypot_f32_full(a, b);
 }
 
 // Short forms of IEEE f32 reciprocal and square root, bit-identical to 1.0f/b and sqrtf(x) for 2^-100 <= |.| <= 2^100
@@ -62,16 +75,16 @@ __device__ __forceinline__ float rip_rcp_mid(float b) {
     const float e = fmaf(-b, r0, 1.0f);
     return fmaf(e, r0, r0);
 }
-// IEEE a/b from the correctly rounded reciprocal rb = 1.0f/b: two Newton corrections with exact (fma)
-// residuals, i.e. the tail of the hardware division macro.  Bit-identical to a/b for finite normal
-// operands and quotients (tools/gpu_checks/divcheck.hip: 1e11 pairs, 0 mismatches); callers fall back
-// to the division operator when b is zero / subnormal / huge.
+// IEEE a/b from the correctly rounded reciprocal rb = 1.0f/b by one correction with an exact (fma) residual: rip_div_rcp1,
+// short_forms.h, with the argument and its range.  Callers fall back to the division operator when b is zero / subnormal / huge.
 __device__ __forceinline__ float div_rcp(float a, float b, float rb) {
-    const float q0 = a * rb;
-    const float r0 = fmaf(-b, q0, a);
-    const float q1 = fmaf(r0, rb, q0);
-    const float r1 = fmaf(-b, q1, a);
-    return fmaf(r1, rb, q1);
+    if constexpr (RIP_LEAN2 & 1) {
+        return rip_div_rcp1(a, b, rb);
+    } else {   // the form before: a second correction, the tail of the hardware division macro
+        const float q1 = rip_div_rcp1(a, b, rb);
+        const float r1 = fmaf(-b, q1, a);
+        return fmaf(r1, rb, q1);
+    }
 }
 __device__ __forceinline__ float rip_sqrt_mid(float x) {
     const float s = __builtin_amdgcn_sqrtf(x);
