@@ -11,7 +11,8 @@
 // The PARAMETERS are the reference's formulas in f64, operation for operation (pinned by goldens made with the reference's own
 // module: tests/golden/pearson_params.npz).  The DEVIATES come from a counter-based generator on the device (Philox-4x32-10
 // keyed by seed, stream and element): the reference draws through scipy.stats on a numpy Generator, whose streams cannot be
-// reproduced here -- the random part is statistically, not bit-wise, comparable (moments tested): PARITY UNPINNED for it.
+// reproduced here: PARITY UNPINNED with those streams.  The recipe itself is pinned: tests/pearson_ref.py restates it in numpy
+// and tests/test_gpu_pearson_deviates.py holds every branch to it draw by draw and to the analytic law of its type.
 // Samplers: gamma by Marsaglia & Tsang (shape < 1 by the U^(1/k) boost), beta and beta prime from two gammas, inverse gamma
 // as scale / gamma, Pearson IV by the rejection method for log-concave densities on the angle variable (Heinrich 2004, sec. 7,
 // the method the reference calls "Devroye"), here always in standard form (a = 1: acceptance ~ 1/4 for every parameter set, so
@@ -169,6 +170,9 @@ __device__ int pearson_classify(double t21, double t31, double t41, double I_in,
         const double d = sqrt(r * r - 4.0 * eps);
         const double q1 = (2.0 - r + d) / 2.0, q2 = (r - 2.0 + d) / 2.0;
         const double alpha = q2 + 1.0, beta = q1 - q2 - 1.0;
+        // next to the type-5 curve r * r - 4 eps rounds below 0 and the shapes are NaN (the reference raises ValueError there:
+        // scipy.stats.betaprime refuses shapes that are not positive)
+        if (!(alpha > 0.0) || !(beta > 0.0)) return PX_NONE;
         const double var1 = alpha * (alpha + beta - 1.0) / ((beta - 2.0) * ((beta - 1.0) * (beta - 1.0)));
         const double scale = sqrt(t21 * I / var1);
         par[0] = alpha, par[1] = beta, par[2] = scale, par[3] = scale * (alpha / (beta - 1.0));

@@ -16,15 +16,21 @@ pytestmark = pytest.mark.gpu
 
 CASES = ["poisson_like", "neg_skew", "beta_prime", "beta_prime_neg", "heavy_tail", "heavy_tail_neg", "symmetric", "light_tail",
          "ramp_fit_weights"]
+# on the curves of types 3 and 5 and to either side of them (tools/make_goldens.py pearson_edges), each with its own intensities
+EDGE_CASES = ["gamma", "gamma_neg", "inv_gamma", "inv_gamma_neg", "inv_gamma_b"]
 
 
-@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("name", CASES + EDGE_CASES)
 def test_types_and_parameters_match_the_reference(name):
-    g = load_golden("pearson_params")
+    g = load_golden("pearson_edges" if name in EDGE_CASES else "pearson_params")
     t21, t31, t41 = g[f"cl_{name}_t"]
-    types, params = dw.classify(t21, t31, t41, g["cl_I"], ctx=gpu_context())
+    types, params = dw.classify(t21, t31, t41, g[f"cl_{name}_I"] if name in EDGE_CASES else g["cl_I"], ctx=gpu_context())
     ref_t, ref_p = g[f"cl_{name}_types"], g[f"cl_{name}_params"]
     np.testing.assert_array_equal(types, ref_t)
+    if name in EDGE_CASES:
+        # type 3 at every intensity, type 5 at the first; type 0 where the reference raises ValueError (next to type 5)
+        assert np.all(ref_t == 3) if name.startswith("gamma") else ref_t[0] == 5
+        assert np.all(ref_t[g[f"cl_{name}_raises"]] == 0)
     # f64 formulas in the reference's order; powers (** 3, ** 1.5) may round differently in the last place
     np.testing.assert_allclose(params, ref_p, rtol=1e-11, atol=1e-300)
 

@@ -633,6 +633,84 @@ def case_pearson():
         out[f"tn_{name}_N"], out[f"tn_{name}_a"], out[f"tn_{name}_W"] = np.array(nb_), np.array(ab_), np.asarray(w)
         out[f"tn_{name}_out"] = np.array(nus, dtype=np.float64)
     # ---- classification + parameters: samplers replaced by recorders
+    classify, restore = _pearson_recorder(dw)
+    try:
+        I = np.concatenate([np.geomspace(1e-3, 1e5, 97), [0.0, -5.0, 0.01, 0.02, 3.0, 1e7]])
+        cases = {
+            "poisson_like": (1.0, 1.0, 1.0),          # kappa = t41 t21 / t31^2 = 1: type 1
+            "neg_skew": (0.8, -0.6, 0.5),             # type 1, negative skew
+            "beta_prime": (1.0, 1.0, 1.7),            # 1.5 < kappa < 1.875: type 6
+            "beta_prime_neg": (0.5, -0.4, 0.55),      # type 6 (kappa = 1.72), negative skew
+            "heavy_tail": (1.0, 0.5, 1.0),            # kappa = 4: type 4
+            "heavy_tail_neg": (2.0, -1.0, 3.0),       # type 4, negative third moment
+            "symmetric": (1.0, 0.0, 2.0),             # beta_1 = 0: type 4 with nu = 0 (Student-like)
+            "light_tail": (1.0, 0.1, -0.5),           # negative excess kurtosis: type 1 near-symmetric beta
+        }
+        tn = tables["K_" + next(iter(READ_PATTERNS))]
+        nus = ft.get_tilde_nus(np.array(tn[0]), np.array(tn[1]), np.asarray(tn[2]))
+        cases["ramp_fit_weights"] = (nus[0] * 3.04, nus[1] * 3.04**2, nus[2] * 3.04**3)   # as gen_noise_image.py:214-217 scales them
+        for name, (t21, t31, t41) in cases.items():
+            out[f"cl_{name}_t"] = np.array([t21, t31, t41])
+            out[f"cl_{name}_types"], out[f"cl_{name}_params"] = classify(t21, t31, t41, I)
+        out["cl_I"] = I
+    finally:
+        restore()
+    save("pearson_params", **out)
+
+
+def case_pearson_edges():
+    """Types 3 and 5 of the Pearson family are the two curves b2 = 1.5 b1 + 3 and b2 = rhs2(b1) of the (b1, b2) plane: the
+    reference reaches them only where its f64 arithmetic lands on them exactly.  Moment ratios and intensities at which it does
+    (and the neighbouring f64 intensities, which fall to either side), through the recorders of ``case_pearson``."""
+    import importlib
+
+    dw = importlib.import_module("romanimpreprocess.L1_to_L2.GalPoisson.draw_with_tilnus")
+    I3 = np.array([0.25, 0.5, 1.0, 2.0, 3.0, 4.0, 5.0, 7.0, 8.0, 16.0, 64.0, 100.0, 1024.0, 1e4, 0.0, -5.0, 0.001])
+
+    def around(x):
+        return np.array([x, np.nextafter(x, -np.inf), np.nextafter(x, np.inf), x - 1.0, x + 1.0])
+
+    cases = {
+        "gamma": ((1.0, 2.0, 6.0), I3),                       # b1 = 4 / I, b2 = 3 + 6 / I: type 3 with shape I
+        "gamma_neg": ((2.0, -2.0, 3.0), I3),                  # b1 = 1 / (2 I), b2 = 3 + 3 / (4 I): type 3, sign -1
+        "inv_gamma": ((1.0, 5.0, 60.0), around(5.0)),         # at 5: b1 = 5, b2 = 15 = rhs2, p = 8
+        "inv_gamma_neg": ((1.0, -5.0, 60.0), around(5.0)),
+        "inv_gamma_b": ((1.0, 1.5, 33.0 / 7.0), around(1.0)),  # at 1: b1 = 2.25, (4 + b1)^1.5 = 15.625
+    }
+    # The unmodified module first, one intensity a call: just past the type-5 curve its type-4 solver finds inner <= 0 and
+    # just before it its type-6 solver takes the root of a negative number (scipy.stats.betaprime then refuses the NaN
+    # shapes); either way it raises ValueError for the whole array.  Those elements are recorded as type 0 with ``raises``
+    # set: what rip_stage_pearson answers there.
+    out = {}
+    for name, ((t21, t31, t41), I) in cases.items():
+        raises = np.zeros(I.shape, bool)
+        for k in range(I.size):
+            try:
+                with np.errstate(all="ignore"):
+                    dw.draw_from_Pearson(t21, t31, t41, I[k:k + 1], rng=np.random.default_rng(1))
+            except ValueError:
+                raises[k] = True
+        out[f"cl_{name}_raises"] = raises
+    classify, restore = _pearson_recorder(dw)
+    try:
+        for name, ((t21, t31, t41), I) in cases.items():
+            out[f"cl_{name}_t"], out[f"cl_{name}_I"] = np.array([t21, t31, t41]), I
+            types, par = np.zeros(I.shape, np.int32), np.zeros(I.shape + (4,))
+            for k in np.nonzero(~out[f"cl_{name}_raises"])[0]:
+                types[k:k + 1], par[k:k + 1] = classify(t21, t31, t41, I[k:k + 1])
+            out[f"cl_{name}_types"], out[f"cl_{name}_params"] = types, par
+    finally:
+        restore()
+    assert np.all(out["cl_gamma_types"] == 3) and np.all(out["cl_gamma_neg_types"] == 3)
+    for name in ("inv_gamma", "inv_gamma_neg", "inv_gamma_b"):
+        assert out[f"cl_{name}_types"][0] == 5, (name, out[f"cl_{name}_types"])
+    save("pearson_edges", **out)
+
+
+def _pearson_recorder(dw):
+    """(classify, restore): ``classify(t21, t31, t41, I)`` runs the reference's ``draw_from_Pearson`` with its per-type samplers
+    replaced by recorders and returns (types int32, params (n, 4)) in the layout of ``rip_stage_pearson``; ``restore()`` puts
+    the module's samplers back."""
     rec = {}
 
     def r1(t21, t31, t41, I, rng=None):
@@ -671,40 +749,24 @@ def case_pearson():
     dw.devroye_acc_rate = lambda nu, a, m: 1.0   # every type-4 element goes to the first recorder, in element order
     dw.random_from_type1, dw.random_from_type3, dw.random_from_type5, dw.random_from_type6 = r1, r3, r5, r6
     dw.pt4_rvs_devroye, dw.pt4_rvs_ar = dev, ar
-    try:
-        I = np.concatenate([np.geomspace(1e-3, 1e5, 97), [0.0, -5.0, 0.01, 0.02, 3.0, 1e7]])
-        cases = {
-            "poisson_like": (1.0, 1.0, 1.0),          # kappa = t41 t21 / t31^2 = 1: type 1
-            "neg_skew": (0.8, -0.6, 0.5),             # type 1, negative skew
-            "beta_prime": (1.0, 1.0, 1.7),            # 1.5 < kappa < 1.875: type 6
-            "beta_prime_neg": (0.5, -0.4, 0.55),      # type 6 (kappa = 1.72), negative skew
-            "heavy_tail": (1.0, 0.5, 1.0),            # kappa = 4: type 4
-            "heavy_tail_neg": (2.0, -1.0, 3.0),       # type 4, negative third moment
-            "symmetric": (1.0, 0.0, 2.0),             # beta_1 = 0: type 4 with nu = 0 (Student-like)
-            "light_tail": (1.0, 0.1, -0.5),           # negative excess kurtosis: type 1 near-symmetric beta
-        }
-        tn = tables["K_" + next(iter(READ_PATTERNS))]
-        nus = ft.get_tilde_nus(np.array(tn[0]), np.array(tn[1]), np.asarray(tn[2]))
-        cases["ramp_fit_weights"] = (nus[0] * 3.04, nus[1] * 3.04**2, nus[2] * 3.04**3)   # as gen_noise_image.py:214-217 scales them
-        for name, (t21, t31, t41) in cases.items():
-            rec.clear()
-            p4.clear()
-            types = dw.draw_from_Pearson(t21, t31, t41, I, rng=np.random.default_rng(1)).astype(np.int32)
-            par = np.zeros(I.shape + (4,))
-            Ic = np.clip(I, 0.01, None)
-            for code, key in ((1, "p1"), (3, "p3"), (5, "p5"), (6, "p6")):
-                if np.any(types == code):
-                    par[types == code] = rec[key]
-            if np.any(types == 4):
-                par[types == 4] = np.array(p4)
-            del Ic
-            out[f"cl_{name}_t"] = np.array([t21, t31, t41])
-            out[f"cl_{name}_types"], out[f"cl_{name}_params"] = types, par
-        out["cl_I"] = I
-    finally:
+
+    def classify(t21, t31, t41, I):
+        rec.clear()
+        p4.clear()
+        types = dw.draw_from_Pearson(t21, t31, t41, I, rng=np.random.default_rng(1)).astype(np.int32)
+        par = np.zeros(I.shape + (4,))
+        for code, key in ((1, "p1"), (3, "p3"), (5, "p5"), (6, "p6")):
+            if np.any(types == code):
+                par[types == code] = rec[key]
+        if np.any(types == 4):
+            par[types == 4] = np.array(p4)
+        return types, par
+
+    def restore():
         for k, v in saved.items():
             setattr(dw, k, v)
-    save("pearson_params", **out)
+
+    return classify, restore
 
 
 def case_noise1f():
@@ -1183,7 +1245,7 @@ CASES = {
     "lin_known_answer": case_lin_known_answer, "multilin": case_multilin, "ipc": case_ipc,
     "weights": case_weights, "rampfit": case_rampfit, "flat": case_flat, "refpix": case_refpix,
     "chain": case_chain, "post": case_post, "harness": case_harness, "il": case_il, "il_example": case_il_example,
-    "pearson": case_pearson, "noise1f": case_noise1f, "l1sim": case_l1sim,
+    "pearson": case_pearson, "pearson_edges": case_pearson_edges, "noise1f": case_noise1f, "l1sim": case_l1sim,
     "refpix_variants": case_refpix_variants, "jump_detect_trunc": case_jump_detect_trunc, "noise_arith": case_noise_arith,
 }
 
