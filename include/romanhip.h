@@ -137,9 +137,12 @@ typedef struct {
        UNPINNED).  flag_saturation != 0: group g >= sat_skip_firstn is SATURATED where data >= threshold in the 3x3
        neighbourhood, sticky for later groups and set on the sat_backup preceding groups; pixeldq |= SATURATED where any
        group is flagged; DO_NOT_USE is set on group 0 when the plan excludes the first group.  groupdq may then be NULL
-       (= zeros); pixeldq is the mask dq. */
+       (= zeros); pixeldq is the mask dq.  A pixel is checked where its threshold is finite (up to FLT_MAX, as np.isfinite
+       has it) and its saturation dq lacks NO_SAT_CHECK; a pixel that is not checked raises no flag whatever its samples
+       (an infinite one included) and still receives its neighbours'. */
     int32_t flag_saturation;
-    int32_t sat_backup;      /* config SATURATION_BACKUP (gen_cal_image.py:172), default 1 */
+    int32_t sat_backup;      /* config SATURATION_BACKUP (gen_cal_image.py:172), default 1.  Any non-negative value is valid; it is
+                                clamped to the group count, from which on larger values mean the same */
     int32_t sat_skip_firstn; /* 1 in the reference's call */
     /* groups that average several reads: a pixel whose LAST reads saturate holds a group value below the threshold, so
        the group is compared with threshold * sat_dilution[g], sat_dilution[g] = mean(read_pattern[g]) / read_pattern[g][-1]

@@ -111,10 +111,11 @@ __global__ __launch_bounds__(256) void sat_exceed_kernel(const T *__restrict__ d
     uint4 sq = {0u, 0u, 0u, 0u};
     if (sat_dq) sq = *reinterpret_cast<const uint4 *>(sat_dq + p);
     const uint32_t sv[4] = {sq.x, sq.y, sq.z, sq.w};
-    float t[4];
+    // checked: the threshold is finite (as np.isfinite has it: up to FLT_MAX) and the pixel is not NO_SAT_CHECK.  The flag masks
+    // the comparison: an infinite sample of an f32 cube would reach any sentinel threshold
+    bool chk[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)  // NaN / inf / NO_SAT_CHECK -> never exceeded
-        t[i] = (!(fabsf(tv[i]) <= 3.4e38f) || (sv[i] & (1u << 21)) != 0) ? INFINITY : tv[i];
+    for (int i = 0; i < 4; ++i) chk[i] = fabsf(tv[i]) <= 3.402823466e+38f && (sv[i] & (1u << 21)) == 0;
     uint64_t m[4] = {0, 0, 0, 0};
     for (int g = skip; g < G; ++g) {
         float d[4];
@@ -129,11 +130,11 @@ __global__ __launch_bounds__(256) void sat_exceed_kernel(const T *__restrict__ d
             const double f = dil.f[g];
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if ((double)d[i] >= (double)t[i] * f) m[i] |= 1ull << g;
+                if (chk[i] && (double)d[i] >= (double)tv[i] * f) m[i] |= 1ull << g;
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (d[i] >= t[i]) m[i] |= 1ull << g;
+                if (chk[i] && d[i] >= tv[i]) m[i] |= 1ull << g;
         }
     }
 #pragma unroll
@@ -161,13 +162,14 @@ __global__ __launch_bounds__(256) void sat_flags_kernel(const uint64_t *__restri
         }
     }
     const uint64_t full = (G >= 64) ? ~0ull : ((1ull << G) - 1ull);
+    const uint64_t from_skip = (skip >= 64) ? 0ull : ~((1ull << skip) - 1ull);  // (skip == G == 64 is allowed: no shift by 64)
     uint64_t sat[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint64_t m = c[i] | c[i + 1] | c[i + 2];
         uint64_t s = m ? (~((m & (~m + 1ull)) - 1ull)) & full : 0ull;  // every group from the first exceeding one on
         for (int b = 0; b < backup; ++b) s |= (s >> 1);
-        sat[i] = s & ~((1ull << skip) - 1ull);  // never the first `skip` groups
+        sat[i] = s & from_skip;  // never the first `skip` groups
     }
     for (int g = 0; g < G; ++g) {
         uint32_t v = gdq_in ? *reinterpret_cast<const uint32_t *>(gdq_in + (size_t)g * npix + p) : 0u;
@@ -216,6 +218,7 @@ int rip_launch_satflag(rip_ctx *ctx, const void *data, int data_dtype, const flo
     if (G < 1 || G > 64 || backup < 0 || skip_firstn < 0 || skip_firstn > G)
         return rip_fail(ctx, RIP_EINVAL, "saturation flagging: bad group / backup / skip arguments");
     if (nx % 4) return rip_fail(ctx, RIP_EINVAL, "saturation flagging: nx=%d is not a multiple of 4", nx);
+    if (backup > G) backup = G;  // any non-negative backup is valid; from the group count on the shifts change nothing
     const size_t npix = (size_t)ny * nx;
     uint64_t *ex = (uint64_t *)rip_ws(ctx, RIP_WS_EXCEED, npix * 8);
     if (!ex) return RIP_ENOMEM;
