@@ -60,7 +60,7 @@ def l2_planes(slope, err_read, err_poisson, pixeldq, nb, float16=False, ctx=None
     specs.update({f"dq_border_ref_pix_{s}": ((ny, nb) if s in ("left", "right") else (nb, nx), np.uint32) for s in SIDES})
     out = empty_arrays(dev, slope, specs)
     ctx.call("rip_stage_l2_planes", slope, err_read, err_poisson, pixeldq, ny, nx, nb, _native.RIP_F16 if float16 else _native.RIP_F32,
-             _native.RIP_DEVICE if dev else _native.RIP_HOST, *(out[k] if out[k].size else None for k in specs))
+             _native.location_of(slope), *(out[k] if out[k].size else None for k in specs))
     if dev:
         ctx.synchronize()
     return out
@@ -81,7 +81,7 @@ def refpix_strips(cube, nb, ctx=None):
     specs = {f"border_ref_pix_{s}": ((ngrp, ny, nb) if s in ("left", "right") else (ngrp, nb, nx), np.float32) for s in SIDES}
     out = empty_arrays(dev, cube, specs)
     ctx.call("rip_stage_l2_refpix_strips", cube, _native.dtype_code(cube), ngrp, ny, nx, nb,
-             _native.RIP_DEVICE if dev else _native.RIP_HOST, *(out[k] if out[k].size else None for k in specs))
+             _native.location_of(cube), *(out[k] if out[k].size else None for k in specs))
     if dev:
         ctx.synchronize()
     return out

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _header
+from .devarray import DevArray
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROMANHIP_LIB") or os.path.join(_HERE, "libromanhip.so")   # the env var: A/B timing of library variants
@@ -196,6 +197,17 @@ def dtype_code(arr):
     if code is None:
         raise TypeError(f"unsupported dtype {arr.dtype}")
     return code
+
+
+def location_of(a):
+    """The ``location`` argument that goes with array ``a``: RIP_DEVICE for a ``DevArray`` or a torch tensor on the GPU, RIP_HOST
+    for a numpy array; TypeError for anything else (a torch tensor in host memory included: ``.numpy()`` it)"""
+    if isinstance(a, np.ndarray):
+        return RIP_HOST
+    t = a.t if isinstance(a, DevArray) else a
+    if hasattr(t, "data_ptr") and getattr(t, "is_cuda", False):
+        return RIP_DEVICE
+    raise TypeError(f"location_of: a numpy array, a DevArray or a tensor on the GPU, got {_describe(a)}")
 
 
 class Context:

@@ -58,7 +58,7 @@ def sigma_clip_mean(stack, sigma=3, maxiters=5, want_count=False, *, sigma_lower
         s = np.ascontiguousarray(s)
         mean = np.empty(shape, np.float32)
         count = np.empty(shape, np.int32) if want_count else None
-    ctx.call("rip_cal_sigma_clip_mean", s, _native.RIP_DEVICE if dev else _native.RIP_HOST, n, npix, npix, lo, hi, maxiters, mean,
+    ctx.call("rip_cal_sigma_clip_mean", s, _native.location_of(s), n, npix, npix, lo, hi, maxiters, mean,
              count)
     return (mean, count) if want_count else mean
 
@@ -84,7 +84,7 @@ def derive_dark_planes(dark1, dark2, dark1_err, dark2_err, cds, nside=None, ctx=
     else:
         planes = [np.ascontiguousarray(a) for a in planes]
         out = [np.empty((ny, nx), np.float32) for _ in range(3)]
-    ctx.call("rip_cal_dark_planes", *planes, _native.RIP_DEVICE if dev[0] else _native.RIP_HOST, ny, nx, width, *out)
+    ctx.call("rip_cal_dark_planes", *planes, _native.location_of(planes[0]), ny, nx, width, *out)
     return tuple(out)
 
 
@@ -141,7 +141,7 @@ class DarkStack:
         nreads, _, width = cube.shape
         if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
             cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
-        self.ctx.call("rip_cal_group_means", cube, _native.RIP_DEVICE if dev else _native.RIP_HOST, nreads, self.ny, width, self.y0,
+        self.ctx.call("rip_cal_group_means", cube, _native.location_of(cube), nreads, self.ny, width, self.y0,
                       self.y1 - self.y0, self.nx, self.reads, self.ng, bool(fits_be16), self.stack, self.capacity, self.n)
         self.n += 1
 

@@ -63,7 +63,7 @@ class RampStack:
             cube = np.ascontiguousarray(cube)
         if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
             cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
-        self.ctx.call("rip_cal_frame_sums", cube, _native.RIP_DEVICE if dev else _native.RIP_HOST, self.nframes, self.ny, cube.shape[2],
+        self.ctx.call("rip_cal_frame_sums", cube, _native.location_of(cube), self.nframes, self.ny, cube.shape[2],
                       self.y0, self.y1 - self.y0, self.nx, 0, bool(fits_be16), self.sums, self.count)
         self.count += 1
 

@@ -528,7 +528,7 @@ def write_fits(path, hdus, ctx=None, chunk_bytes=64 << 20):
                     data.sync()
                 bitpix, bzero = _fits_out_type(data.dtype)
                 width = data.dtype.itemsize
-                where = _native.RIP_DEVICE if on_device else _native.RIP_HOST
+                where = _native.location_of(data)
                 step = chunk // width
                 for first in range(0, data.size, step):
                     if failed:

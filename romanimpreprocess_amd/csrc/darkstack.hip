@@ -199,28 +199,6 @@ __global__ __launch_bounds__(256) void dark_planes_kernel(const float *__restric
     read_noise[i] = (float)((double)cds[q] / root2);
 }
 
-// an array argument in device memory: the caller's pointer, or a scoped copy of the host array
-template <typename T>
-int ds_in(DevBuf<T> &b, const T *src, size_t n, int location, const T *&dev) {
-    if (location == RIP_DEVICE) {
-        dev = src;
-        return RIP_OK;
-    }
-    const int rc = b.upload(src, n);
-    dev = b.p;
-    return rc;
-}
-template <typename T>
-int ds_out(DevBuf<T> &b, T *dst, size_t n, int location, T *&dev) {
-    if (location == RIP_DEVICE || !dst) {
-        dev = dst;
-        return RIP_OK;
-    }
-    const int rc = b.alloc(n);
-    dev = b.p;
-    return rc;
-}
-
 }   // namespace
 
 // ============================================================================================ C-ABI
@@ -229,7 +207,7 @@ int rip_cal_group_means(rip_ctx *ctx, const uint16_t *cube, int location, int nr
                         const int32_t *reads, int ng, int fits_be16, float *stack, int cap, int j) {
     if (ng < 1 || ng > RIP_MAX_GROUPS) return rip_fail(ctx, RIP_EINVAL, "cal_group_means: %d groups (1..%d supported)", ng, RIP_MAX_GROUPS);
     if (!cube || !reads || !stack) return rip_fail(ctx, RIP_EINVAL, "cal_group_means: a required array is NULL");
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_group_means: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_group_means", "location", location)) return rc;
     if (nreads < 1 || ny_file < 1 || nx_file < 1 || ny < 1 || nx < 1 || y0 < 0 || (int64_t)y0 + ny > ny_file)
         return rip_fail(ctx, RIP_EINVAL, "cal_group_means: rows %d+%d of a (%d,%d,%d) cube", y0, ny, nreads, ny_file, nx_file);
     if (nx > nx_file) return rip_fail(ctx, RIP_EINVAL, "cal_group_means: %d columns wanted of a frame of %d", nx, nx_file);
@@ -281,27 +259,24 @@ int rip_cal_sigma_clip_mean(rip_ctx *ctx, const float *stack, int location, int 
     if (n < 1 || n > DS_MAX_PLANES) return rip_fail(ctx, RIP_EINVAL, "cal_sigma_clip_mean: %d planes (1..%d supported)", n, DS_MAX_PLANES);
     if (!stack || !mean || npix < 1 || plane_stride < npix || npix > (size_t)0x7FFFFFFF * 64)
         return rip_fail(ctx, RIP_EINVAL, "cal_sigma_clip_mean: bad arguments (%zu pixels, plane stride %zu)", npix, plane_stride);
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_sigma_clip_mean: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_sigma_clip_mean", "location", location)) return rc;
     if (maxiters < 0 || maxiters > DS_MAX_ITERS)
         return rip_fail(ctx, RIP_EINVAL, "cal_sigma_clip_mean: maxiters %d (0..%d supported)", maxiters, DS_MAX_ITERS);
     if (!(sigma_lower >= 0.0 && sigma_lower <= 1.7976931348623157e308 && sigma_upper >= 0.0 && sigma_upper <= 1.7976931348623157e308))
         return rip_fail(ctx, RIP_EINVAL, "cal_sigma_clip_mean: sigma_lower %g, sigma_upper %g (finite, not negative)", sigma_lower, sigma_upper);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<float> ds(ctx), dm(ctx);
-    DevBuf<int32_t> dc(ctx);
-    const float *s;
-    float *m;
-    int32_t *c;
+    DevArg<float> s, m;
+    DevArg<int32_t> c;
     int rc;
-    if ((rc = ds_in(ds, stack, (size_t)(n - 1) * plane_stride + npix, location, s)) || (rc = ds_out(dm, mean, npix, location, m)) ||
-        (rc = ds_out(dc, count, npix, location, c)))
+    if ((rc = s.in(ctx, stack, (size_t)(n - 1) * plane_stride + npix, location)) || (rc = m.out(ctx, mean, npix, location)) ||
+        (rc = c.out(ctx, count, npix, location)))
         return rc;
     const size_t bytes = (size_t)n * 64 * sizeof(uint32_t);
     if ((rc = with_lds(ctx, sigma_clip_kernel, bytes))) return rc;
-    hipLaunchKernelGGL(sigma_clip_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), bytes, ctx->stream, s, n, plane_stride, npix,
-                       sigma_lower, sigma_upper, maxiters, m, c);
+    hipLaunchKernelGGL(sigma_clip_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), bytes, ctx->stream, s.p, n, plane_stride, npix,
+                       sigma_lower, sigma_upper, maxiters, m.p, c.p);
     RIP_HIP(ctx, hipGetLastError());
-    if (location == RIP_HOST && ((rc = dm.download(mean, npix)) || (count && (rc = dc.download(count, npix))))) return rc;
+    if ((rc = m.download()) || (rc = c.download())) return rc;
     return dev_sync(ctx);
 }
 
@@ -311,23 +286,18 @@ int rip_cal_dark_planes(rip_ctx *ctx, const float *dark1, const float *dark2, co
     if (!dark1 || !dark2 || !dark1_err || !dark2_err || !cds || !dark_slope || !dark_slope_err || !read_noise || ny < 1 || nx < 1 ||
         row_stride < (size_t)nx)
         return rip_fail(ctx, RIP_EINVAL, "cal_dark_planes: bad arguments (%d x %d, row stride %zu)", ny, nx, row_stride);
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_dark_planes: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_dark_planes", "location", location)) return rc;
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nin = (size_t)(ny - 1) * row_stride + nx, n = (size_t)ny * nx;
-    DevBuf<float> b1(ctx), b2(ctx), e1(ctx), e2(ctx), bc(ctx), o1(ctx), o2(ctx), o3(ctx);
-    const float *d1, *d2, *x1, *x2, *dc;
-    float *s, *se, *rn;
+    DevArg<float> d1, d2, x1, x2, dc, s, se, rn;
     int rc;
-    if ((rc = ds_in(b1, dark1, nin, location, d1)) || (rc = ds_in(b2, dark2, nin, location, d2)) ||
-        (rc = ds_in(e1, dark1_err, nin, location, x1)) || (rc = ds_in(e2, dark2_err, nin, location, x2)) ||
-        (rc = ds_in(bc, cds, nin, location, dc)) || (rc = ds_out(o1, dark_slope, n, location, s)) ||
-        (rc = ds_out(o2, dark_slope_err, n, location, se)) || (rc = ds_out(o3, read_noise, n, location, rn)))
+    if ((rc = d1.in(ctx, dark1, nin, location)) || (rc = d2.in(ctx, dark2, nin, location)) || (rc = x1.in(ctx, dark1_err, nin, location)) ||
+        (rc = x2.in(ctx, dark2_err, nin, location)) || (rc = dc.in(ctx, cds, nin, location)) || (rc = s.out(ctx, dark_slope, n, location)) ||
+        (rc = se.out(ctx, dark_slope_err, n, location)) || (rc = rn.out(ctx, read_noise, n, location)))
         return rc;
-    hipLaunchKernelGGL(dark_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d1, d2, x1, x2, dc, row_stride, ny,
-                       nx, sqrt(2.0), s, se, rn);
+    hipLaunchKernelGGL(dark_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d1.p, d2.p, x1.p, x2.p, dc.p,
+                       row_stride, ny, nx, sqrt(2.0), s.p, se.p, rn.p);
     RIP_HIP(ctx, hipGetLastError());
-    if (location == RIP_HOST && ((rc = o1.download(dark_slope, n)) || (rc = o2.download(dark_slope_err, n)) ||
-                                 (rc = o3.download(read_noise, n))))
-        return rc;
+    if ((rc = s.download()) || (rc = se.download()) || (rc = rn.download())) return rc;
     return dev_sync(ctx);
 }

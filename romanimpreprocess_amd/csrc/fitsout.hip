@@ -139,10 +139,6 @@ int launch_fits_encode(rip_ctx *ctx, const void *src, int w, bool flip, size_t n
     return RIP_OK;
 }
 
-bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
 }   // namespace
 
 extern "C" int rip_stage_fits_encode(rip_ctx *ctx, const void *src, int bitpix, int flip_sign, size_t n, int src_location,
@@ -154,8 +150,10 @@ extern "C" int rip_stage_fits_encode(rip_ctx *ctx, const void *src, int bitpix, 
     if (n == 0) return rip_fail(ctx, RIP_EINVAL, "fits_encode: n is 0");
     if (!src) return rip_fail(ctx, RIP_EINVAL, "fits_encode: src is NULL");
     if (!dst) return rip_fail(ctx, RIP_EINVAL, "fits_encode: dst is NULL");
-    if (src_location != RIP_HOST && src_location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "fits_encode: src_location %d", src_location);
-    if (dst_location != RIP_HOST && dst_location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "fits_encode: dst_location %d", dst_location);
+    int rc;
+    if ((rc = rip_check_location(ctx, "fits_encode", "src_location", src_location)) ||
+        (rc = rip_check_location(ctx, "fits_encode", "dst_location", dst_location)))
+        return rc;
     const int w = (bitpix < 0 ? -bitpix : bitpix) / 8;
     if (n > ((size_t)1 << 60)) return rip_fail(ctx, RIP_EINVAL, "fits_encode: n = %zu samples", n);
     const size_t bytes = n * (size_t)w;
@@ -164,41 +162,26 @@ extern "C" int rip_stage_fits_encode(rip_ctx *ctx, const void *src, int bitpix, 
     if (mask && src_location == dst_location && ranges_meet(mask, n, dst, bytes))
         return rip_fail(ctx, RIP_EINVAL, "fits_encode: dst overlaps mask");
     // device memory is used where it is: the kernel's loads and stores are sample-wide at least
-    if (src_location == RIP_DEVICE && ((uintptr_t)src % (uintptr_t)w))
+    if (src_location == RIP_DEVICE && !aligned(src, w))
         return rip_fail(ctx, RIP_EINVAL, "fits_encode: the device pointer src is not aligned to the %d-byte sample", w);
-    if (dst_location == RIP_DEVICE && ((uintptr_t)dst % (uintptr_t)w))
+    if (dst_location == RIP_DEVICE && !aligned(dst, w))
         return rip_fail(ctx, RIP_EINVAL, "fits_encode: the device pointer dst is not aligned to the %d-byte sample", w);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const bool sense = mask_sense != 0;
-    if (src_location == RIP_DEVICE && dst_location == RIP_DEVICE) {
-        ctx->stream_dirty = true;   // (the next overlapped rip_calibrate orders its pre-pass behind this work)
-        return launch_fits_encode(ctx, src, w, flip_sign != 0, n, mask, sense, fill, dst);
-    }
-    // a host side: the samples are encoded in a scoped device buffer (a host source: in place in its copy; a host destination of
-    // a device source: into a buffer of its own) and the call returns when the bytes have arrived
-    DevBuf<unsigned char> in(ctx), out(ctx);
-    DevBuf<uint8_t> m(ctx);
+    const bool queued = src_location == RIP_DEVICE && dst_location == RIP_DEVICE;   // device to device: not waited for
+    if (queued) ctx->stream_dirty = true;   // (the next overlapped rip_calibrate orders its pre-pass behind this work)
+    // a host source is encoded in place in dst's device memory (dst itself, or the scoped buffer of a host dst); the call
+    // returns when the bytes have arrived
+    DevArg<unsigned char> d;
+    DevArg<uint8_t> m;
+    if ((rc = d.out(ctx, (unsigned char *)dst, bytes, dst_location))) return rc;
     const void *s = src;
-    const uint8_t *mk = mask;
-    void *d = dst;
-    int rc;
     if (src_location == RIP_HOST) {
-        if (dst_location == RIP_DEVICE) {   // straight into dst, encoded there in place
-            RIP_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream));
-            s = dst;
-        } else {
-            if ((rc = in.upload(src, bytes))) return rc;
-            s = d = in.p;
-        }
-        if (mask) {
-            if ((rc = m.upload(mask, n))) return rc;
-            mk = m.p;
-        }
-    } else {
-        if ((rc = out.alloc(bytes))) return rc;
-        d = out.p;
+        RIP_HIP(ctx, hipMemcpyAsync(d.p, src, bytes, hipMemcpyDefault, ctx->stream));
+        s = d.p;
     }
-    if ((rc = launch_fits_encode(ctx, s, w, flip_sign != 0, n, mk, sense, fill, d))) return rc;
-    if (dst_location == RIP_HOST) RIP_HIP(ctx, hipMemcpyAsync(dst, d, bytes, hipMemcpyDefault, ctx->stream));
-    return dev_sync(ctx);
+    if ((rc = m.in(ctx, mask, n, src_location)) || (rc = launch_fits_encode(ctx, s, w, flip_sign != 0, n, m.p, sense, fill, d.p)) ||
+        (rc = d.download()))
+        return rc;
+    return queued ? RIP_OK : dev_sync(ctx);
 }

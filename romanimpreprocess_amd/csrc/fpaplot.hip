@@ -287,8 +287,6 @@ __global__ __launch_bounds__(256) void fpa_render_kernel(FrLayout L, const doubl
     o[2] = b;
 }
 
-bool bad_location(int loc) { return loc != RIP_HOST && loc != RIP_DEVICE; }
-
 }  // namespace
 
 // ============================================================================================ C-ABI
@@ -300,12 +298,15 @@ int rip_fpa_bin(rip_ctx *ctx, const uint32_t *dq, int dq_location, const uint8_t
         return rip_fail(ctx, RIP_EINVAL, "fpa_bin: n1 %d is not a power of two that divides nside %d", n1, nside);
     if (nplanes < 1 || nplanes > RIP_FPA_MAX_PLANES)
         return rip_fail(ctx, RIP_EINVAL, "fpa_bin: %d planes, outside 1..%d", nplanes, RIP_FPA_MAX_PLANES);
-    if (bad_location(dq_location) || bad_location(out_location)) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: unknown dq or out location");
+    int rc;
+    if ((rc = rip_check_location(ctx, "fpa_bin", "dq_location", dq_location)) ||
+        (rc = rip_check_location(ctx, "fpa_bin", "out_location", out_location)))
+        return rc;
     for (int i = 0; i < nplanes; ++i) {
         if (!planes[i]) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: plane %d is NULL", i);
         if (dtypes[i] != RIP_F32 && dtypes[i] != RIP_F64)
             return rip_fail(ctx, RIP_EINVAL, "fpa_bin: plane %d has dtype %d, neither RIP_F32 nor RIP_F64", i, dtypes[i]);
-        if (bad_location(locations[i])) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: plane %d has an unknown location", i);
+        if (!rip_is_location(locations[i])) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: plane %d has the location %d", i, locations[i]);
         const int m = sides[i];
         if (m < 1 || m > nside) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: plane %d of side %d does not fit the frame of side %d", i, m, nside);
         if ((nside - m) % 2)
@@ -323,33 +324,20 @@ int rip_fpa_bin(rip_ctx *ctx, const uint32_t *dq, int dq_location, const uint8_t
     if (nty > 65535) return rip_fail(ctx, RIP_EINVAL, "fpa_bin: a frame of side %d is too large", nside);
     const int direct = (FB_TH % s == 0 && FB_TW % s == 0) ? 1 : 0;
     const int fstride = (FB_TW - 1) / s + 2, fmax = ((FB_TH - 1) / s + 2) * fstride;   // the most bins a tile can touch
-    DevBuf<uint32_t> ddq(ctx);
-    DevBuf<char> dpl[RIP_FPA_MAX_PLANES] = {DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx),
-                                            DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx)};
+    DevArg<uint32_t> q;
+    DevArg<char> dpl[RIP_FPA_MAX_PLANES];
     DevBuf<FbPart> part(ctx);
-    DevBuf<double> o(ctx);
-    int rc;
-    const uint32_t *q = dq;
-    if (dq && dq_location == RIP_HOST) {
-        if ((rc = ddq.upload(dq, npix))) return rc;
-        q = ddq.p;
-    }
+    DevArg<double> o;
+    if ((rc = q.in(ctx, dq, npix, dq_location))) return rc;
     FbPlanes pl{};
     for (int i = 0; i < nplanes; ++i) {
         pl.f64[i] = dtypes[i] == RIP_F64;
         pl.side[i] = sides[i];
-        pl.data[i] = planes[i];
-        if (locations[i] == RIP_HOST) {
-            if ((rc = dpl[i].upload(planes[i], (size_t)pl.side[i] * pl.side[i] * dsize(dtypes[i])))) return rc;
-            pl.data[i] = dpl[i].p;
-        }
+        if ((rc = dpl[i].in(ctx, (const char *)planes[i], (size_t)pl.side[i] * pl.side[i] * dsize(dtypes[i]), locations[i]))) return rc;
+        pl.data[i] = dpl[i].p;
     }
     if (!direct && (rc = part.alloc((size_t)ntx * nty * fmax * nplanes))) return rc;
-    double *dout = out;
-    if (out_location == RIP_HOST) {
-        if ((rc = o.alloc(nout))) return rc;
-        dout = o.p;
-    }
+    if ((rc = o.out(ctx, out, nout, out_location))) return rc;
     int steps = 0;   // 2^steps >= the longest run of lanes in one bin column
     while ((1 << steps) < (s < FB_TW ? s : FB_TW)) ++steps;
     // as many planes between two barriers as 32 KB of LDS hold: all 8 from s = 8 on, one at s = 1
@@ -357,15 +345,15 @@ int rip_fpa_bin(rip_ctx *ctx, const uint32_t *dq, int dq_location, const uint8_t
     const int group = (int)std::max<size_t>(1, std::min<size_t>(nplanes, 32768 / per_plane));
     const size_t lds = group * per_plane;
     if ((rc = with_lds(ctx, fpa_bin_kernel, lds))) return rc;
-    hipLaunchKernelGGL(fpa_bin_kernel, dim3(ntx, nty), dim3(256), lds, ctx->stream, q, g, pl, nplanes, nside, n1, s, direct, fmax, fstride,
-                       steps, group, part.p, dout);
+    hipLaunchKernelGGL(fpa_bin_kernel, dim3(ntx, nty), dim3(256), lds, ctx->stream, q.p, g, pl, nplanes, nside, n1, s, direct, fmax, fstride,
+                       steps, group, part.p, o.p);
     RIP_HIP(ctx, hipGetLastError());
     if (!direct) {
         hipLaunchKernelGGL(fpa_finish_kernel, dim3(n1 * n1, nplanes), dim3(256), 0, ctx->stream, part.p, nplanes, nside, n1, s, ntx, fmax,
-                           fstride, dout);
+                           fstride, o.p);
         RIP_HIP(ctx, hipGetLastError());
     }
-    if (out_location == RIP_HOST && (rc = o.download(out, nout))) return rc;
+    if ((rc = o.download())) return rc;
     return dev_sync(ctx);
 }
 
@@ -379,7 +367,10 @@ int rip_fpa_render(rip_ctx *ctx, int n1, int nsca, int npanel, int nw, int gap, 
     } l{n1, nsca, npanel, nw, gap, ny, nx, (n1 > 64 ? n1 : 64) / 64, nstamps};
     if (l.n1 < 1 || l.nsca < 1 || l.npanel < 1 || l.nw < 1 || l.gap < 0 || l.ny < 1 || l.nx < 1 || l.sc < 1 || l.nstamps < 0)
         return rip_fail(ctx, RIP_EINVAL, "fpa_render: a count or size of the layout is below 1");
-    if (bad_location(maps_location) || bad_location(out_location)) return rip_fail(ctx, RIP_EINVAL, "fpa_render: unknown maps or out location");
+    int rc;
+    if ((rc = rip_check_location(ctx, "fpa_render", "maps_location", maps_location)) ||
+        (rc = rip_check_location(ctx, "fpa_render", "out_location", out_location)))
+        return rc;
     if (l.nstamps > 0 && (!glyphs || !stamps)) return rip_fail(ctx, RIP_EINVAL, "fpa_render: %d stamps without a glyph table", l.nstamps);
     for (int k = 0; k < l.nsca; ++k) {
         const int py = sca_pos[2 * k], px = sca_pos[2 * k + 1];
@@ -424,28 +415,21 @@ int rip_fpa_render(rip_ctx *ctx, int n1, int nsca, int npanel, int nw, int gap, 
 
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nmaps = (size_t)l.npanel * l.nsca * l.n1 * l.n1, nout = (size_t)NYl * NXl * 3;
-    DevBuf<double> dm(ctx), dlo(ctx), dhi(ctx);
-    DevBuf<uint8_t> dpres(ctx), dscale(ctx), dtab(ctx), dgl(ctx), o(ctx);
+    DevArg<double> m;
+    DevArg<uint8_t> o;
+    DevBuf<double> dlo(ctx), dhi(ctx);
+    DevBuf<uint8_t> dpres(ctx), dscale(ctx), dtab(ctx), dgl(ctx);
     DevBuf<int32_t> dpos(ctx), dst(ctx), dat(ctx);
-    int rc;
-    const double *m = maps;
-    if (maps_location == RIP_HOST) {
-        if ((rc = dm.upload(maps, nmaps))) return rc;
-        m = dm.p;
-    }
+    if ((rc = m.in(ctx, maps, nmaps, maps_location))) return rc;
     if ((rc = dlo.upload(vmin, l.npanel)) || (rc = dhi.upload(vmax, l.npanel)) || (rc = dpres.upload(present, (size_t)l.npanel * l.nsca)) ||
         (rc = dscale.upload(scale, l.npanel)) || (rc = dtab.upload(table, 768)) || (rc = dpos.upload(sca_pos, (size_t)2 * l.nsca)) ||
         (rc = l.nstamps ? dst.upload(sorted.data(), sorted.size()) : dst.alloc(1)) || (rc = dat.upload(at.data(), at.size())))
         return rc;
     if (glyphs && (rc = dgl.upload(glyphs, 256 * 12 * 6))) return rc;
-    uint8_t *dout = out;
-    if (out_location == RIP_HOST) {
-        if ((rc = o.alloc(nout))) return rc;
-        dout = o.p;
-    }
-    hipLaunchKernelGGL(fpa_render_kernel, dim3((L.NX + 255) / 256, L.NY), dim3(256), 0, ctx->stream, L, m, dpres.p, dpos.p, dlo.p, dhi.p,
-                       dscale.p, dtab.p, dgl.p, dst.p, dat.p, dout);
+    if ((rc = o.out(ctx, out, nout, out_location))) return rc;
+    hipLaunchKernelGGL(fpa_render_kernel, dim3((L.NX + 255) / 256, L.NY), dim3(256), 0, ctx->stream, L, m.p, dpres.p, dpos.p, dlo.p, dhi.p,
+                       dscale.p, dtab.p, dgl.p, dst.p, dat.p, o.p);
     RIP_HIP(ctx, hipGetLastError());
-    if (out_location == RIP_HOST && (rc = o.download(out, nout))) return rc;
+    if ((rc = o.download())) return rc;
     return dev_sync(ctx);   // the tables above are host vectors of this call: their copies are done before it returns
 }

@@ -204,7 +204,7 @@ int rip_cal_gain_ipc4d(rip_ctx *ctx, const double *means, const uint8_t *good, i
         return rip_fail(ctx, RIP_EINVAL, "cal_gain_ipc4d: kernel dtype code %d is neither RIP_F32 nor RIP_F64", kernel_dtype);
     if (!gain && !gain_dq && !kernel && !kernel_dq) return rip_fail(ctx, RIP_EINVAL, "cal_gain_ipc4d: every output is NULL");
     if (!means || !good) return rip_fail(ctx, RIP_EINVAL, "cal_gain_ipc4d: a table is NULL");
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_gain_ipc4d: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_gain_ipc4d", "location", location)) return rc;
     const int ry = ny / nsy, rx = nx / nsx, nya = ny - 2 * nb, nxa = nx - 2 * nb;
     const size_t ntab = (size_t)nsy * nsx, npix = (size_t)ny * nx, na = (size_t)nya * nxa, ksize = dsize(kernel_dtype);
     if (npix / GF_THREADS + (size_t)ny > (size_t)INT_MAX / 2)   // one workgroup per row segment, counted in 32 bits
@@ -214,47 +214,42 @@ int rip_cal_gain_ipc4d(rip_ctx *ctx, const double *means, const uint8_t *good, i
     // the tables as the script's .astype(np.float32) leaves them: g, aH, aV, aD
     std::vector<float> t32(4 * ntab);
     for (size_t i = 0; i < 4 * ntab; ++i) t32[i] = (float)means[i];
-    DevBuf<float> dt(ctx), dgain(ctx);
+    DevBuf<float> dt(ctx);
     DevBuf<uint8_t> dgood(ctx);
-    DevBuf<uint32_t> dgq(ctx), dkq(ctx);
-    DevBuf<char> dk(ctx);
+    DevArg<float> pg;
+    DevArg<uint32_t> pgq, pkq;
+    DevArg<char> pk;
     int rc;
     if ((rc = dt.upload(t32.data(), 4 * ntab)) || (rc = dgood.upload(good, ntab))) return rc;
-    const bool host = location == RIP_HOST;
-    if (host && ((gain && (rc = dgain.alloc(npix))) || (gain_dq && (rc = dgq.alloc(npix))) || (kernel && (rc = dk.alloc(9 * na * ksize))) ||
-                 (kernel_dq && (rc = dkq.alloc(na)))))
+    if ((rc = pg.out(ctx, gain, npix, location)) || (rc = pgq.out(ctx, gain_dq, npix, location)) ||
+        (rc = pk.out(ctx, (char *)kernel, 9 * na * ksize, location)) || (rc = pkq.out(ctx, kernel_dq, na, location)))
         return rc;
-    float *pg = gain ? (host ? dgain.p : gain) : nullptr;
-    uint32_t *pgq = gain_dq ? (host ? dgq.p : gain_dq) : nullptr, *pkq = kernel_dq ? (host ? dkq.p : kernel_dq) : nullptr;
-    void *pk = kernel ? (host ? (void *)dk.p : kernel) : nullptr;
 
-    if (pk) {
-        const int v = store_width(pk, nxa, ksize);
+    if (pk.p) {
+        const int v = store_width(pk.p, nxa, ksize);
         if (kernel_dtype == RIP_F64) {
-            if (v == 2) launch_ipc4d<double, 2>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk);
-            else launch_ipc4d<double, 1>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk);
+            if (v == 2) launch_ipc4d<double, 2>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk.p);
+            else launch_ipc4d<double, 1>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk.p);
         } else {
-            if (v == 4) launch_ipc4d<float, 4>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk);
-            else if (v == 2) launch_ipc4d<float, 2>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk);
-            else launch_ipc4d<float, 1>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk);
+            if (v == 4) launch_ipc4d<float, 4>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk.p);
+            else if (v == 2) launch_ipc4d<float, 2>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk.p);
+            else launch_ipc4d<float, 1>(ctx, dt.p, ntab, nsy, nsx, ry, rx, nb, nya, nxa, pk.p);
         }
         RIP_HIP(ctx, hipGetLastError());
     }
-    if (pg || pgq) {
-        const bool wide = nx % 4 == 0 && (uintptr_t)pg % 16 == 0 && (uintptr_t)pgq % 16 == 0;   // a null plane does not count
+    if (pg.p || pgq.p) {
+        const bool wide = nx % 4 == 0 && aligned(pg.p, 16) && aligned(pgq.p, 16);   // a null plane does not count
         const int V = wide ? 4 : 1, nbx = (nx / V + GF_THREADS - 1) / GF_THREADS;
         if (wide)
             hipLaunchKernelGGL(gainfile_gain_kernel<4>, dim3((unsigned)nbx * (unsigned)ny), dim3(GF_THREADS), 0, ctx->stream, dt.p, dgood.p,
-                               nsx, ry, rx, nb, ny, nx, nbx, pg, pgq);
+                               nsx, ry, rx, nb, ny, nx, nbx, pg.p, pgq.p);
         else
             hipLaunchKernelGGL(gainfile_gain_kernel<1>, dim3((unsigned)nbx * (unsigned)ny), dim3(GF_THREADS), 0, ctx->stream, dt.p, dgood.p,
-                               nsx, ry, rx, nb, ny, nx, nbx, pg, pgq);
+                               nsx, ry, rx, nb, ny, nx, nbx, pg.p, pgq.p);
         RIP_HIP(ctx, hipGetLastError());
     }
     // the ipc4d flags: the script convolves its bad-pixel map with an all-zero 3 x 3 kernel, so every pixel comes out good
-    if (pkq) RIP_HIP(ctx, hipMemsetAsync(pkq, 0, na * sizeof(uint32_t), ctx->stream));
-    if (host && ((gain && (rc = dgain.download(gain, npix))) || (gain_dq && (rc = dgq.download(gain_dq, npix))) ||
-                 (kernel && (rc = dk.download(kernel, 9 * na * ksize))) || (kernel_dq && (rc = dkq.download(kernel_dq, na)))))
-        return rc;
+    if (pkq.p) RIP_HIP(ctx, hipMemsetAsync(pkq.p, 0, na * sizeof(uint32_t), ctx->stream));
+    if ((rc = pg.download()) || (rc = pgq.download()) || (rc = pk.download()) || (rc = pkq.download())) return rc;
     return dev_sync(ctx);
 }

@@ -166,8 +166,6 @@ int launch_strips(rip_ctx *ctx, const void *src, int np, int ny, int nx, int nb,
     return launch_strip<TI, TO>(ctx, src, np, ny, nx, 0, nb, 0, nx, bottom);
 }
 
-bool aligned(const void *p, uintptr_t to) { return ((uintptr_t)p % to) == 0; }
-
 // device pointers
 int launch_l2_planes(rip_ctx *ctx, const L2Planes &a, int ny, int nx, int nb, bool f16) {
     const int nya = ny - 2 * nb, nxa = nx - 2 * nb;
@@ -199,10 +197,6 @@ int launch_l2_planes(rip_ctx *ctx, const L2Planes &a, int ny, int nx, int nb, bo
     return RIP_OK;
 }
 
-bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
-    return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
 struct Out {   // an output of an entry: the caller's pointer, its bytes, its element size, its name
     void *p;
     size_t bytes;
@@ -222,7 +216,7 @@ extern "C" int rip_stage_l2_planes(rip_ctx *ctx, const float *slope, const float
     if (2 * (long long)nb >= ny || 2 * (long long)nb >= nx)
         return rip_fail(ctx, RIP_EINVAL, "l2_planes: a border of %d leaves no active region in a %d x %d frame", nb, ny, nx);
     if (var_dtype != RIP_F32 && var_dtype != RIP_F16) return rip_fail(ctx, RIP_EINVAL, "l2_planes: var_dtype %d", var_dtype);
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "l2_planes: location %d", location);
+    if (const int rc = rip_check_location(ctx, "l2_planes", "location", location)) return rc;
     const bool f16 = var_dtype == RIP_F16;
     const size_t n = (size_t)ny * nx, na = (size_t)(ny - 2 * nb) * (size_t)(nx - 2 * nb), vw = f16 ? 2 : 4;
     const size_t side = (size_t)ny * nb * 4, edge = (size_t)nb * nx * 4;
@@ -240,32 +234,23 @@ extern "C" int rip_stage_l2_planes(rip_ctx *ctx, const float *slope, const float
         for (const void *in : ins)
             if (!aligned(in, 4)) return rip_fail(ctx, RIP_EINVAL, "l2_planes: a device input pointer is not aligned to its 4-byte element");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
+    if (location == RIP_DEVICE) ctx->stream_dirty = true;   // (the next overlapped rip_calibrate orders its pre-pass behind this work)
+    DevArg<float> d_in[3];
+    DevArg<uint32_t> d_pdq;
+    DevArg<char> d[9];
     int rc;
-    if (location == RIP_DEVICE) {
-        ctx->stream_dirty = true;   // (the next overlapped rip_calibrate orders its pre-pass behind this work)
-        const L2Planes a = {reinterpret_cast<const uint32_t *>(slope), err_read, err_poisson, pixeldq,
-                            reinterpret_cast<uint32_t *>(data), dq, var_rnoise, var_poisson, err};
-        if ((rc = launch_l2_planes(ctx, a, ny, nx, nb, f16))) return rc;
-        return launch_strips<uint32_t, uint32_t>(ctx, pixeldq, 1, ny, nx, nb, dq_left, dq_right, dq_top, dq_bottom);
-    }
-    // host arrays: the inputs into scoped device buffers, every wanted output made in one of its own and copied back
-    DevBuf<float> d_in[3] = {DevBuf<float>(ctx), DevBuf<float>(ctx), DevBuf<float>(ctx)};
-    DevBuf<uint32_t> d_pdq(ctx);
-    DevBuf<char> d_out[9] = {DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx),
-                             DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx)};
-    if ((rc = d_in[0].upload(slope, n)) || (rc = d_in[1].upload(err_read, n)) || (rc = d_in[2].upload(err_poisson, n)) ||
-        (rc = d_pdq.upload(pixeldq, n)))
+    if ((rc = d_in[0].in(ctx, slope, n, location)) || (rc = d_in[1].in(ctx, err_read, n, location)) ||
+        (rc = d_in[2].in(ctx, err_poisson, n, location)) || (rc = d_pdq.in(ctx, pixeldq, n, location)))
         return rc;
     for (int k = 0; k < 9; ++k)
-        if (outs[k].p && (rc = d_out[k].alloc(outs[k].bytes))) return rc;
-    const L2Planes a = {reinterpret_cast<const uint32_t *>(d_in[0].p), d_in[1].p, d_in[2].p, d_pdq.p,
-                        reinterpret_cast<uint32_t *>(d_out[0].p), reinterpret_cast<uint32_t *>(d_out[1].p), d_out[2].p, d_out[3].p,
-                        d_out[4].p};
+        if ((rc = d[k].out(ctx, (char *)outs[k].p, outs[k].bytes, location))) return rc;
+    const L2Planes a = {reinterpret_cast<const uint32_t *>(d_in[0].p), d_in[1].p, d_in[2].p, d_pdq.p, reinterpret_cast<uint32_t *>(d[0].p),
+                        reinterpret_cast<uint32_t *>(d[1].p), d[2].p, d[3].p, d[4].p};
     if ((rc = launch_l2_planes(ctx, a, ny, nx, nb, f16))) return rc;
-    if ((rc = launch_strips<uint32_t, uint32_t>(ctx, d_pdq.p, 1, ny, nx, nb, d_out[5].p, d_out[6].p, d_out[7].p, d_out[8].p))) return rc;
+    if ((rc = launch_strips<uint32_t, uint32_t>(ctx, d_pdq.p, 1, ny, nx, nb, d[5].p, d[6].p, d[7].p, d[8].p))) return rc;
     for (int k = 0; k < 9; ++k)
-        if (outs[k].p && outs[k].bytes && (rc = d_out[k].download(outs[k].p, outs[k].bytes))) return rc;
-    return dev_sync(ctx);
+        if ((rc = d[k].download())) return rc;
+    return location == RIP_DEVICE ? RIP_OK : dev_sync(ctx);   // device pointers: queued, not waited for
 }
 
 extern "C" int rip_stage_l2_refpix_strips(rip_ctx *ctx, const void *cube, int cube_dtype, int ngrp, int ny, int nx, int nb,
@@ -274,7 +259,7 @@ extern "C" int rip_stage_l2_refpix_strips(rip_ctx *ctx, const void *cube, int cu
     if (ngrp < 1 || ny < 1 || nx < 1) return rip_fail(ctx, RIP_EINVAL, "l2_refpix_strips: cube %d x %d x %d", ngrp, ny, nx);
     if (nb < 0 || nb > ny || nb > nx) return rip_fail(ctx, RIP_EINVAL, "l2_refpix_strips: nb = %d in a %d x %d frame", nb, ny, nx);
     if (cube_dtype != RIP_U16 && cube_dtype != RIP_F32) return rip_fail(ctx, RIP_EINVAL, "l2_refpix_strips: cube_dtype %d", cube_dtype);
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "l2_refpix_strips: location %d", location);
+    if (const int rc = rip_check_location(ctx, "l2_refpix_strips", "location", location)) return rc;
     const bool u16 = cube_dtype == RIP_U16;
     const size_t cw = u16 ? 2 : 4, n = (size_t)ngrp * ny * nx;
     const size_t side = (size_t)ngrp * ny * nb * 4, edge = (size_t)ngrp * nb * nx * 4;
@@ -287,21 +272,16 @@ extern "C" int rip_stage_l2_refpix_strips(rip_ctx *ctx, const void *cube, int cu
     if (location == RIP_DEVICE && !aligned(cube, cw))
         return rip_fail(ctx, RIP_EINVAL, "l2_refpix_strips: the device pointer cube is not aligned to its %d-byte element", (int)cw);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    if (location == RIP_DEVICE) {
-        ctx->stream_dirty = true;
-        return u16 ? launch_strips<uint16_t, float>(ctx, cube, ngrp, ny, nx, nb, left, right, top, bottom)
-                   : launch_strips<uint32_t, uint32_t>(ctx, cube, ngrp, ny, nx, nb, left, right, top, bottom);
-    }
-    DevBuf<char> d_cube(ctx);
-    DevBuf<char> d_out[4] = {DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx), DevBuf<char>(ctx)};
+    if (location == RIP_DEVICE) ctx->stream_dirty = true;
+    DevArg<char> d_cube, d[4];
     int rc;
-    if ((rc = d_cube.upload(cube, n * cw))) return rc;
+    if ((rc = d_cube.in(ctx, (const char *)cube, n * cw, location))) return rc;
     for (int k = 0; k < 4; ++k)
-        if (outs[k].p && (rc = d_out[k].alloc(outs[k].bytes))) return rc;
-    if ((rc = u16 ? launch_strips<uint16_t, float>(ctx, d_cube.p, ngrp, ny, nx, nb, d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p)
-                  : launch_strips<uint32_t, uint32_t>(ctx, d_cube.p, ngrp, ny, nx, nb, d_out[0].p, d_out[1].p, d_out[2].p, d_out[3].p)))
+        if ((rc = d[k].out(ctx, (char *)outs[k].p, outs[k].bytes, location))) return rc;
+    if ((rc = u16 ? launch_strips<uint16_t, float>(ctx, d_cube.p, ngrp, ny, nx, nb, d[0].p, d[1].p, d[2].p, d[3].p)
+                  : launch_strips<uint32_t, uint32_t>(ctx, d_cube.p, ngrp, ny, nx, nb, d[0].p, d[1].p, d[2].p, d[3].p)))
         return rc;
     for (int k = 0; k < 4; ++k)
-        if (outs[k].p && outs[k].bytes && (rc = d_out[k].download(outs[k].p, outs[k].bytes))) return rc;
-    return dev_sync(ctx);
+        if ((rc = d[k].download())) return rc;
+    return location == RIP_DEVICE ? RIP_OK : dev_sync(ctx);
 }

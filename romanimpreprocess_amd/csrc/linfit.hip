@@ -343,7 +343,7 @@ void lf_launch(rip_ctx *ctx, size_t npix, const LfSets &st, int nsets, const flo
 int rip_cal_frame_sums(rip_ctx *ctx, const uint16_t *cube, int location, int nreads, int ny_file, int nx_file, int y0, int ny, int nx,
                        int f0, int fits_be16, uint32_t *sums, int count) {
     if (!cube || !sums) return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: a required array is NULL");
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_frame_sums", "location", location)) return rc;
     if (count < 0 || count >= LF_MAX_EXPOSURES)
         return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: exposure %d of a set (at most %d: the sums are uint32)", count + 1, LF_MAX_EXPOSURES);
     if (nreads < 1 || ny_file < 1 || nx_file < 1 || ny < 1 || nx < 1 || y0 < 0 || (int64_t)y0 + ny > ny_file)
@@ -367,8 +367,8 @@ int rip_cal_frame_sums(rip_ctx *ctx, const uint16_t *cube, int location, int nre
                                           ctx->stream));
         dcube = band.p;
     }
-    const bool w8 = nx_file % 8 == 0 && ((uintptr_t)dcube & 15) == 0;
-    const int vec_sums = nx % 4 == 0 && ((uintptr_t)sums & 15) == 0;
+    const bool w8 = nx_file % 8 == 0 && aligned(dcube, 16);
+    const int vec_sums = nx % 4 == 0 && aligned(sums, 16);
     const size_t threads = (size_t)nframes * ny * (w8 ? (nx + 7) / 8 : nx);
     if ((threads + 255) / 256 > 0x7FFFFFFFu) return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: a (%d,%d,%d) set is too large", nframes, ny, nx);
     const dim3 grid((unsigned)((threads + 255) / 256));

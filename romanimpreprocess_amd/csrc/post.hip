@@ -423,7 +423,7 @@ int rip_stage_legendre2d(rip_ctx *ctx, float *arr, int ny, int nx, int order, co
 }
 
 int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, double scale, int out_location, double *out) {
-    if (!wcs || !out || ny < 1 || nx < 1 || (out_location != RIP_HOST && out_location != RIP_DEVICE))
+    if (!wcs || !out || ny < 1 || nx < 1 || !rip_is_location(out_location))
         return rip_fail(ctx, RIP_EINVAL, "pixel_area: bad arguments (ny %d, nx %d, out_location %d)", ny, nx, out_location);
     if (!(scale > 0.0) || !std::isfinite(scale)) return rip_fail(ctx, RIP_EINVAL, "pixel_area: scale %g is not a positive number", scale);
     if (wcs->projection < RIP_PROJ_TAN || wcs->projection > RIP_PROJ_SIN)
@@ -441,16 +441,11 @@ int rip_stage_pixel_area(rip_ctx *ctx, const rip_wcs_desc *wcs, int ny, int nx, 
     const size_t n = (size_t)ny * nx;
     const dim3 grid((nx + PA_T - 1) / PA_T, (ny + PA_T - 1) / PA_T);
     if (grid.y > 65535) return rip_fail(ctx, RIP_EINVAL, "pixel_area: %d rows is too many", ny);
-    if (out_location == RIP_DEVICE) {
-        hipLaunchKernelGGL(pixel_area_kernel, grid, dim3(256), 0, ctx->stream, *wcs, ny, nx, scale, out);
-        RIP_HIP(ctx, hipGetLastError());
-        return RIP_OK;
-    }
-    DevBuf<double> o(ctx);
+    DevArg<double> o;
     int rc;
-    if ((rc = o.alloc(n))) return rc;
+    if ((rc = o.out(ctx, out, n, out_location))) return rc;
     hipLaunchKernelGGL(pixel_area_kernel, grid, dim3(256), 0, ctx->stream, *wcs, ny, nx, scale, o.p);
     RIP_HIP(ctx, hipGetLastError());
-    if ((rc = o.download(out, n))) return rc;
-    return dev_sync(ctx);
+    if ((rc = o.download())) return rc;
+    return out_location == RIP_DEVICE ? RIP_OK : dev_sync(ctx);   // a device map: queued, not waited for
 }

@@ -104,11 +104,6 @@ __global__ __launch_bounds__(256) void slopes_kernel(const uint16_t *__restrict_
     }
 }
 
-bool rf_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-bool rf_meet(const void *a, size_t na, const void *b, size_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
 }   // namespace
 
 // ============================================================================================ C-ABI
@@ -116,30 +111,26 @@ bool rf_meet(const void *a, size_t na, const void *b, size_t nb) {
 int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny, int nx, int orient, int nflip, int stored,
                       uint16_t *dst) {
     if (!frame || !dst) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: a required array is NULL");
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: location %d", location);
+    if (const int rc = rip_check_location(ctx, "cal_raw_frame", "location", location)) return rc;
     if (ny < 1 || nx < 1) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: a frame of %d x %d samples", ny, nx);
     if (orient < 0 || orient > 2) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: orient %d (0 none, 1 columns, 2 rows)", orient);
     if (nflip < 0 || nflip > nx) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: nflip %d outside 0..%d", nflip, nx);
     if (stored < 0 || stored > 2)
         return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: stored %d (0 native, 1 FITS with BZERO 32768, 2 FITS int16)", stored);
     const size_t n = (size_t)ny * nx;
-    if (((uintptr_t)dst & 1) || (location == RIP_DEVICE && ((uintptr_t)frame & 1)))
+    if (!aligned(dst, 2) || (location == RIP_DEVICE && !aligned(frame, 2)))
         return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: a device pointer is not aligned to the 2-byte sample");
-    if (rf_meet(frame, n * 2, dst, n * 2)) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: dst overlaps frame");
+    if (ranges_meet(frame, n * 2, dst, n * 2)) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: dst overlaps frame");
     if ((n + 255) / 256 > 0x7FFFFFFFu) return rip_fail(ctx, RIP_EINVAL, "cal_raw_frame: %zu samples are more than one launch takes", n);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    DevBuf<uint16_t> in(ctx);
-    const uint16_t *src = frame;
-    if (location == RIP_HOST) {
-        if (const int rc = in.upload(frame, n)) return rc;
-        src = in.p;
-    }
-    const bool w8 = nx % 8 == 0 && nflip % 8 == 0 && rf_aligned16(src) && rf_aligned16(dst);
+    DevArg<uint16_t> src;
+    if (const int rc = src.in(ctx, frame, n, location)) return rc;
+    const bool w8 = nx % 8 == 0 && nflip % 8 == 0 && aligned(src.p, 16) && aligned(dst, 16);
     const dim3 grid((unsigned)(((w8 ? n / 8 : n) + 255) / 256));
     if (w8)
-        hipLaunchKernelGGL(frame_kernel<true>, grid, dim3(256), 0, ctx->stream, src, ny, nx, orient, nflip, stored, dst);
+        hipLaunchKernelGGL(frame_kernel<true>, grid, dim3(256), 0, ctx->stream, src.p, ny, nx, orient, nflip, stored, dst);
     else
-        hipLaunchKernelGGL(frame_kernel<false>, grid, dim3(256), 0, ctx->stream, src, ny, nx, orient, nflip, stored, dst);
+        hipLaunchKernelGGL(frame_kernel<false>, grid, dim3(256), 0, ctx->stream, src.p, ny, nx, orient, nflip, stored, dst);
     RIP_HIP(ctx, hipGetLastError());
     return dev_sync(ctx);
 }
@@ -147,32 +138,27 @@ int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny,
 int rip_cal_frame_slopes(rip_ctx *ctx, const uint16_t *cube, int n, int nc, size_t npix, const double *w0, double de0, const double *w1,
                          double de1, float *slp, int out_location) {
     if (!cube || !w0 || !w1 || !slp) return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: a required array is NULL");
-    if (out_location != RIP_HOST && out_location != RIP_DEVICE)
-        return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: out_location %d", out_location);
+    if (const int rc = rip_check_location(ctx, "cal_frame_slopes", "out_location", out_location)) return rc;
     if (n < 1 || npix < 1 || npix > ((size_t)1 << 38) || (size_t)n > ((size_t)1 << 60) / npix)
         return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: a cube of %d planes of %zu pixels", n, npix);
     if (nc < 1 || nc > n) return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: nc %d outside 1..%d", nc, n);
-    if (((uintptr_t)cube & 1) || (out_location == RIP_DEVICE && ((uintptr_t)slp & 3)))
+    if (!aligned(cube, 2) || (out_location == RIP_DEVICE && !aligned(slp, 4)))
         return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: a device pointer is not aligned to its sample");
-    if (rf_meet(cube, (size_t)n * npix * 2, slp, npix * 8)) return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: slp overlaps the cube");
+    if (ranges_meet(cube, (size_t)n * npix * 2, slp, npix * 8)) return rip_fail(ctx, RIP_EINVAL, "cal_frame_slopes: slp overlaps the cube");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
     DevBuf<double> w(ctx);
-    DevBuf<float> out(ctx);
+    DevArg<float> d;
     int rc;
     if ((rc = w.alloc(2 * (size_t)nc)) || (rc = w.copy_in(w0, (size_t)nc))) return rc;
     RIP_HIP(ctx, hipMemcpyAsync(w.p + nc, w1, (size_t)nc * sizeof(double), hipMemcpyDefault, ctx->stream));
-    float *d = slp;
-    if (out_location == RIP_HOST) {
-        if ((rc = out.alloc(2 * npix))) return rc;
-        d = out.p;
-    }
-    const bool w8 = npix % 8 == 0 && rf_aligned16(cube) && rf_aligned16(d);
+    if ((rc = d.out(ctx, slp, 2 * npix, out_location))) return rc;
+    const bool w8 = npix % 8 == 0 && aligned(cube, 16) && aligned(d.p, 16);
     const dim3 grid((unsigned)(((w8 ? npix / 8 : npix) + 255) / 256));
     if (w8)
-        hipLaunchKernelGGL(slopes_kernel<true>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d);
+        hipLaunchKernelGGL(slopes_kernel<true>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d.p);
     else
-        hipLaunchKernelGGL(slopes_kernel<false>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d);
+        hipLaunchKernelGGL(slopes_kernel<false>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d.p);
     RIP_HIP(ctx, hipGetLastError());
-    if (out_location == RIP_HOST && (rc = out.download(slp, 2 * npix))) return rc;
+    if ((rc = d.download())) return rc;
     return dev_sync(ctx);
 }

@@ -68,14 +68,12 @@ __global__ __launch_bounds__(256) void decode_ref_kernel(const uint16_t *data, i
     if ((threadIdx.x & 63) == 0) atomicAdd(count, bad);
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }   // namespace
 
 int rip_launch_decode_reference_read(rip_ctx *ctx, const uint16_t *data, int ngrp, size_t n, const uint16_t *ref, int offset,
                                      uint16_t *out, unsigned long long *count, hipStream_t stream) {
     hipStream_t st = stream ? stream : ctx->stream;
-    const bool w8 = n % 8 == 0 && aligned16(data) && aligned16(ref) && aligned16(out);
+    const bool w8 = n % 8 == 0 && aligned(data, 16) && aligned(ref, 16) && aligned(out, 16);
     const size_t threads = w8 ? n / 8 : n;
     const size_t blocks = (threads + 255) / 256;
     if (blocks > 0x7FFFFFFFu) return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: %zu pixels a plane are more than one launch takes", n);
@@ -112,26 +110,28 @@ extern "C" int rip_stage_decode_reference_read(rip_ctx *ctx, const uint16_t *dat
     if (ngrp < 1 || n < 1) return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: %d groups of %zu pixels", ngrp, n);
     if (offset > (1 << 30) || offset < -(1 << 30))
         return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: data_encoding_offset %d (|offset| <= 2^30 supported)", offset);
-    if (location != RIP_HOST && location != RIP_DEVICE) return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: location %d", location);
+    if (const int rc = rip_check_location(ctx, "decode_reference_read", "location", location)) return rc;
     const size_t total = (size_t)ngrp * n;
     if (total / n != (size_t)ngrp || total > ((size_t)1 << 62))
         return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: %d groups of %zu pixels", ngrp, n);
     if (out != data && (uintptr_t)out < (uintptr_t)(data + total) && (uintptr_t)data < (uintptr_t)(out + total))
         return rip_fail(ctx, RIP_EINVAL, "decode_reference_read: out overlaps data without being equal to it");
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned long long *words = (unsigned long long *)n_out_of_range;
-    if (location == RIP_DEVICE) {
-        ctx->stream_dirty = true;   // (the next overlapped rip_calibrate orders its pre-pass behind this work: these may be its inputs)
-        RIP_HIP(ctx, hipMemsetAsync(words, 0, 8, ctx->stream));
-        return rip_launch_decode_reference_read(ctx, data, ngrp, n, reference_read, offset, out, words);
-    }
-    DevBuf<uint16_t> cube(ctx), ref(ctx);
-    DevBuf<unsigned long long> cnt(ctx);
+    // (the next overlapped rip_calibrate orders its pre-pass behind this work: these may be its inputs)
+    if (location == RIP_DEVICE) ctx->stream_dirty = true;
+    DevArg<uint16_t> o, ref;
+    DevArg<unsigned long long> cnt;
     int rc;
-    if ((rc = cube.upload(data, total)) || (rc = ref.upload(reference_read, n)) || (rc = cnt.alloc(1))) return rc;
-    RIP_HIP(ctx, hipMemsetAsync(cnt.p, 0, 8, ctx->stream));
-    if ((rc = rip_launch_decode_reference_read(ctx, cube.p, ngrp, n, ref.p, offset, cube.p, cnt.p)) || (rc = cube.download(out, total)) ||
-        (rc = cnt.download(words, 1)))
+    if ((rc = o.out(ctx, out, total, location))) return rc;
+    const uint16_t *d = data;
+    if (location == RIP_HOST) {   // a host cube is decoded in place, in the buffer of the result
+        if ((rc = o.buf.copy_in(data, total))) return rc;
+        d = o.p;
+    }
+    if ((rc = ref.in(ctx, reference_read, n, location)) || (rc = cnt.out(ctx, (unsigned long long *)n_out_of_range, 1, location)))
         return rc;
-    return dev_sync(ctx);
+    RIP_HIP(ctx, hipMemsetAsync(cnt.p, 0, 8, ctx->stream));
+    if ((rc = rip_launch_decode_reference_read(ctx, d, ngrp, n, ref.p, offset, o.p, cnt.p)) || (rc = o.download()) || (rc = cnt.download()))
+        return rc;
+    return location == RIP_DEVICE ? RIP_OK : dev_sync(ctx);   // device pointers: queued, not waited for
 }

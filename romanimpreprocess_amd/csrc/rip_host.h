@@ -2,27 +2,29 @@
 // declarations the host translation units share.  Included by host code in .hip files only -- never by rip_common.h or by a
 // header that holds device code.
 //
-// Pointer kinds of the ARRAY arguments of the stage-level entry points (include/romanhip.h says the same at each):
-//   host arrays OR device pointers   rip_stage_noise_inject (in-place calls, out == cube, included), rip_stage_poisson_resample,
-//                                    rip_stage_pearson, and the post-path entries of post.hip (rip_stage_build_mask, _endslice,
-//                                    _bin_mean, _select_ranks, _gauss_hist, _legendre2d; rip_stage_pixel_area by out_location),
-//                                    and the calibration-file entries of calfiles.hip (rip_cal_biascorr, _pflat, _saturation,
-//                                    _mask).  The noise-layer driver (L1_to_L2/gen_noise_image.py) hands them planes that live in HBM.
-//   host arrays OR device pointers,  the dark-file entries of darkstack.hip (rip_cal_group_means, _sigma_clip_mean, _dark_planes):
-//   told by a `location` argument    RIP_DEVICE arrays are used where they are -- the stack of group means is too large to copy;
-//                                    the OUTPUTS of rip_cal_gain_ipc4d (gainfile.hip), whose inputs are small host tables;
-//                                    rip_stage_fits_encode (fitsout.hip): one location for src and mask, another for dst;
-//                                    rip_stage_l2_planes, rip_stage_l2_refpix_strips (l2out.hip): one location for every pointer;
-//                                    rip_cal_raw_frame (rawframes.hip): the frame by its location, the cube plane always in HBM;
-//                                    rip_cal_frame_slopes: the cube always in HBM, the slopes by out_location;
-//                                    rip_fpa_bin (fpaplot.hip): dq, every plane and out each by a location of its own;
-//                                    rip_fpa_render: the maps and the picture by theirs, its small tables host arrays
-//                                    rip_cal_frame_sums (linfit.hip): the cube by its location, the sums always in HBM
-//   device pointers                  rip_cal_linearity_fit: the sums of every set, Sref and all result planes (its tables are host arrays)
-//   host arrays                      the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f
-// Small tables (nreads, group tables, weights, ranks, counts) are host arrays everywhere.
+// Pointer kinds of the ARRAY arguments of the stage-level entry points (include/romanhip.h says the same at each).
+// THE RULE: an entry that takes a `location` (RIP_HOST or RIP_DEVICE) for an array declares that array as a DevArg below: a
+// RIP_DEVICE pointer is used where it is, a RIP_HOST array goes through a scoped device buffer, a NULL optional array stays NULL,
+// and the end of the entry reads the same for every location.  Which arrays a location covers is said by the entry's in() / out()
+// lines; whether it waits before it returns, by its last line.  Under the rule:
+// rip_cal_group_means, _sigma_clip_mean, _dark_planes, rip_cal_gain_ipc4d, rip_cal_raw_frame, rip_cal_frame_slopes,
+// rip_cal_frame_sums, rip_stage_l2_planes, rip_stage_l2_refpix_strips, rip_fpa_bin, rip_fpa_render, rip_stage_fits_encode,
+// rip_stage_decode_reference_read, rip_stage_pixel_area.  The exceptions:
+//   partial copies                   rip_cal_group_means copies only its row band of a host cube, rip_cal_frame_sums only the frames
+//                                    and rows it uses (hipMemcpy2DAsync into a DevBuf); rip_stage_fits_encode and
+//                                    rip_stage_decode_reference_read turn a host source into the result in place, in the
+//                                    output's buffer
+//   always device pointers           the cube plane of rip_cal_raw_frame, the cube of rip_cal_frame_slopes, the sums of
+//                                    rip_cal_frame_sums, and every plane of rip_cal_linearity_fit
+//   always host arrays               the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f; the tables of
+//                                    rip_cal_gain_ipc4d and rip_fpa_render; small tables (nreads, group tables, weights, ranks,
+//                                    counts) everywhere
+//   host arrays OR device pointers,  rip_stage_noise_inject (in place, out == cube, included), rip_stage_poisson_resample,
+//   not told apart                   rip_stage_pearson, the post-path entries of post.hip but rip_stage_pixel_area, and the entries
+//                                    of calfiles.hip (rip_cal_biascorr, _pflat, _saturation, _mask): they copy through DevBuf
+//                                    either way (the noise-layer driver hands them planes that live in HBM)
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
-// copy for a host array, so the one helper serves both rows.  A copy direction "tidied" to an explicit kind breaks the first.
+// copy for a host array, so the one helper serves both.  A copy direction "tidied" to an explicit kind breaks the last row.
 #pragma once
 
 #include "rip_common.h"
@@ -64,6 +66,47 @@ struct DevBuf {
         RIP_HIP(ctx, hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDefault, stream ? stream : ctx->stream));
         return RIP_OK;
     }
+};
+
+// ---- array arguments that come with a `location`
+inline bool rip_is_location(int location) { return location == RIP_HOST || location == RIP_DEVICE; }
+inline int rip_check_location(rip_ctx *ctx, const char *who, const char *name, int location) {
+    return rip_is_location(location) ? RIP_OK : rip_fail(ctx, RIP_EINVAL, "%s: %s %d", who, name, location);
+}
+// (NULL or empty ranges meet nothing)
+inline bool ranges_meet(const void *a, size_t na, const void *b, size_t nb) {
+    return a && b && na && nb && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+inline bool aligned(const void *p, uintptr_t to) { return ((uintptr_t)p % to) == 0; }
+
+// One array argument of n elements at a checked `location`, resolved to the device pointer `p` that the kernels get: the
+// caller's own pointer for RIP_DEVICE (nothing owned) and for a NULL optional array (NULL), a scoped buffer for RIP_HOST.
+// in() queues the upload of a host input; out() remembers a host output, and download() queues its way back (and does nothing
+// in the other cases).  Nothing here waits.  An entry that fills a host output's buffer itself copies into `buf`.
+template <typename T = char>
+struct DevArg {
+    T *p = nullptr;
+    DevBuf<T> buf{nullptr};
+    int out(rip_ctx *ctx, T *dst, size_t n, int location, const char *who = __builtin_FUNCTION()) {
+        p = dst;
+        if (!dst || location == RIP_DEVICE) return RIP_OK;
+        buf.ctx = ctx, buf.who = who;
+        host = dst, count = n;
+        const int rc = buf.alloc(n);
+        p = buf.p;
+        return rc;
+    }
+    int in(rip_ctx *ctx, const T *src, size_t n, int location, const char *who = __builtin_FUNCTION()) {   // p: read only
+        const int rc = out(ctx, const_cast<T *>(src), n, location, who);
+        if (rc || !host) return rc;
+        host = nullptr;
+        return buf.copy_in(src, n);
+    }
+    int download() const { return host && count ? buf.download(host, count) : RIP_OK; }
+
+private:
+    T *host = nullptr;   // where a host output goes back to
+    size_t count = 0;
 };
 
 // waits for what an entry point has queued (its downloads among it)

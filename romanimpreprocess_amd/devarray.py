@@ -3,8 +3,9 @@
 The stage-level entry points of ``libromanhip`` that the post-path and the noise layers use (``rip_stage_select_ranks``,
 ``rip_stage_legendre2d``, ``rip_stage_gauss_hist``, ``rip_stage_bin_mean``, ``rip_stage_build_mask``, ``rip_stage_endslice``,
 ``rip_stage_noise_inject``, ``rip_stage_poisson_resample``, ``rip_stage_pearson``) copy their array arguments with
-``hipMemcpyDefault``: a pointer may be a host array or device memory (so may those of the calibration-file entries
-``rip_cal_*`` and of the L2-output entries ``rip_stage_l2_planes`` / ``rip_stage_l2_refpix_strips``, which take a ``location``).  ``Context.call`` takes a ``DevArray`` wherever it takes a numpy array and checks
+``hipMemcpyDefault``: a pointer may be a host array or device memory.  So may the arrays of every entry that takes a
+``location`` argument, which ``_native.location_of(array)`` supplies: device memory is then used where it lies
+(``include/romanhip.h`` says at each entry which arrays its location covers).  ``Context.call`` takes a ``DevArray`` wherever it takes a numpy array and checks
 its ``dtype`` against the element type the header declares for the parameter.  ``DevArray`` wraps a torch tensor on the GPU so that the
 mirrors written for numpy arrays (``utils/sky.py``, ``L1_to_L2/gen_noise_image.py``) can be handed a plane that never leaves
 HBM: it offers what those functions ask of an array -- ``shape``, ``dtype`` (numpy's), ``ndim``, ``size``,

@@ -183,9 +183,9 @@ def bin_planes(dq, planes, nside, n1, mask=None, ctx=None, out=None):
     if out is None:
         torch, dev = _torch_device(ctx)
         out = DevArray(torch.empty((len(planes), max(int(n1), 1), max(int(n1), 1)), dtype=torch.float64, device=dev)).sync()
-    ctx.call("rip_fpa_bin", dq, _native.RIP_DEVICE if is_dev(dq) else _native.RIP_HOST, grow, nside, n1, len(planes), ptrs,
+    ctx.call("rip_fpa_bin", dq, _native.RIP_HOST if dq is None else _native.location_of(dq), grow, nside, n1, len(planes), ptrs,
              as_int([_native.dtype_code(a) for a in keep]), as_int([a.shape[0] for a in keep]),
-             as_int([_native.RIP_DEVICE if is_dev(a) else _native.RIP_HOST for a in keep]), out, _native.RIP_DEVICE)
+             as_int([_native.location_of(a) for a in keep]), out, _native.location_of(out))
     return out
 
 
@@ -212,11 +212,11 @@ def render(maps, present, vmin, vmax, scale, n1, ny, nx, sca_pos, table=None, fo
     if not is_dev(maps):
         maps = np.ascontiguousarray(maps)
     as_f64 = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (npanel,)))   # noqa: E731
-    ctx.call("rip_fpa_render", n1, nsca, npanel, nw, gap, ny, nx, maps, _native.RIP_DEVICE if is_dev(maps) else _native.RIP_HOST, present,
+    ctx.call("rip_fpa_render", n1, nsca, npanel, nw, gap, ny, nx, maps, _native.location_of(maps), present,
              np.ascontiguousarray(sca_pos, dtype=np.int32).reshape(nsca, 2), as_f64(vmin), as_f64(vmax),
              np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=bool), (npanel,)), dtype=np.uint8),
              np.ascontiguousarray(VIRIDIS if table is None else table, dtype=np.uint8).reshape(256, 3), glyphs,
-             len(st), st if len(st) else None, img, _native.RIP_DEVICE if is_dev(img) else _native.RIP_HOST)
+             len(st), st if len(st) else None, img, _native.location_of(img))
     return img
 
 

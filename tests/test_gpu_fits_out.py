@@ -199,6 +199,26 @@ def test_masked_encode(fill):
             assert work.read() == masked_expected(arr, mask, 1, fill), f"in place n={n} {name}"
 
 
+@pytest.mark.parametrize("n", [17, 4099])
+def test_masked_encode_between_host_and_device(n):
+    """src and mask in one place, dst in the other, against both in the same place: the same bytes, with a mask and without"""
+    ctx = gpu_context()
+    kind = (-32, 0)
+    arr = samples(np.float32, n, seed=9)
+    mask = masks_for(n, 0)["other_bytes"]
+    for m, want in ((mask, masked_expected(arr, mask, 1, -1000.0)), (None, expected(arr))):
+        got = {}
+        for sloc, dloc in ((HOST, HOST), (DEVICE, DEVICE), (HOST, DEVICE), (DEVICE, HOST)):
+            src, dm = DevBytes(n * 4, 4, arr.tobytes()), None if m is None else DevBytes(n, 1, m.tobytes())
+            dst, out = DevBytes(n * 4, 4), np.full(n * 4, SENTINEL, np.uint8)
+            mk = None if m is None else (m if sloc == HOST else dm.ptr)
+            encode(ctx, arr if sloc == HOST else src.ptr, kind, n, sloc, out if dloc == HOST else dst.ptr, dloc, mask=mk, sense=1, fill=-1000.0)
+            got[sloc, dloc] = out.tobytes() if dloc == HOST else dst.read()
+            assert src.read() == arr.tobytes() and (dm is None or dm.read() == m.tobytes()), "an input was written"
+        assert got[HOST, HOST] == want
+        assert all(v == want for v in got.values()), [k for k, v in got.items() if v != want]
+
+
 def test_masked_sample_carries_the_fill_bits_and_a_nan_keeps_its_payload():
     ctx = gpu_context()
     arr = np.array([0x7FC12345, 0x3F800000, 0xFFC54321, 0x7F800001, 0x40490FDB], np.uint32).view(np.float32)

@@ -154,6 +154,64 @@ def test_two_calls_give_the_same_bits():
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("nside, n1", [(64, 16), (96, 32)])   # finished in the tile (s = 4), and added from parts (s = 3)
+def test_bin_locations_give_the_same_bits(nside, n1):
+    """the raw entry with dq, the planes and out each in host memory or in HBM, and without dq: one set of bits"""
+    import ctypes as C
+
+    from romanimpreprocess_amd import _native
+    from romanimpreprocess_amd.devarray import to_device
+    ctx = gpu_context()
+    rng = np.random.default_rng(nside)
+    dq, planes = np.ascontiguousarray(fr.random_dq(rng, nside, 0.1), dtype=np.uint32), mixed_planes(rng, nside)[:4]
+    grow = np.ascontiguousarray(fr.PIXELMASK1, dtype=np.uint8)
+    H, D = _native.RIP_HOST, _native.RIP_DEVICE
+    assert _native.location_of(to_device(dq)) == D and _native.location_of(to_device(dq).t) == D and _native.location_of(dq) == H
+
+    def run(dq_on, planes_on, out_on, with_dq=True):
+        q = None if not with_dq else (to_device(dq) if dq_on else dq)
+        keep = [to_device(a) if on else a for a, on in zip(planes, planes_on)]
+        out = np.full((len(keep), n1, n1), 7.0)
+        if out_on:
+            out = to_device(out)
+        ints = lambda v: np.array(v, dtype=np.intc)   # noqa: E731
+        ctx.call("rip_fpa_bin", q, D if dq_on else H, grow, nside, n1, len(keep), (C.c_void_p * len(keep))(*[a.ctypes.data for a in keep]),
+                 ints([_native.dtype_code(a) for a in keep]), ints([a.shape[0] for a in keep]), ints([D if on else H for on in planes_on]),
+                 out, D if out_on else H)
+        return (out.numpy() if out_on else out).tobytes()
+
+    for with_dq in (True, False):
+        host = run(False, [False] * 4, False, with_dq)
+        assert host == run(True, [True] * 4, True, with_dq), "everything in HBM"
+        assert host == run(True, [False, True, True, False], False, with_dq), "mixed, out on the host"
+        assert host == run(False, [True, False, False, True], True, with_dq), "mixed, out in HBM"
+    want = fp().bin_planes(dq, planes, nside, n1, mask=fr.PIXELMASK1, ctx=ctx).numpy()
+    assert run(False, [False] * 4, False) == want.tobytes(), "the wrapper's bits"
+
+
+def test_render_locations_give_the_same_bits(g):
+    """maps and the picture each in host memory or in HBM, with stamps and a font and without (glyphs and stamps NULL)"""
+    from romanimpreprocess_amd.devarray import to_device
+    ctx = gpu_context()
+    n1, ny, nx = 8, 40, 60
+    maps = render_case(np.random.default_rng(13), n1, nsca=2)
+    present, pos = np.ones((2, 2), np.uint8), np.array([[1, 2], [20, 30]], np.int32)
+    stamps = fp().text_stamps(1, (ny, nx), (2, 20), 1, 200, "ab")
+
+    def run(font, maps_on, out_on):
+        out = to_device(np.full((ny, 2 * nx + 3, 3), 7, np.uint8)) if out_on else None
+        got = fp().render(to_device(maps) if maps_on else maps, present, -1.0, 3.0, (True, False), n1, ny, nx, pos, table=g["table"],
+                          font=font, stamps=stamps, ctx=ctx, out=out)
+        assert (got is out) if out_on else isinstance(got, np.ndarray)
+        return (got.numpy() if out_on else got).tobytes()
+
+    for font in (g["glyphs"], None):
+        host = run(font, False, False)
+        for maps_on, out_on in ((True, True), (False, True), (True, False)):
+            assert run(font, maps_on, out_on) == host, (font is not None, maps_on, out_on)
+    assert run(g["glyphs"], False, False) != run(None, False, False), "the stamps are drawn"
+
+
 def test_bin_refusals_launch_nothing():
     import torch
 

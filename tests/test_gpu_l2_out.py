@@ -257,6 +257,34 @@ def test_refpix_strips(dtype, ngrp):
             check({k: o.read(np.float32, want[k].shape) for k, o in outs.items()}, want, f"device pointers, shifted {shifted}")
 
 
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32], ids=["u16", "f32"])
+@pytest.mark.parametrize("nb", [0, 1])
+def test_refpix_strips_host_and_device_with_null_outputs(dtype, nb):
+    """the raw entry at RIP_HOST and at RIP_DEVICE on a 2 x 5 x 12 cube, with every strip, with two and with one: the same bits
+    from both, and a strip not asked for is left alone.  nb = 0: the strips hold no element, and nothing is written"""
+    ctx = gpu_context()
+    ngrp, ny, nx = 2, 5, 12
+    cube = cube_of(dtype, ngrp, ny, nx)
+    want = lr.refpix_strips(cube, nb)
+    names = tuple(want)
+    src = DevBytes(cube.nbytes, 0, cube.tobytes())
+    for keep in (names, names[:2], names[3:]):
+        host = {k: np.full(want[k].shape, 7, np.float32) for k in names}
+        ctx.call("rip_stage_l2_refpix_strips", cube, _native.dtype_code(cube), ngrp, ny, nx, nb, HOST,
+                 *(host[k] if k in keep else None for k in names))
+        outs = {k: DevBytes(want[k].nbytes) for k in names}
+        ctx.call("rip_stage_l2_refpix_strips", src.ptr, _native.dtype_code(cube), ngrp, ny, nx, nb, DEVICE,
+                 *(outs[k].ptr if k in keep else None for k in names))
+        ctx.synchronize()
+        for k in names:
+            if k in keep:
+                lr.same_bits(host[k], want[k], f"host arrays, {k} of {keep}")
+                lr.same_bits(outs[k].read(np.float32, want[k].shape), host[k], f"device pointers against host arrays, {k} of {keep}")
+            else:
+                assert np.all(host[k] == 7) and outs[k].untouched(), f"{k} was not asked for"
+    assert src.read().tobytes() == cube.tobytes()
+
+
 def test_refpix_strips_refusals_leave_the_outputs_alone():
     ctx = gpu_context()
     ngrp, ny, nx, nb = 2, 16, 24, 4

@@ -149,6 +149,31 @@ def test_slopes_forms_agree_host_output_and_real_row():
         convert_frames.cube_slopes(cube, N + 1, ctx=ctx)
 
 
+@pytest.mark.parametrize("ny, nx", [(6, 16), (5, 12)])
+def test_slopes_host_and_device_outputs_are_the_same_bits(ny, nx):
+    """out_location RIP_HOST against RIP_DEVICE on one cube: 96 pixels (a multiple of 8: the wide form where the pointers allow
+    it) and 60 (the narrow form), the device slopes on a 16-byte boundary and one float behind it"""
+    import torch
+
+    ctx = gpu_context()
+    N, Nc, npix = 7, 5, ny * nx
+    cube = np.random.default_rng(ny * nx).integers(0, 65536, (1, N, ny, nx)).astype(np.uint16)
+    want = rr.slopes(cube, Nc).reshape(2, npix)
+    dcube = torch.from_numpy(words(cube).reshape(-1)).cuda()
+    w0, de0, w1, de1 = convert_frames.slope_weights(Nc)
+    host = np.full((2, npix), 7, np.float32)
+    ctx.call("rip_cal_frame_slopes", dcube.data_ptr(), N, Nc, npix, w0, de0, w1, de1, host, HOST)
+    assert_same_bits(host, want, "host output")
+    for off in (0, 1):
+        dev = torch.full((2 * npix + 4,), 7.0, dtype=torch.float32, device="cuda")
+        assert dev.data_ptr() % 16 == 0
+        torch.cuda.synchronize()
+        ctx.call("rip_cal_frame_slopes", dcube.data_ptr(), N, Nc, npix, w0, de0, w1, de1, dev.data_ptr() + 4 * off, DEVICE)
+        got = dev.cpu().numpy()
+        assert_same_bits(got[off:off + 2 * npix].reshape(2, npix), host, f"device output {off} floats off the boundary against the host output")
+        assert np.all(got[:off] == 7) and np.all(got[off + 2 * npix:] == 7), "written outside the slopes"
+
+
 def test_slopes_refusals_come_before_any_launch():
     import torch
 

@@ -161,6 +161,18 @@ def test_marshal_checks_torch_tensors_by_width_and_kind():
         assert word in str(e.value)
 
 
+def test_location_of_tells_host_arrays_and_refuses_the_rest():
+    assert _native.location_of(np.zeros(3)) == _native.RIP_HOST
+    assert _native.location_of(np.zeros((2, 3), np.uint16)[:, 1:]) == _native.RIP_HOST   # a view is a numpy array too
+    for other in (None, [1.0, 2.0], 7, np.float32(1), b"abc", np.zeros(3).ctypes.data):
+        with pytest.raises(TypeError, match="location_of"):
+            _native.location_of(other)
+    import torch
+
+    with pytest.raises(TypeError, match="location_of"):   # host memory, but no numpy array: .numpy() says which bytes are meant
+        _native.location_of(torch.zeros(3))
+
+
 def test_call_needs_no_context_for_the_entries_without_one():
     assert _native.call("rip_version") == 100
     assert _native.call("rip_chain_form_for", 9, 8, _native.RIP_F32, _native.RIP_F32) == 2
