@@ -902,6 +902,63 @@ int rip_cal_linearity_fit(rip_ctx *ctx, int nsets, const uint32_t **sums, const 
                           double slopecut, double negativepad, int bright, int dark, float *data, float *smin, float *smax, uint32_t *dq,
                           float *pflat, float *dark_rate, uint16_t *ramperr, int32_t *cut);
 
+/* ---- the noise summary of a dark set --------------------------------------------------------- */
+/* The step of the reference's runs/2026_July/make_sca_files_2026Jul.job (line 76) that calls solid-waffle's noise_run, whose
+   output make_dark_file.py reads.  solid-waffle's source is not in the reference tree: the rule below IS the specification,
+   parity with solid-waffle is unpinned.  The noise parameters are defined as the inverse of the reference's own generator
+   (from_sim/sim_to_isim.py:306-402) and tested by round trip (calfiles/noisestack.py: noise_params).  The three calls return when
+   their kernels are done.
+   Geometry: C science channels of cw columns (cw even, at most 256; production 32 x 128), nch = C + 1 channels with ref_out != 0:
+   the reference output is the cw columns after the science ones.  Frames used: f0 .. f0+n-1 (-t = f0 + 1, -tn = n). */
+
+/* One dark exposure, read once.  cube (nreads,ny,nx_file) u16 where `location` says (RIP_HOST: the n frames used are staged
+   through a scoped device buffer); fits_be16 as for rip_cal_group_means; the columns 0 .. nch*cw-1 are used.  count: the number
+   of exposures added so far.  With x_i the sample of frame f0+i, d_i = x_(i+1) - x_i and S = sum_i (2i - (n-1)) x_i, the
+   per-pixel accumulators (ny, nch*cw), ALWAYS device pointers, zeroed by the caller before the first exposure, get
+     a0 u32 += x_0      a1 u64 += x_0^2     b0 i32 += d_0            b1 u64 += d_0^2
+     s0 i64 += S        s1 u64 += S^2       c0 i32 += x_(n-1) - x_0  c1 u64 += sum_i d_i^2
+   and m33 (ny,cw) u32 (ref_out only, else NULL) += sum_i x_i of the reference-output columns.  All are integers: the result
+   depends on no order.  Nothing wraps for n <= 64 and 512 exposures: |S| <= 65535 n^2 / 2, so 512 S^2 < 2^64.
+   rowsum (n,ny,nch,2) u32, a device pointer, is WRITTEN: rowsum[i][y][c][p] = the sum of frame f0+i over the columns of channel c
+   (C: the reference output) in row y whose index has parity p.  The lanes of a channel meet in LDS; no atomics.
+   A lane takes 8 adjacent pixels (16-byte loads and stores) when nx_file % 8 == 0, cw % 8 == 0 and the first sample and the
+   accumulators are 16-byte aligned; otherwise one.  Both forms give the same words.
+   RIP_EINVAL, before anything is launched or copied: n outside 2..64, count outside 0..511, f0 + n > nreads (the message names
+   -tn), cw odd or above 256, ny < 128, nch * cw > nx_file, a NULL pointer, an unknown location. */
+int rip_cal_noise_add(rip_ctx *ctx, const uint16_t *cube, int location, int nreads, int ny, int nx_file, int C, int cw, int ref_out, int f0,
+                      int n, int fits_be16, int count, uint32_t *a0, uint64_t *a1, int32_t *b0, uint64_t *b1, int64_t *s0, uint64_t *s1,
+                      int32_t *c0, uint64_t *c1, uint32_t *m33, uint32_t *rowsum);
+
+/* The rowsum of one exposure into the f64 moment tables, all DEVICE pointers, zeroed by the caller before the first exposure.
+   Scales j = 0 .. J, J = min(6, floor(log2(ny / 64))); scale j has ny >> (j+1) blocks b, and the (j, b) of all scales are laid end
+   to end: nbt = sum_j (ny >> (j+1)).  For the CDS pair k = 0 .. n-2: D_k[y][c] = rowsum[k+1][y][c][0] + rowsum[k+1][y][c][1] -
+   rowsum[k][y][c][0] - rowsum[k][y][c][1] (i64); H[k][j][b][c] = the sum of D_k over the rows [2b 2^j, (2b+1) 2^j) minus the sum
+   over the next 2^j rows (trailing rows are unused); T[k][j][b] = sum over c < C of H; Q[k][c] = the sum over all rows of
+   (rowsum[k+1][y][c][0] - rowsum[k][y][c][0]) - (rowsum[k+1][y][c][1] - rowsum[k][y][c][1]).
+     h1, h2 (n-1,nbt,nch) += H, H^2     t1, t2 (n-1,nbt) += T, T^2     ht (n-1,nbt) += H[..][C] * T (ref_out only, else NULL)
+     q1, q2 (n-1,nch) += Q, Q^2
+   Every term is f64(int) * f64(int), one rounding, added with one rounding; every word has one writer and calls come in exposure
+   order, so a numpy loop over the exposures gives the same bits.  No atomics.
+   RIP_EINVAL: n outside 2..64, ny < 128, C < 1, a NULL pointer. */
+int rip_cal_noise_rowstats(rip_ctx *ctx, const uint32_t *rowsum, int n, int ny, int C, int ref_out, double *h1, double *h2, double *t1,
+                           double *t2, double *ht, double *q1, double *q2);
+
+/* The per-pixel planes from the accumulators of nexp exposures (device pointers), one lane per pixel in f64, one rounding per
+   operation (no contraction; / and sqrt correctly rounded), each result rounded once to f32.  With N = nexp, n_tot = N (n-1),
+   var(q, s, m) = (q - s*s/m) / (m - 1) where that is positive, else 0, and nn = n (n^2 - 1):
+     planes (6,ny,C*cw) f32:  0 DARK1 = b0 / (N tframe)              1 DARK1ERR = sqrt(var(b1, b0, N) / N) / tframe
+                              2 DARK2 = (6 s0) / ((N nn) tframe)      3 DARK2ERR = (6 sqrt(var(s1, s0, N) / N)) / (nn tframe)
+                              4 CDS = sqrt(var(c1, c0, n_tot))        5 RESET = sqrt(var(a1, a0, N))
+     amp33 (2,ny,cw) f32 (ref_out only, else NULL), from the reference-output columns:  0 = m33 / (N n), the mean sample;
+                              1 = f32(f64(CDS) / sqrt(2)), as rip_cal_dark_planes makes read_noise
+   DARK1 is the short-baseline rate in DN/s, DARK2 the unweighted least-squares slope of the n frames.  planes and amp33 live where
+   `location` says (RIP_HOST: filled through a scoped device buffer).
+   RIP_EINVAL: nexp outside 2..512 (a variance over exposures needs two), n outside 2..64, tframe not positive, a NULL pointer, an
+   unknown location. */
+int rip_cal_noise_planes(rip_ctx *ctx, const uint32_t *a0, const uint64_t *a1, const int32_t *b0, const uint64_t *b1, const int64_t *s0,
+                         const uint64_t *s1, const int32_t *c0, const uint64_t *c1, const uint32_t *m33, int nexp, int n, int ny, int C,
+                         int cw, int ref_out, double tframe, int location, float *planes, float *amp33);
+
 /* ---- focal-plane overview of a calibration set (utils/fpaplot.py of the reference) ---------- */
 #define RIP_FPA_MAX_PLANES 8
 

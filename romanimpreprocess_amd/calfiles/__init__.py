@@ -9,7 +9,9 @@ drop-in ``make_dark_file.run``; in front of that, the exposure cubes and slope i
 ``csrc/rawframes.hip``) with the drop-ins ``convert_dark``, ``convert_flt`` and ``convert_loflt``.  The ``gain`` and ``ipc4d`` files that all of them read come from ``summary_means`` (numpy, on
 the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hip``), with the drop-in ``make_gain_file.run``.  The
 ``linearitylegendre`` file itself -- the per-frame sums of the flat and dark ramps and the constrained Legendre fit to them -- is
-``linfit.py`` (``RampStack``, ``derive_linearity``, ``csrc/linfit.hip``) with the drop-in ``linearity_run.run``.
+``linfit.py`` (``RampStack``, ``derive_linearity``, ``csrc/linfit.hip``) with the drop-in ``linearity_run.run``.  The noise summary
+that ``make_dark_file`` reads -- the ``DARK1`` .. ``RESET`` planes, ``AMP33`` and the parameters of the correlated noise -- is
+``noisestack.py`` (``NoiseStack``, ``noise_params``, ``csrc/noisestat.hip``) with the drop-in ``noise_run.run``.
 """
 
 import warnings
@@ -213,3 +215,4 @@ def derive_gain_ipc4d(means, good, shape=(pars.nside, pars.nside), nb=NBORDER, i
 from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E402, F401
 from .convert_frames import convert, cube_slopes, find_frames, frames_to_cube  # noqa: E402, F401
 from .linfit import RampStack, derive_linearity  # noqa: E402, F401
+from .noisestack import NoiseStack, NoiseSummary, noise_params  # noqa: E402, F401

@@ -11,6 +11,8 @@ extension).  Every exposure is read ONCE (the script opens each once per group):
 ``DarkStack`` keeps the group means of all exposures in HBM; where they do not fit, the frame is worked in row bands and the
 exposures are read once per band.  The two ``_asdf_data.fits`` display dumps of the script are written too (``calio.write_fits``:
 an empty primary HDU and the planes of each tree, byte order made on the device).  The clipped mean follows the rule of ``rip_cal_sigma_clip_mean``; parity with astropy is unpinned.
+Where the noise summary does not exist yet, ``run(..., noise_out=None, noise_args=[...])`` makes it in the same pass over the
+exposures (``noise_run.Feeder``, ``NoiseStack``), writes it where ``noise_run`` would and goes on with its planes from HBM.
 """
 
 import sys
@@ -26,6 +28,7 @@ from ..devarray import DevArray, is_dev
 from .darkstack import DarkStack, derive_dark_planes
 
 NSIDE = 4096   # dimension of H4RG (make_dark_file.py:26)
+CHANNELWIDTH = 128   # columns of a read-out channel and of the reference output
 
 
 def _meta(pattern, sca, ng, reftype):
@@ -77,11 +80,12 @@ def _dev_cube(cube):
     return DevArray(cube.t[0], np.uint16) if cube.ndim == 4 else cube
 
 
-def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July"):
+def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July", each=None):
     """The clipped mean of the group means of ``files``, float32 (ng, ny, min(nside, width)): one pass over the files, or one
     per band of ``band_rows`` rows (default: as many rows as fit into four fifths of the free device memory).  ``layout``: where
     an exposure sits in its file (``_open_dark``).  ``files`` may also be a list of ``DevArray`` cubes, uint16 (1, N, ny, nx) or
-    (N, ny, nx) in native samples: they are read where they are and no file is opened."""
+    (N, ny, nx) in native samples: they are read where they are and no file is opened.  ``each(cube, fits_be16)`` is handed
+    every exposure of the first pass as well (``noise_run.Feeder.feed``: the noise summary from the same read)."""
     import torch
 
     if layout not in LAYOUTS:
@@ -105,20 +109,24 @@ def dark_data(files, reads, nside=NSIDE, band_rows=None, ctx=None, layout="2026_
             if j % 10 == 0:
                 print("loading groups", y0, j)
                 sys.stdout.flush()
-            if resident:
-                stack.add(_dev_cube(name))
-            else:
-                stack.add(_open_dark(name, layout), fits_be16=True)
+            cube = _dev_cube(name) if resident else _open_dark(name, layout)
+            stack.add(cube, fits_be16=not resident)
+            if each is not None and y0 == 0:
+                each(cube, not resident)
         mean = stack.finish(sigma=3)
         out[:, y0:y1, :] = mean.numpy() if is_dev(mean) else mean
         del stack
     return out
 
 
-def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July"):
+def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, band_rows=None, ctx=None, layout="2026_July",
+        noise_args=None, channelwidth=CHANNELWIDTH):
     """Write the dark file ``outfile`` and its read-noise sibling; returns their two paths.  ``reads`` (the flat ``READS`` list)
     replaces the yaml of the working directory; ``nside`` is the script's constant (smaller frames: for tests); ``layout``
-    ``"summer2025"`` reads the exposures as ``convert_dark`` writes them (``dark_data``)."""
+    ``"summer2025"`` reads the exposures as ``convert_dark`` writes them (``dark_data``).  ``noise_out`` None: there is no noise
+    summary yet; it is made in the same pass over the exposures from ``noise_args``, the options of the job's ``noise_run`` line
+    (``["-f", "1", "-o", <summary>, "-n", "100", "-t", "3", "-tn", "34", "-ro", ...]``; ``-i`` is ``target``), written to its
+    ``-o`` as ``noise_run`` writes it, and its planes go on from HBM; the two files are the ones a run on that summary gives."""
     sca, nside = int(sca), int(nside)
     if reads is None:
         with open("settings_" + pattern + ".yaml") as f:
@@ -129,19 +137,43 @@ def run(pattern, target, noise_out, sca, outfile, *, reads=None, nside=NSIDE, ba
     print(files)
     if not files:
         raise FileNotFoundError(f"no noise file {target[:-8]}001.fits")
-    darkave = dark_data(files, reads, nside=nside, band_rows=band_rows, ctx=ctx, layout=layout)
+    feeder = None
+    if noise_out is None:
+        from . import noise_run
+
+        if noise_args is None:
+            raise ValueError("without a noise summary, noise_args (the options of the noise_run line) are needed")
+        na = noise_run.parse(["-i", target] + [str(v) for v in noise_args])
+        feeder = noise_run.Feeder(na.tstart, na.nframe, na.ref_out, na.tframe, nside=nside, cw=channelwidth, ndark=na.ndark, ctx=ctx)
+    darkave = dark_data(files, reads, nside=nside, band_rows=band_rows, ctx=ctx, layout=layout, each=feeder and feeder.feed)
 
     # the dark current maps, read noise and reset noise of the summary
-    header, summary = calio.read_fits_image(noise_out, 1)
+    if feeder is not None:
+        made = feeder.finish()
+        noise_out = na.out
+        noise_run.write(noise_out, made, na.cdscut, na.rowover, ctx=ctx)
+        header, summary = calio.read_fits_image(noise_out, 1, header_only=True)[0], made.planes   # the planes stay in HBM
+    else:
+        header, summary = calio.read_fits_image(noise_out, 1)
 
     def plane(key):
+        if feeder is not None:
+            return DevArray(summary.t[int(header[key])], np.float32)
         return np.asarray(summary[int(header[key])], dtype=np.float32)
 
     dark_slope, dark_slope_err, read_noise = derive_dark_planes(plane("DARK1"), plane("DARK2"), plane("DARK1ERR"), plane("DARK2ERR"),
                                                                 plane("CDS"), nside=nside, ctx=ctx)
-    reset_noise = np.ascontiguousarray(plane("RESET")[:, :nside])
+    reset_noise = plane("RESET")
+    if feeder is not None:
+        dark_slope, dark_slope_err, read_noise, reset_noise = (a.numpy() for a in (dark_slope, dark_slope_err, read_noise, reset_noise))
+    reset_noise = np.ascontiguousarray(reset_noise[:, :nside])
     try:   # AMP33 if it is there
-        h33, d33 = calio.read_fits_image(noise_out, "AMP33")
+        if feeder is not None:
+            if made.amp33 is None:
+                raise KeyError("AMP33")
+            h33, d33 = calio.read_fits_image(noise_out, "AMP33", header_only=True)[0], made.amp33.numpy()
+        else:
+            h33, d33 = calio.read_fits_image(noise_out, "AMP33")
         amp33 = {"valid": True, "med": np.array(d33[0], dtype=np.float32), "std": np.array(d33[1], dtype=np.float32),
                  "M_PINK": float(h33["M_PINK"]), "RU_PINK": float(h33["RU_PINK"])}
     except (KeyError, ValueError, TypeError):   # placeholders

@@ -9,13 +9,15 @@
 // lines; whether it waits before it returns, by its last line.  Under the rule:
 // rip_cal_group_means, _sigma_clip_mean, _dark_planes, rip_cal_gain_ipc4d, rip_cal_raw_frame, rip_cal_frame_slopes,
 // rip_cal_frame_sums, rip_stage_l2_planes, rip_stage_l2_refpix_strips, rip_fpa_bin, rip_fpa_render, rip_stage_fits_encode,
-// rip_stage_decode_reference_read, rip_stage_pixel_area.  The exceptions:
+// rip_stage_decode_reference_read, rip_stage_pixel_area, rip_cal_noise_add, rip_cal_noise_planes.  The exceptions:
 //   partial copies                   rip_cal_group_means copies only its row band of a host cube, rip_cal_frame_sums only the frames
-//                                    and rows it uses (hipMemcpy2DAsync into a DevBuf); rip_stage_fits_encode and
+//                                    and rows it uses (hipMemcpy2DAsync into a DevBuf), rip_cal_noise_add only the frames it
+//                                    uses; rip_stage_fits_encode and
 //                                    rip_stage_decode_reference_read turn a host source into the result in place, in the
 //                                    output's buffer
 //   always device pointers           the cube plane of rip_cal_raw_frame, the cube of rip_cal_frame_slopes, the sums of
-//                                    rip_cal_frame_sums, and every plane of rip_cal_linearity_fit
+//                                    rip_cal_frame_sums, every plane of rip_cal_linearity_fit, the accumulators and row sums
+//                                    of rip_cal_noise_add and every array of rip_cal_noise_rowstats
 //   always host arrays               the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f; the tables of
 //                                    rip_cal_gain_ipc4d and rip_fpa_render; small tables (nreads, group tables, weights, ranks,
 //                                    counts) everywhere
