@@ -1005,6 +1005,60 @@ int rip_fpa_render(rip_ctx *ctx, int n1, int nsca, int npanel, int nw, int gap, 
                    const uint8_t *present, const int32_t *sca_pos, const double *vmin, const double *vmax, const uint8_t *scale,
                    const uint8_t *table, const uint8_t *glyphs, int nstamps, const int32_t *stamps, uint8_t *out, int out_location);
 
+/* ---- quick-look pictures of a Level-1 cube (utils/visualize.py, utils/diff.py of the reference) ---------- */
+#define RIP_VIEW_MAX_RANKS 8
+
+/* The three entries read a cube (ng,ny,nx) of dtype RIP_U16 or RIP_F32 where cube_location says (RIP_HOST: through a scoped
+   device buffer; RIP_DEVICE: read where it is) and are ordered on rip_stream(); each returns when its kernels and copies are
+   done.  The value of a sample of plane g is f32(sample), minus f32(sample of plane `minus` at the same pixel) where minus >= 0
+   (minus = -1: no differencing): data.astype(np.float32) - data[minus], exact for u16.  No f32 copy of the cube is made.
+
+   np.percentile's raw material (visualize.py:58-59, 83-84, 97): exact order statistics of the window rows y0..y1, columns
+   x0..x1 (both INCLUSIVE, as the reference's slice) of the planes g0 .. g1-1.  values[r] (HOST, f32) is the element of 0-based
+   rank ranks[r] (HOST) of the n = (g1-g0)(y1-y0+1)(x1-x0+1) values in ascending order; nan_count (HOST, one word) the number
+   of NaNs among them.  The order is that of the key of rip_select.h: -0 just below +0, NaNs beyond the infinities on the side of
+   their sign (np.sort puts every NaN last: with nan_count > 0 a caller that mirrors numpy answers NaN).  Three histogram levels
+   of 11 + 11 + 10 key bits, each one pass over the window; integer atomics only: two calls give the same bits.
+   RIP_EINVAL, before anything is launched or copied: a NULL pointer; an unknown dtype or location; an empty or out-of-frame
+   window or plane range; minus outside -1..ng-1; nranks outside 1..8; a rank >= n; n >= 2^32. */
+int rip_view_ranks(rip_ctx *ctx, const void *cube, int dtype, int cube_location, int ng, int ny, int nx, int y0, int y1, int x0, int x1,
+                   int g0, int g1, int minus, int nranks, const uint32_t *ranks, float *values, uint32_t *nan_count);
+
+/* diff.py:17: out (ny,nx) f32 = f32(cube[g2]) - f32(cube[g1]) over the whole frame; out where out_location says.  Of a host
+   cube only the two planes travel.  RIP_EINVAL: a NULL pointer, an unknown dtype or location, a plane outside the cube. */
+int rip_view_plane_diff(rip_ctx *ctx, const void *cube, int dtype, int cube_location, int ng, int ny, int nx, int g1, int g2, float *out,
+                        int out_location);
+
+/* visualize.py:60-111: the finished RGB picture in one store-only launch, every byte written once by the thread that owns the
+   pixel.  out (pic_ny,pic_nx,3) u8 where out_location says; row 0 is the BOTTOM row of the picture (as rip_fpa_render's).  The
+   background is white.  Every panel is a cell of (cell_h,cell_w) pixels and shows the window rows y0..y1, columns x0..x1
+   (inclusive) of one plane, every sample as zoom x zoom pixels (nearest neighbour), window row y0 at the bottom
+   (origin="lower"), from the cell's first pixel on: H = zoom (y1-y0+1) rows, W = zoom (x1-x0+1) columns.
+   HOST tables:
+     panels  (npanel,6) i32   plane g, minus (or -1), norm kind (0 linear, 1 power), (y, x) of the cell's first pixel in the
+                              picture, colour bar (0 / 1)
+     limits  (npanel,3) f32   vmin, vmax, gamma (read for the power norm only)
+     table   (256,3) u8       the colour table;  glyphs (256,12,6) u8 or NULL (then nstamps must be 0)
+     stamps  (nstamps,6) i32  as rip_fpa_render's, (y, x) inside the cell
+   Per pixel the arithmetic is matplotlib's (3.10, numpy 2) for float32 input, cmap(norm(v), bytes=True)[..., :3]:
+     d = v - vmin in f32;  linear (Normalize):  t = f32(f64(d) / (f64(vmax) - f64(vmin)))
+                           power (PowerNorm):   t = d / (vmax - vmin) in f32, then t = powf(t, gamma) where t > 0
+     index = int(t * 256), below 0 -> 0, from 256 on -> 255 (t == 1 gives 255);  NaN -> white (the map's bad colour is
+     transparent);  vmin == vmax -> index 0 for every sample, NaN included (Normalize fills with 0).  / is correctly rounded.
+   The colour bar of a panel: the columns W + bar_gap .. W + bar_gap + bar_w - 1 of the rows 0 .. H-1, np.linspace(0, 1, H) from
+   the bottom through the same index rule in f64; then its ticks, black, one row high and `tick` columns long, right of the bar at
+   the rows 0, H / 2 and H - 1; then the stamps.  A later panel draws over an earlier one.
+   RIP_EINVAL, before anything is launched or copied: a NULL cube, table or out; an unknown dtype or location; an empty or
+   out-of-frame window; npanel < 1; a plane or minus outside the cube; an unknown norm kind; vmin > vmax or a bound that is not
+   finite (matplotlib raises there too); a power norm whose gamma is not finite and positive; zoom < 1; bar_gap or tick < 0,
+   bar_w < 1; a cell smaller than H x W, or than W + bar_gap + bar_w + tick columns where the panel has a bar; a cell that
+   reaches past the picture; a picture of more than 65535 rows; stamps without glyphs; a stamp of a panel that does not exist,
+   outside its cell, of size < 1, of a value or character outside 0..255. */
+int rip_view_render(rip_ctx *ctx, const void *cube, int dtype, int cube_location, int ng, int ny, int nx, int y0, int y1, int x0, int x1,
+                    int npanel, const int32_t *panels, const float *limits, int zoom, int bar_gap, int bar_w, int tick, int cell_h,
+                    int cell_w, int pic_ny, int pic_nx, const uint8_t *table, const uint8_t *glyphs, int nstamps, const int32_t *stamps,
+                    uint8_t *out, int out_location);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ can be exchanged with the reference tooling.  ``parse_fits_header`` reads the FI
 (``config["FITSWCS"]``, ``gen_cal_image.py:64-87``) without astropy; ``read_fits_image`` maps the image of one HDU of a FITS file
 (the dark exposures and noise summaries of ``calfiles/make_dark_file.py``).  ``fits_header`` and ``write_fits`` write image HDUs
 (the mask files, ``FITSOUT`` and the display dumps of the calibration-file scripts): the header on the host, the data units put
-into FITS storage order on the GPU (``rip_stage_fits_encode``).  ``write_png`` writes an 8-bit RGB picture (``utils/fpaplot.py``).
+into FITS storage order on the GPU (``rip_stage_fits_encode``).  ``write_png`` writes an 8-bit RGB picture (``utils/fpaplot.py``), ``write_pdf_image`` the same raster as a one-page PDF (``utils/visualize.py``).
 """
 
 import bz2
@@ -563,3 +563,34 @@ def write_png(path, arr, level=6):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", nx, ny, 8, 2, 0, 0, 0))
                 + chunk(b"IDAT", zlib.compress(rows.tobytes(), level)) + chunk(b"IEND", b""))
+
+
+# ------------------------------------------------------------------------------- PDF
+def write_pdf_image(path, arr, level=6):
+    """An (ny, nx, 3) uint8 array as a one-page PDF 1.4 file that holds it as a single Flate-coded DeviceRGB image, rows in the
+    order given (first row at the top), one pixel a point: what ``utils/visualize.py`` writes where the reference's command line
+    names a ``.pdf``.  Host only (``zlib``)."""
+    arr = np.asarray(arr)
+    if arr.ndim != 3 or arr.shape[2] != 3 or arr.dtype != np.uint8 or arr.shape[0] < 1 or arr.shape[1] < 1:
+        raise ValueError(f"write_pdf_image: expected a uint8 array (ny, nx, 3), got {arr.dtype}{arr.shape}")
+    ny, nx, _ = arr.shape
+    data = zlib.compress(np.ascontiguousarray(arr).tobytes(), level)
+    draw = f"q {nx} 0 0 {ny} 0 0 cm /Im0 Do Q".encode("ascii")
+    objects = [
+        b"<< /Type /Catalog /Pages 2 0 R >>",
+        b"<< /Type /Pages /Kids [3 0 R] /Count 1 >>",
+        f"<< /Type /Page /Parent 2 0 R /MediaBox [0 0 {nx} {ny}] /Resources << /XObject << /Im0 4 0 R >> >> /Contents 5 0 R >>".encode("ascii"),
+        (f"<< /Type /XObject /Subtype /Image /Width {nx} /Height {ny} /ColorSpace /DeviceRGB /BitsPerComponent 8 /Filter /FlateDecode "
+         f"/Length {len(data)} >>\nstream\n").encode("ascii") + data + b"\nendstream",
+        f"<< /Length {len(draw)} >>\nstream\n".encode("ascii") + draw + b"\nendstream",
+    ]
+    out, offsets = bytearray(b"%PDF-1.4\n%\xe2\xe3\xcf\xd3\n"), []
+    for i, body in enumerate(objects):
+        offsets.append(len(out))
+        out += f"{i + 1} 0 obj\n".encode("ascii") + body + b"\nendobj\n"
+    xref = len(out)
+    out += f"xref\n0 {len(objects) + 1}\n".encode("ascii") + b"0000000000 65535 f \n"
+    out += b"".join(f"{o:010d} 00000 n \n".encode("ascii") for o in offsets)
+    out += f"trailer\n<< /Size {len(objects) + 1} /Root 1 0 R >>\nstartxref\n{xref}\n%%EOF".encode("ascii")
+    with open(path, "wb") as f:
+        f.write(out)

@@ -11,6 +11,7 @@
 
 #include "rip_grow.h"
 #include "rip_host.h"
+#include "rip_stamp.h"
 
 namespace {
 
@@ -264,22 +265,13 @@ __global__ __launch_bounds__(256) void fpa_render_kernel(FrLayout L, const doubl
                 gch = table[3 * idx + 1];
                 b = table[3 * idx + 2];
             }
-            if (y >= L.ny - bh - 2 * L.sc && y < L.ny - bh)
-                for (int j = 0; j < 3; ++j) {
-                    const int xt = x - (L.nx / 2 - L.n1 + j * L.n1);
-                    if (xt >= 0 && xt < L.sc) r = gch = b = 0;
-                }
+            for (int j = 0; j < 3; ++j) tick_over(L.ny - bh - 2 * L.sc, L.nx / 2 - L.n1 + j * L.n1, 2 * L.sc, L.sc, y, x, r, gch, b);
         } else if (idx >= 0) {
             r = table[3 * idx];
             gch = table[3 * idx + 1];
             b = table[3 * idx + 2];
         }
-        for (int i = stamp_at[panel]; i < stamp_at[panel + 1]; ++i) {
-            const int32_t *st = stamps + 6 * i;
-            const int size = st[3], yy = y - st[1], xx = x - st[2];
-            if (yy < 0 || yy >= 12 * size || xx < 0 || xx >= 6 * size) continue;
-            if (glyphs[(st[5] * 12 + 11 - yy / size) * 6 + xx / size] > 0) r = gch = b = (uint8_t)st[4];
-        }
+        stamps_over(glyphs, stamps, stamp_at[panel], stamp_at[panel + 1], y, x, r, gch, b);
     }
     uint8_t *o = out + ((size_t)Y * L.NX + X) * 3;
     o[0] = r;
@@ -387,27 +379,8 @@ int rip_fpa_render(rip_ctx *ctx, int n1, int nsca, int npanel, int nw, int gap, 
         if (l.nx / 2 - l.n1 < 0 || l.nx / 2 + l.n1 > l.nx || l.n1 / 8 + 2 * l.sc > l.ny || l.nx / 2 + l.n1 + l.sc > l.nx)
             return rip_fail(ctx, RIP_EINVAL, "fpa_render: the scale of n1 %d does not fit the panel of (%d, %d)", l.n1, l.ny, l.nx);
     }
-    std::vector<int32_t> at(l.npanel + 1, 0), sorted((size_t)l.nstamps * 6);
-    for (int i = 0; i < l.nstamps; ++i) {
-        const int32_t *st = stamps + 6 * i;
-        if (st[0] < 0 || st[0] >= l.npanel) return rip_fail(ctx, RIP_EINVAL, "fpa_render: stamp %d is of panel %d of %d", i, st[0], l.npanel);
-        if (st[3] < 1 || st[4] < 0 || st[4] > 255 || st[5] < 0 || st[5] > 255)
-            return rip_fail(ctx, RIP_EINVAL, "fpa_render: stamp %d has size %d, value %d, character %d", i, st[3], st[4], st[5]);
-        if (st[1] < 0 || st[2] < 0 || st[1] >= l.ny || st[2] >= l.nx)
-            return rip_fail(ctx, RIP_EINVAL, "fpa_render: stamp %d starts outside the image, at (%d, %d) of (%d, %d)", i, st[1], st[2], l.ny, l.nx);
-        if (st[1] + 12 * (long)st[3] > l.ny || st[2] + 6 * (long)st[3] > l.nx)
-            return rip_fail(ctx, RIP_EINVAL, "fpa_render: stamp %d at (%d, %d) of size %d reaches past the image of (%d, %d)", i, st[1], st[2],
-                            st[3], l.ny, l.nx);
-        ++at[st[0] + 1];
-    }
-    for (int p = 0; p < l.npanel; ++p) at[p + 1] += at[p];
-    {   // stamps by panel, list order kept within each
-        std::vector<int32_t> next(at.begin(), at.end() - 1);
-        for (int i = 0; i < l.nstamps; ++i) {
-            const int32_t *st = stamps + 6 * i;
-            std::copy(st, st + 6, sorted.begin() + (size_t)6 * next[st[0]]++);
-        }
-    }
+    std::vector<int32_t> at, sorted;
+    if ((rc = rip_stamp_table(ctx, "fpa_render", l.nstamps, stamps, l.npanel, l.ny, l.nx, at, sorted))) return rc;
     const int nh = (l.npanel - 1) / l.nw + 1;
     const long NYl = (long)nh * l.ny + (long)(nh - 1) * l.gap, NXl = (long)l.nw * l.nx + (long)(l.nw - 1) * l.gap;
     if (NYl > 65535 || NXl > (1 << 24)) return rip_fail(ctx, RIP_EINVAL, "fpa_render: a picture of (%ld, %ld) pixels is too large", NYl, NXl);

@@ -9,17 +9,18 @@
 // lines; whether it waits before it returns, by its last line.  Under the rule:
 // rip_cal_group_means, _sigma_clip_mean, _dark_planes, rip_cal_gain_ipc4d, rip_cal_raw_frame, rip_cal_frame_slopes,
 // rip_cal_frame_sums, rip_stage_l2_planes, rip_stage_l2_refpix_strips, rip_fpa_bin, rip_fpa_render, rip_stage_fits_encode,
-// rip_stage_decode_reference_read, rip_stage_pixel_area, rip_cal_noise_add, rip_cal_noise_planes.  The exceptions:
+// rip_stage_decode_reference_read, rip_stage_pixel_area, rip_cal_noise_add, rip_cal_noise_planes, rip_view_ranks,
+// rip_view_plane_diff, rip_view_render.  The exceptions:
 //   partial copies                   rip_cal_group_means copies only its row band of a host cube, rip_cal_frame_sums only the frames
 //                                    and rows it uses (hipMemcpy2DAsync into a DevBuf), rip_cal_noise_add only the frames it
-//                                    uses; rip_stage_fits_encode and
+//                                    uses, rip_view_plane_diff only its two planes; rip_stage_fits_encode and
 //                                    rip_stage_decode_reference_read turn a host source into the result in place, in the
 //                                    output's buffer
 //   always device pointers           the cube plane of rip_cal_raw_frame, the cube of rip_cal_frame_slopes, the sums of
 //                                    rip_cal_frame_sums, every plane of rip_cal_linearity_fit, the accumulators and row sums
 //                                    of rip_cal_noise_add and every array of rip_cal_noise_rowstats
 //   always host arrays               the wrappers of stage.hip, rip_stage_invlinearity, rip_stage_noise_1f; the tables of
-//                                    rip_cal_gain_ipc4d and rip_fpa_render; small tables (nreads, group tables, weights, ranks,
+//                                    rip_cal_gain_ipc4d, rip_fpa_render and rip_view_render; small tables (nreads, group tables, weights, ranks,
 //                                    counts) everywhere
 //   host arrays OR device pointers,  rip_stage_noise_inject (in place, out == cube, included), rip_stage_poisson_resample,
 //   not told apart                   rip_stage_pearson, the post-path entries of post.hip but rip_stage_pixel_area, and the entries
@@ -28,6 +29,8 @@
 // DevBuf copies with hipMemcpyDefault in both directions: under unified addressing that IS the host-to-device (device-to-host)
 // copy for a host array, so the one helper serves both.  A copy direction "tidied" to an explicit kind breaks the last row.
 #pragma once
+
+#include <algorithm>
 
 #include "rip_common.h"
 
@@ -122,6 +125,36 @@ template <typename K>
 inline int with_lds(rip_ctx *ctx, K kernel, size_t lds) {
     if (lds > 48 * 1024)
         RIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return RIP_OK;
+}
+
+// The stamp list of a picture entry (rip_fpa_render, rip_view_render; rip_stamp.h draws it): nstamps rows of [panel, y, x, size,
+// value, character], positions inside a panel of (ny, nx) pixels.  Refuses (RIP_EINVAL, `who`: the entry's name) a stamp of a
+// panel that does not exist, of size < 1, of a value or character outside 0..255, one that does not start inside its panel or
+// reaches past it; otherwise leaves the stamps by panel in `sorted`, list order kept within each, and in at[p] .. at[p + 1] the
+// range of panel p.
+inline int rip_stamp_table(rip_ctx *ctx, const char *who, int nstamps, const int32_t *stamps, int npanel, int ny, int nx,
+                           std::vector<int32_t> &at, std::vector<int32_t> &sorted) {
+    at.assign(npanel + 1, 0);
+    sorted.resize((size_t)nstamps * 6);
+    for (int i = 0; i < nstamps; ++i) {
+        const int32_t *st = stamps + 6 * i;
+        if (st[0] < 0 || st[0] >= npanel) return rip_fail(ctx, RIP_EINVAL, "%s: stamp %d is of panel %d of %d", who, i, st[0], npanel);
+        if (st[3] < 1 || st[4] < 0 || st[4] > 255 || st[5] < 0 || st[5] > 255)
+            return rip_fail(ctx, RIP_EINVAL, "%s: stamp %d has size %d, value %d, character %d", who, i, st[3], st[4], st[5]);
+        if (st[1] < 0 || st[2] < 0 || st[1] >= ny || st[2] >= nx)
+            return rip_fail(ctx, RIP_EINVAL, "%s: stamp %d starts outside the image, at (%d, %d) of (%d, %d)", who, i, st[1], st[2], ny, nx);
+        if (st[1] + 12 * (long)st[3] > ny || st[2] + 6 * (long)st[3] > nx)
+            return rip_fail(ctx, RIP_EINVAL, "%s: stamp %d at (%d, %d) of size %d reaches past the image of (%d, %d)", who, i, st[1], st[2],
+                            st[3], ny, nx);
+        ++at[st[0] + 1];
+    }
+    for (int p = 0; p < npanel; ++p) at[p + 1] += at[p];
+    std::vector<int32_t> next(at.begin(), at.end() - 1);
+    for (int i = 0; i < nstamps; ++i) {
+        const int32_t *st = stamps + 6 * i;
+        std::copy(st, st + 6, sorted.begin() + (size_t)6 * next[st[0]]++);
+    }
     return RIP_OK;
 }
 

@@ -64,18 +64,37 @@ VIRIDIS = np.frombuffer(bytes.fromhex(
     "d7e219dae218dce218dfe318e1e318e4e318e7e419e9e419ece41aeee51bf1e51cf3e51ef6e61ff8e621fae622fde724"
 ), dtype=np.uint8).reshape(256, 3)
 
+# matplotlib.colormaps["magma"](np.arange(256), bytes=True)[:, :3] (matplotlib 3.10): the map of utils/visualize.py
+MAGMA = np.frombuffer(bytes.fromhex(
+    "00000300000400000601000701010901010b02020d02020f03031104031304041505041706051907051b08061d09071f0a07220b08240c09260d0a28"
+    "0e0a2a0f0b2c100c2f110c31120d33140d35150e38160e3a170f3c180f3f1a10411b10441c10461e10491f114b20114d221150231152251155261157"
+    "2811592a115c2b115e2d10602f1062301065321067341068350f6a370f6c390f6e3b0f6f3c0f713e0f72400f73420f74430f75450f76470f77481078"
+    "4a10794b10794d117a4f117b50127b52127c53137c55137d57147d58157e5a157e5b167e5d177e5e177f60187f61187f63197f651a80661a80681b80"
+    "691c806b1c806c1d806e1e816f1e81711f81731f817420817621817721817922817a22817c23817e24817f2481812581822581842681852681872781"
+    "8928818a28818c29808d29808f2a80912a80922b80942b80952c80972c7f992d7f9a2d7f9c2e7f9e2e7e9f2f7ea12f7ea3307ea4307da6317da7317d"
+    "a9327cab337cac337bae347bb0347bb1357ab3357ab53679b63679b83778b93778bb3877bd3977be3976c03a75c23a75c33b74c53c74c63c73c83d72"
+    "ca3e72cb3e71cd3f70ce4070d0416fd1426ed3426dd4436dd6446cd7456bd9466ada4769dc4869dd4968de4a67e04b66e14c66e24d65e44e64e55063"
+    "e65162e75262e85461ea5560eb5660ec585fed595fee5b5eee5d5def5e5df0605df1615cf2635cf3655cf3675bf4685bf56a5bf56c5bf66e5bf6705b"
+    "f7715bf7735cf8755cf8775cf9795cf97b5df97d5dfa7f5efa805efa825ffb8460fb8660fb8861fb8a62fc8c63fc8e63fc9064fc9265fc9366fd9567"
+    "fd9768fd9969fd9b6afd9d6bfd9f6cfda16efda26ffda470fea671fea873feaa74feac75feae76feaf78feb179feb37bfeb57cfeb77dfeb97ffebb80"
+    "febc82febe83fec085fec286fec488fec689fec78bfec98dfecb8efdcd90fdcf92fdd193fdd295fdd497fdd698fdd89afdda9cfddc9dfddd9ffddfa1"
+    "fde1a3fce3a5fce5a6fce6a8fce8aafceaacfcecaefceeb0fcf0b1fcf1b3fcf3b5fcf5b7fbf7b9fbf9bbfbfabdfbfcbf"
+), dtype=np.uint8).reshape(256, 3)
+
 
 def color_table(cmap="viridis"):
-    """The (256, 3) uint8 table of a colour map: viridis is shipped; any other name is matplotlib's where that is importable and
-    the map has 256 entries, otherwise it is refused by name."""
+    """The (256, 3) uint8 table of a colour map: viridis and magma are shipped; any other name is matplotlib's where that is
+    importable and the map has 256 entries, otherwise it is refused by name."""
     if cmap == "viridis":
         return VIRIDIS
+    if cmap == "magma":
+        return MAGMA
     try:
         import matplotlib  # noqa: PLC0415
 
         cm = matplotlib.colormaps[cmap]
     except (ImportError, KeyError):
-        raise ValueError(f"fpaplot: colour map {cmap!r} is not shipped (only 'viridis') and matplotlib does not supply it") from None
+        raise ValueError(f"fpaplot: colour map {cmap!r} is not shipped (only 'viridis' and 'magma') and matplotlib does not supply it") from None
     if cm.N != 256:
         raise ValueError(f"fpaplot: colour map {cmap!r} has {cm.N} entries, not 256")
     return np.ascontiguousarray(cm(np.arange(256), bytes=True)[:, :3])
