@@ -959,6 +959,42 @@ int rip_cal_noise_planes(rip_ctx *ctx, const uint32_t *a0, const uint64_t *a1, c
                          const uint64_t *s1, const int32_t *c0, const uint64_t *c1, const uint32_t *m33, int nexp, int n, int ny, int C,
                          int cw, int ref_out, double tframe, int location, float *planes, float *amp33);
 
+/* ---- gain and IPC summaries of a flat set --------------------------------------------------- */
+/* The device half of the step of the reference's runs/2026_July/make_sca_files_2026Jul.job (lines 48-64) that calls
+   solid-waffle's correlation_run (run_ir_all), whose _summary.txt files make_gain_file.py reads.  solid-waffle's source is not
+   in the reference tree: the rule below IS the specification, parity with solid-waffle is unpinned.  The host half
+   (calfiles/corrstack.py: solve_summary) turns these sums into gain, IPC couplings and non-linearity as the inverse of the
+   package's own generator (L1Synth), tested by round trip.
+
+   One pair of exposures.  cube1, cube2 (nreads,ny_file,nx_file) u16, each where its location says (RIP_HOST: only the first ny
+   rows of the four frames used are staged through a scoped device buffer); fits_be16 (both cubes) as for rip_cal_group_means.
+   fa, fb, fc, fd: 0-based frames (TIME a b c d minus one), fa < fb, fc < fd, fa < fd.  The frame is the first (ny,nx) samples of
+   the file's (ny_file,nx_file), nb its border, a superpixel (sy,sx) pixels with ny % sy == 0 and nx % sx == 0, at most 16384
+   pixels (128 x 128, NBIN 32 32 on 4096: its differences are held in LDS).
+   table int64 [ny/sy][nx/sx][25] where table_location says.  Per superpixel, with S1, S2 the two exposures, cds_i(p,q) = S_i[q] -
+   S_i[p] as int32 and e = cds_1(a,d) - cds_2(a,d) on the n0 pixels of the superpixel outside the nb border of the frame:
+     q25, q50, q75   the order statistics of those n0 values of e at the 0-based ranks (n0-1)/4, (n0-1)/2, 3(n0-1)/4 (integer
+                     division)
+     kept            a pixel with |e - q50| * 1349 <= 5000 * (q75 - q25) in 64-bit integers: five robust sigmas
+     slot 0, 1, 2    n (kept), sum e, sum e^2 over the kept pixels
+     slots 3 .. 18   for the shifts (dy,dx) = (0,1), (1,0), (1,1), (1,-1) in this order four slots each: the count m of pixels p
+                     with p and q = p + shift both kept and both inside this superpixel, sum e_p, sum e_q, sum e_p e_q
+     slot 19, 20, 21 sum of cds_1(a,b) + cds_2(a,b) over the kept pixels; the same for (c,d); the same for (a,d)
+     slots 22 .. 24  q25, q50, q75
+   n0 = 0 (a superpixel inside the border) gives 25 zeros.  Integers only: no order of threads changes a bit, and
+   tests/corr_ref.py restates every slot with np.sort.
+   One workgroup per superpixel: the samples are read once (a lane takes 8 adjacent pixels with 16-byte loads when sx % 8 == 0,
+   nx_file % 8 == 0 and every frame used starts on 16 bytes; otherwise one pixel; both forms give the same words; the samples of a
+   pixel that is not kept are read a second time), the ranks come from a two-level histogram selection in LDS, the neighbours from
+   LDS; the sums meet by wave shuffles and LDS, every slot has one writer, no atomics on the sums.  Returns when its kernel and
+   copies are done.
+   RIP_EINVAL, before anything is launched or copied: a NULL pointer, an unknown location, a frame of TIME outside the cube or an
+   order other than the above (the message names TIME), a frame outside the file, nb negative, sy or sx that do not divide the
+   frame or a superpixel above 16384 pixels (the message names NBIN). */
+int rip_cal_corr_pair(rip_ctx *ctx, const uint16_t *cube1, int location1, const uint16_t *cube2, int location2, int nreads, int ny_file,
+                      int nx_file, int fits_be16, int fa, int fb, int fc, int fd, int ny, int nx, int nb, int sy, int sx, int64_t *table,
+                      int table_location);
+
 /* ---- focal-plane overview of a calibration set (utils/fpaplot.py of the reference) ---------- */
 #define RIP_FPA_MAX_PLANES 8
 

@@ -11,7 +11,10 @@ the host: the tables are a few KB) and ``derive_gain_ipc4d`` (``csrc/gainfile.hi
 ``linearitylegendre`` file itself -- the per-frame sums of the flat and dark ramps and the constrained Legendre fit to them -- is
 ``linfit.py`` (``RampStack``, ``derive_linearity``, ``csrc/linfit.hip``) with the drop-in ``linearity_run.run``.  The noise summary
 that ``make_dark_file`` reads -- the ``DARK1`` .. ``RESET`` planes, ``AMP33`` and the parameters of the correlated noise -- is
-``noisestack.py`` (``NoiseStack``, ``noise_params``, ``csrc/noisestat.hip``) with the drop-in ``noise_run.run``.
+``noisestack.py`` (``NoiseStack``, ``noise_params``, ``csrc/noisestat.hip``) with the drop-in ``noise_run.run``.  The superpixel
+summaries that ``make_gain_file`` reads -- gain and inter-pixel capacitance from pairs of flats and darks -- are ``corrstack.py``
+(``CorrStack``, ``solve_summary``, ``csrc/corrstat.hip``) with the drop-in ``correlation_run.run_ir_all`` and, for the job's whole
+gain step, ``correlation_run.gain_from_flats``.
 """
 
 import warnings
@@ -216,3 +219,4 @@ from .darkstack import DarkStack, derive_dark_planes, sigma_clip_mean  # noqa: E
 from .convert_frames import convert, cube_slopes, find_frames, frames_to_cube  # noqa: E402, F401
 from .linfit import RampStack, derive_linearity  # noqa: E402, F401
 from .noisestack import NoiseStack, NoiseSummary, noise_params  # noqa: E402, F401
+from .corrstack import CorrStack, solve_summary  # noqa: E402, F401

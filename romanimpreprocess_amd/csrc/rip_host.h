@@ -10,10 +10,11 @@
 // rip_cal_group_means, _sigma_clip_mean, _dark_planes, rip_cal_gain_ipc4d, rip_cal_raw_frame, rip_cal_frame_slopes,
 // rip_cal_frame_sums, rip_stage_l2_planes, rip_stage_l2_refpix_strips, rip_fpa_bin, rip_fpa_render, rip_stage_fits_encode,
 // rip_stage_decode_reference_read, rip_stage_pixel_area, rip_cal_noise_add, rip_cal_noise_planes, rip_view_ranks,
-// rip_view_plane_diff, rip_view_render.  The exceptions:
+// rip_view_plane_diff, rip_view_render, rip_cal_corr_pair.  The exceptions:
 //   partial copies                   rip_cal_group_means copies only its row band of a host cube, rip_cal_frame_sums only the frames
 //                                    and rows it uses (hipMemcpy2DAsync into a DevBuf), rip_cal_noise_add only the frames it
-//                                    uses, rip_view_plane_diff only its two planes; rip_stage_fits_encode and
+//                                    uses, rip_view_plane_diff only its two planes, rip_cal_corr_pair only the rows of its four
+//                                    frames of either cube; rip_stage_fits_encode and
 //                                    rip_stage_decode_reference_read turn a host source into the result in place, in the
 //                                    output's buffer
 //   always device pointers           the cube plane of rip_cal_raw_frame, the cube of rip_cal_frame_slopes, the sums of
