@@ -12,7 +12,7 @@ the ``ipc4d`` kernel, ``1 / gain``, the inverse linearity, read noise, rounding)
 import numpy as np
 
 from .. import _native
-from ..devarray import DevArray, is_dev
+from ._cubes import raw_cube
 
 SLOTS = 25            # corrstat.hip: CR_SLOTS
 MAX_SUPERPIXEL = 16384   # CR_MAX_PIX: a superpixel's differences are held in LDS
@@ -50,23 +50,9 @@ def check_geometry(ny, nx, nbin, nb):
 
 def _cube(cube, fits_be16):
     """a cube as ``rip_cal_corr_pair`` takes it: (nreads, ny_file, nx_file) 16-bit words, contiguous, viewed as uint16"""
-    dev = is_dev(cube)
-    if not dev and not isinstance(cube, np.ndarray):
-        cube = np.asarray(cube)
-    if cube.ndim == 4 and cube.shape[0] == 1:
-        cube = DevArray(cube.t[0], cube.dtype) if dev else cube[0]
-    if cube.dtype.itemsize != 2 or cube.dtype.kind not in "iu":
-        raise TypeError(f"a cube of 16-bit samples is needed, not {cube.dtype.name}")
-    if not fits_be16 and (cube.dtype.kind != "u" or cube.dtype.byteorder == ">"):
-        raise TypeError(f"native samples must be uint16, not {cube.dtype.str} (FITS storage: fits_be16=True)")
+    cube = raw_cube(cube, fits_be16, True)
     if cube.ndim != 3:
         raise ValueError(f"a (nreads, ny, nx) cube is needed, not {tuple(cube.shape)}")
-    if dev:
-        cube.sync()
-    elif not cube.flags.c_contiguous:
-        cube = np.ascontiguousarray(cube)
-    if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
-        cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
     return cube
 
 

@@ -11,6 +11,7 @@ import numpy as np
 
 from .. import _native
 from ..devarray import DevArray, is_dev
+from ._cubes import raw_cube
 
 MAX_PLANES = 512   # darkstack.hip: DS_MAX_PLANES
 
@@ -124,23 +125,11 @@ class DarkStack:
         (only the rows of the band)."""
         if self.n >= self.capacity:
             raise ValueError(f"the stack holds {self.capacity} exposures already")
-        dev = is_dev(cube)
-        if not dev:
-            cube = np.asarray(cube) if not isinstance(cube, np.ndarray) else cube
-        if cube.dtype.itemsize != 2 or cube.dtype.kind not in "iu":
-            raise TypeError(f"a cube of 16-bit samples is needed, not {cube.dtype.name}")
-        if not fits_be16 and (cube.dtype.kind != "u" or cube.dtype.byteorder == ">"):
-            raise TypeError(f"native samples must be uint16, not {cube.dtype.str} (FITS storage: fits_be16=True)")
+        cube = raw_cube(cube, fits_be16, False)
         if cube.ndim != 3 or cube.shape[1] != self.ny:
             raise ValueError(f"a (nreads, {self.ny}, width) cube is needed, not {tuple(cube.shape)}")
-        if dev:
-            cube.sync()
-            self._dev = True
-        elif not cube.flags.c_contiguous:
-            cube = np.ascontiguousarray(cube)
+        self._dev = self._dev or is_dev(cube)
         nreads, _, width = cube.shape
-        if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
-            cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
         self.ctx.call("rip_cal_group_means", cube, _native.location_of(cube), nreads, self.ny, width, self.y0,
                       self.y1 - self.y0, self.nx, self.reads, self.ng, bool(fits_be16), self.stack, self.capacity, self.n)
         self.n += 1

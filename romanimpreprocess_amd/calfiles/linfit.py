@@ -12,6 +12,7 @@ import numpy as np
 
 from .. import _native
 from ..devarray import DevArray, is_dev, to_device
+from ._cubes import raw_cube
 
 MAX_SETS = 8        # linfit.hip: LF_MAX_SETS
 MAX_ORDER = 10      # LF_MAX_ORDER
@@ -46,23 +47,9 @@ class RampStack:
         """One exposure, a (nframes, ny, width >= nx) or (1, nframes, ny, width) cube of 16-bit samples (numpy array, memory map or
         ``DevArray``, as ``frames_to_cube`` makes them).  ``fits_be16``: the samples are FITS storage (big-endian int16 with ``BZERO
         = 32768``), as ``calio.read_fits_image`` maps them; otherwise they are native uint16."""
-        dev = is_dev(cube)
-        if not dev and not isinstance(cube, np.ndarray):
-            cube = np.asarray(cube)
-        if cube.ndim == 4 and cube.shape[0] == 1:
-            cube = DevArray(cube.t[0], cube.dtype) if dev else cube[0]
-        if cube.dtype.itemsize != 2 or cube.dtype.kind not in "iu":
-            raise TypeError(f"a cube of 16-bit samples is needed, not {cube.dtype.name}")
-        if not fits_be16 and (cube.dtype.kind != "u" or cube.dtype.byteorder == ">"):
-            raise TypeError(f"native samples must be uint16, not {cube.dtype.str} (FITS storage: fits_be16=True)")
+        cube = raw_cube(cube, fits_be16, True)
         if cube.ndim != 3 or cube.shape[0] != self.nframes or cube.shape[1] != self.ny:
             raise ValueError(f"a ({self.nframes}, {self.ny}, width) cube is needed, not {tuple(cube.shape)}")
-        if dev:
-            cube.sync()
-        elif not cube.flags.c_contiguous:
-            cube = np.ascontiguousarray(cube)
-        if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
-            cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
         self.ctx.call("rip_cal_frame_sums", cube, _native.location_of(cube), self.nframes, self.ny, cube.shape[2],
                       self.y0, self.y1 - self.y0, self.nx, 0, bool(fits_be16), self.sums, self.count)
         self.count += 1

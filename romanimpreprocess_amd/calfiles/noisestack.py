@@ -13,7 +13,8 @@ and parity with solid-waffle is unpinned.  The parameters are defined as the inv
 import numpy as np
 
 from .. import _native
-from ..devarray import DevArray, is_dev
+from ..devarray import DevArray
+from ._cubes import raw_cube
 
 MAX_FRAMES = 64       # noisestat.hip: NS_MAX_FRAMES
 MAX_EXPOSURES = 512   # NS_MAX_EXPOSURES
@@ -164,23 +165,9 @@ class NoiseStack:
         or ``DevArray`` (as ``frames_to_cube`` makes them).  ``fits_be16``: the samples are FITS storage (big-endian int16 with
         ``BZERO = 32768``), as ``calio.read_fits_image`` maps them; otherwise native uint16.  Of a host array only the frames used
         travel."""
-        dev = is_dev(cube)
-        if not dev and not isinstance(cube, np.ndarray):
-            cube = np.asarray(cube)
-        if cube.ndim == 4 and cube.shape[0] == 1:
-            cube = DevArray(cube.t[0], cube.dtype) if dev else cube[0]
-        if cube.dtype.itemsize != 2 or cube.dtype.kind not in "iu":
-            raise TypeError(f"a cube of 16-bit samples is needed, not {cube.dtype.name}")
-        if not fits_be16 and (cube.dtype.kind != "u" or cube.dtype.byteorder == ">"):
-            raise TypeError(f"native samples must be uint16, not {cube.dtype.str} (FITS storage: fits_be16=True)")
+        cube = raw_cube(cube, fits_be16, True)
         if cube.ndim != 3 or cube.shape[1] != self.ny or cube.shape[2] != self.nx_file:
             raise ValueError(f"a (nreads, {self.ny}, {self.nx_file}) cube is needed, not {tuple(cube.shape)}")
-        if dev:
-            cube.sync()
-        elif not cube.flags.c_contiguous:
-            cube = np.ascontiguousarray(cube)
-        if cube.dtype != np.uint16:   # FITS storage: the entry takes the same 16-bit words and un-swaps them itself
-            cube = DevArray(cube.t, np.uint16) if dev else cube.view(np.uint16)
         a, t = self.acc, self.tables
         self.ctx.call("rip_cal_noise_add", cube, _native.location_of(cube), cube.shape[0], self.ny, self.nx_file, self.C, self.cw,
                       self.ref_out, self.f0, self.n, bool(fits_be16), self.count, a["a0"], a["a1"], a["b0"], a["b1"], a["s0"], a["s1"],

@@ -8,6 +8,7 @@
 // Bounds (samples <= 65535, a superpixel of at most 16384 pixels): |e| <= 131070 (18 bits with its sign), e^2 and e_p e_q
 // <= 1.72e10, their sums < 2^48; the CDS sums < 2^32; all slots are int64.
 #include "rip_host.h"
+#include "rip_samples.h"
 #include "rip_select.h"
 
 namespace {
@@ -23,17 +24,6 @@ namespace {
 struct CrFrames {
     const uint16_t *p[2][4];    // the first sample of the frames a, b, c, d of the two exposures; rows are nx_file samples
 };
-
-// FITS storage: big-endian int16 with BZERO = 32768; the unsigned sample is the swapped word with its top bit flipped
-__device__ __forceinline__ int cr_sample(uint32_t raw, bool be16) {
-    if (be16) raw = (((raw & 0xFFu) << 8) | (raw >> 8)) ^ 0x8000u;
-    return (int)raw;
-}
-// the same for the two samples of a 32-bit word at once
-__device__ __forceinline__ uint32_t cr_sample2(uint32_t raw, bool be16) {
-    if (be16) raw = (((raw & 0x00FF00FFu) << 8) | ((raw >> 8) & 0x00FF00FFu)) ^ 0x80008000u;
-    return raw;
-}
 
 // the three CDS sums of one pixel from its eight samples v[exposure][frame a, b, c, d]
 struct CrCds {
@@ -79,7 +69,18 @@ __global__ __launch_bounds__(CR_THREADS) void corr_pair_kernel(const CrFrames sr
         if (tid < CR_SLOTS) o[tid] = 0;
         return;
     }
-    const bool be = be16 != 0;
+    const int stored = be16 != 0;
+    // the eight samples of the pixel at sample `at` of every frame
+    auto samples = [&](size_t at, int(&v)[2][4]) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                uint32_t x[1];
+                load_samples<1>(src.p[s][f] + at, stored, x);
+                v[s][f] = (int)x[0];
+            }
+    };
     for (int k = tid; k < SEL_BINS; k += CR_THREADS) hist[k] = 0u;
     __syncthreads();
 
@@ -101,15 +102,11 @@ __global__ __launch_bounds__(CR_THREADS) void corr_pair_kernel(const CrFrames sr
         for (int ch = tid; ch < sy * cpr; ch += CR_THREADS) {
             const int r = ch / cpr, c = (ch - r * cpr) << 3;
             const size_t at = (size_t)(y0 + r) * nx_file + x0 + c;
-            uint32_t w[2][4][4];
+            uint32_t x[2][4][8];
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const uint4 q = *reinterpret_cast<const uint4 *>(src.p[s][f] + at);
-                    w[s][f][0] = cr_sample2(q.x, be), w[s][f][1] = cr_sample2(q.y, be), w[s][f][2] = cr_sample2(q.z, be),
-                    w[s][f][3] = cr_sample2(q.w, be);
-                }
+                for (int f = 0; f < 4; ++f) load_samples<8>(src.p[s][f] + at, stored, x[s][f]);
             int32_t words[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -117,7 +114,7 @@ __global__ __launch_bounds__(CR_THREADS) void corr_pair_kernel(const CrFrames sr
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
 #pragma unroll
-                    for (int f = 0; f < 4; ++f) v[s][f] = (int)((k & 1) ? w[s][f][k >> 1] >> 16 : w[s][f][k >> 1] & 0xFFFFu);
+                    for (int f = 0; f < 4; ++f) v[s][f] = (int)x[s][f][k];
                 words[k] = pixel(v, r, c + k);
             }
             int4 *dst = reinterpret_cast<int4 *>(tile + r * sx + c);   // sx % 8 == 0: 32-byte aligned
@@ -127,12 +124,8 @@ __global__ __launch_bounds__(CR_THREADS) void corr_pair_kernel(const CrFrames sr
     } else {
         for (int i = tid; i < npix; i += CR_THREADS) {
             const int r = i / sx, c = i - r * sx;
-            const size_t at = (size_t)(y0 + r) * nx_file + x0 + c;
             int v[2][4];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int f = 0; f < 4; ++f) v[s][f] = cr_sample(src.p[s][f][at], be);
+            samples((size_t)(y0 + r) * nx_file + x0 + c, v);
             tile[i] = pixel(v, r, c);
         }
     }
@@ -195,12 +188,8 @@ __global__ __launch_bounds__(CR_THREADS) void corr_pair_kernel(const CrFrames sr
                 if (kept(q)) m[s] += 1, sp[s] += e, sq[s] += q, spq[s] += (long long)e * q;
             }
         } else if (e != CR_BORDER) {
-            const size_t at = (size_t)(y0 + r) * nx_file + x0 + c;
             int v[2][4];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int f = 0; f < 4; ++f) v[s][f] = cr_sample(src.p[s][f][at], be);
+            samples((size_t)(y0 + r) * nx_file + x0 + c, v);
             const CrCds s = cr_cds(v);
             tab -= s.ab, tcd -= s.cd, tad -= s.ad;
         }
@@ -265,37 +254,29 @@ int rip_cal_corr_pair(rip_ctx *ctx, const uint16_t *cube1, int location1, const 
     if (nby > 65535) return rip_fail(ctx, RIP_EINVAL, "cal_corr_pair: NBIN: %d rows of superpixels (at most 65535)", nby);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
 
-    const size_t plane_file = (size_t)ny_file * nx_file, plane = (size_t)ny * nx_file;
     const int frames[4] = {fa, fb, fc, fd};
     const uint16_t *cubes[2] = {cube1, cube2};
     const int locations[2] = {location1, location2};
-    DevBuf<uint16_t> band[2] = {DevBuf<uint16_t>(ctx), DevBuf<uint16_t>(ctx)};
+    const size_t plane = (size_t)ny * nx_file;
+    DevBuf<uint16_t> rows[2] = {DevBuf<uint16_t>(ctx), DevBuf<uint16_t>(ctx)};   // of a host cube only the rows of the four frames travel
     CrFrames src;
     bool w8 = sx % 8 == 0 && nx_file % 8 == 0;
     for (int s = 0; s < 2; ++s) {
-        if (locations[s] == RIP_HOST)   // only the rows of the four frames travel
-            if ((rc = band[s].alloc(4 * plane))) return rc;
+        if (locations[s] == RIP_HOST && (rc = rows[s].alloc(4 * plane))) return rc;
         for (int f = 0; f < 4; ++f) {
-            const uint16_t *from = cubes[s] + (size_t)frames[f] * plane_file;
-            if (locations[s] == RIP_HOST) {
-                RIP_HIP(ctx, hipMemcpyAsync(band[s].p + f * plane, from, plane * 2, hipMemcpyHostToDevice, ctx->stream));
-                from = band[s].p + f * plane;
-            }
-            src.p[s][f] = from;
-            w8 = w8 && aligned(from, 16);
+            CubeBand band(ctx);   // one frame
+            uint16_t *into = rows[s].p ? rows[s].p + f * plane : nullptr;
+            if ((rc = band.in(cubes[s], locations[s], ny_file, nx_file, frames[f], 1, 0, ny, into))) return rc;
+            src.p[s][f] = band.p;
+            w8 = w8 && aligned(src.p[s][f], 16);
         }
     }
     DevArg<int64_t> t;
     if ((rc = t.out(ctx, table, (size_t)nby * nbx * CR_SLOTS, table_location))) return rc;
     const size_t lds = (size_t)sy * sx * 4;
     const dim3 grid((unsigned)nbx, (unsigned)nby);
-    if (w8) {
-        if ((rc = with_lds(ctx, corr_pair_kernel<true>, lds))) return rc;
-        hipLaunchKernelGGL(corr_pair_kernel<true>, grid, dim3(CR_THREADS), lds, ctx->stream, src, nx_file, ny, nx, nb, sy, sx, fits_be16, t.p);
-    } else {
-        if ((rc = with_lds(ctx, corr_pair_kernel<false>, lds))) return rc;
-        hipLaunchKernelGGL(corr_pair_kernel<false>, grid, dim3(CR_THREADS), lds, ctx->stream, src, nx_file, ny, nx, nb, sy, sx, fits_be16, t.p);
-    }
+    if ((rc = with_lds(ctx, RIP_W8_KERNEL(corr_pair_kernel, w8), lds))) return rc;
+    RIP_LAUNCH_W8(corr_pair_kernel, w8, grid, dim3(CR_THREADS), lds, ctx->stream, src, nx_file, ny, nx, nb, sy, sx, fits_be16, t.p);
     RIP_HIP(ctx, hipGetLastError());
     if ((rc = t.download())) return rc;
     return dev_sync(ctx);

@@ -8,6 +8,7 @@
 // The stack (groups x exposures x ny x nx f32, 13 GB for 100 darks of the production table) lives in HBM and never moves: the
 // array arguments take a location (RIP_HOST: staged through a scoped device buffer; RIP_DEVICE: used where they are).
 #include "rip_host.h"
+#include "rip_samples.h"
 #include "rip_select.h"
 
 namespace {
@@ -20,12 +21,6 @@ struct DsReads {
 };
 
 // ------------------------------------------------------------------------------------------ group means
-__device__ __forceinline__ float ds_sample(uint32_t raw, bool be16) {
-    // FITS storage: big-endian int16 with BZERO = 32768; the unsigned sample is the swapped word with its top bit flipped
-    if (be16) raw = (((raw & 0xFFu) << 8) | (raw >> 8)) ^ 0x8000u;
-    return (float)raw;
-}
-
 // One thread per 8 consecutive columns of one row (W8: one 16-byte load per read; needs nx_file % 8 == 0 and a 16-byte aligned
 // cube) or per column.  cube points at row y0 of read 0; reads are `plane` samples apart.  Per group the f32 sum runs in read
 // order and is divided once by f32(b - a): np.mean over axis 0 of a float32 array (no pairwise blocking across that axis).
@@ -40,7 +35,7 @@ __global__ __launch_bounds__(256) void group_means_kernel(const uint16_t *__rest
     const int y = (int)(i / nvec), x0 = (int)(i - (size_t)y * nvec) * V;
     const uint16_t *src = cube + (size_t)y * nx_file + x0;
     float *dst = stack + (size_t)y * nx + x0;
-    const bool be = be16 != 0;
+    const int stored = be16 != 0;
     for (int g = 0; g < ng; ++g) {
         const int a = rd.r[2 * g], b = rd.r[2 * g + 1];
         float acc[V];
@@ -48,28 +43,16 @@ __global__ __launch_bounds__(256) void group_means_kernel(const uint16_t *__rest
         for (int k = 0; k < V; ++k) acc[k] = 0.0f;
 #pragma unroll 4
         for (int r = a; r < b; ++r) {
-            if (W8) {
-                const uint4 q = *reinterpret_cast<const uint4 *>(src + (size_t)r * plane);
-                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+            uint32_t x[V];
+            load_samples<V>(src + (size_t)r * plane, stored, x);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    acc[2 * k] = acc[2 * k] + ds_sample(w[k] & 0xFFFFu, be);
-                    acc[2 * k + 1] = acc[2 * k + 1] + ds_sample(w[k] >> 16, be);
-                }
-            } else {
-                acc[0] = acc[0] + ds_sample(src[(size_t)r * plane], be);
-            }
+            for (int k = 0; k < V; ++k) acc[k] = acc[k] + (float)x[k];
         }
         const float d = (float)(b - a);
-        float *o = dst + (size_t)g * group_stride;
-        if (W8 && x0 + 8 <= nx && (nx & 3) == 0) {   // rows of the stack start on 16 bytes when nx % 4 == 0
-            *reinterpret_cast<float4 *>(o) = make_float4(acc[0] / d, acc[1] / d, acc[2] / d, acc[3] / d);
-            *reinterpret_cast<float4 *>(o + 4) = make_float4(acc[4] / d, acc[5] / d, acc[6] / d, acc[7] / d);
-        } else {
 #pragma unroll
-            for (int k = 0; k < V; ++k)
-                if (x0 + k < nx) o[k] = acc[k] / d;
-        }
+        for (int k = 0; k < V; ++k) acc[k] = acc[k] / d;
+        // rows of the stack start on 16 bytes when nx % 4 == 0
+        store_results(dst + (size_t)g * group_stride, acc, nx - x0, (nx & 3) == 0);
     }
 }
 
@@ -223,33 +206,16 @@ int rip_cal_group_means(rip_ctx *ctx, const uint16_t *cube, int location, int nr
         rd.r[2 * g + 1] = (int32_t)b;
     }
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t plane_file = (size_t)ny_file * nx_file;
-    const uint16_t *dcube = cube + (size_t)y0 * nx_file;
-    size_t plane = plane_file;
-    DevBuf<uint16_t> band(ctx);
-    if (location == RIP_HOST) {   // only the rows of the band travel
-        plane = (size_t)ny * nx_file;
-        int rc;
-        if ((rc = band.alloc((size_t)nreads * plane))) return rc;
-        if (ny == ny_file)
-            RIP_HIP(ctx, hipMemcpyAsync(band.p, cube, (size_t)nreads * plane * 2, hipMemcpyHostToDevice, ctx->stream));
-        else
-            RIP_HIP(ctx, hipMemcpy2DAsync(band.p, plane * 2, dcube, plane_file * 2, plane * 2, (size_t)nreads, hipMemcpyHostToDevice,
-                                          ctx->stream));
-        dcube = band.p;
-    }
+    CubeBand band(ctx);
+    if (const int rc = band.in(cube, location, ny_file, nx_file, 0, nreads, y0, ny)) return rc;
     const size_t npix = (size_t)ny * nx;
     float *out = stack + (size_t)j * npix;
     const size_t group_stride = (size_t)cap * npix;
-    const bool w8 = nx_file % 8 == 0 && (((uintptr_t)dcube | (uintptr_t)stack) & 15) == 0;
+    const bool w8 = nx_file % 8 == 0 && aligned(band.p, 16) && aligned(stack, 16);
     const size_t threads = (size_t)ny * (w8 ? (nx + 7) / 8 : nx);
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (w8)
-        hipLaunchKernelGGL(group_means_kernel<true>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, ny, nx, rd, ng, fits_be16, out,
-                           group_stride);
-    else
-        hipLaunchKernelGGL(group_means_kernel<false>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, ny, nx, rd, ng, fits_be16,
-                           out, group_stride);
+    RIP_LAUNCH_W8(group_means_kernel, w8, grid, dim3(256), 0, ctx->stream, band.p, band.plane, nx_file, ny, nx, rd, ng, fits_be16, out,
+                  group_stride);
     RIP_HIP(ctx, hipGetLastError());
     return dev_sync(ctx);
 }

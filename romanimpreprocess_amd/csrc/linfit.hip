@@ -7,6 +7,7 @@
 //   rip_cal_linearity_fit   one lane per pixel: range, constrained Legendre least squares, rates and residuals, all in f64
 // tests/linfit_ref.py restates both in numpy, operation by operation.
 #include "rip_host.h"
+#include "rip_samples.h"
 
 namespace {
 
@@ -15,12 +16,6 @@ namespace {
 #define LF_MAX_EXPOSURES 65536   // 65535 x 65536 still fits in uint32
 
 // ------------------------------------------------------------------------------------------ frame sums
-__device__ __forceinline__ uint32_t lf_sample(uint32_t raw, bool be16) {
-    // FITS storage: big-endian int16 with BZERO = 32768; the unsigned sample is the swapped word with its top bit flipped
-    if (be16) raw = (((raw & 0xFFu) << 8) | (raw >> 8)) ^ 0x8000u;
-    return raw;
-}
-
 // One thread per 8 consecutive columns of one row of one frame (W8: one 16-byte load of samples; needs nx_file % 8 == 0 and a
 // 16-byte aligned cube) or per column.  cube points at row y0 of frame f0; frames are `plane` samples apart.  vec_sums: the rows
 // of sums start on 16 bytes (nx % 4 == 0, aligned base), so that a full vector is two 16-byte read-modify-writes.  Every word of
@@ -35,32 +30,9 @@ __global__ __launch_bounds__(256) void frame_sums_kernel(const uint16_t *__restr
     const size_t row = i / nvec;
     const int x0 = (int)(i - row * nvec) * V;
     const size_t f = row / ny, y = row - f * ny;
-    const uint16_t *src = cube + f * plane + y * nx_file + x0;
-    uint32_t *dst = sums + row * nx + x0;
-    const bool be = be16 != 0;
-    if (W8) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(src);
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        uint32_t s[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            s[2 * k] = lf_sample(w[k] & 0xFFFFu, be);
-            s[2 * k + 1] = lf_sample(w[k] >> 16, be);
-        }
-        if (vec_sums && x0 + 8 <= nx) {
-            uint4 a = *reinterpret_cast<uint4 *>(dst), b = *reinterpret_cast<uint4 *>(dst + 4);
-            a.x += s[0], a.y += s[1], a.z += s[2], a.w += s[3];
-            b.x += s[4], b.y += s[5], b.z += s[6], b.w += s[7];
-            *reinterpret_cast<uint4 *>(dst) = a;
-            *reinterpret_cast<uint4 *>(dst + 4) = b;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (x0 + k < nx) dst[k] += s[k];
-        }
-    } else {
-        dst[0] += lf_sample(src[0], be);
-    }
+    uint32_t s[V];
+    load_samples<V>(cube + f * plane + y * nx_file + x0, be16 != 0, s);
+    add_results(sums + row * nx + x0, s, nx - x0, vec_sums != 0);
 }
 
 // ------------------------------------------------------------------------------------------ the fit
@@ -352,32 +324,15 @@ int rip_cal_frame_sums(rip_ctx *ctx, const uint16_t *cube, int location, int nre
     if (f0 < 0 || f0 >= nreads) return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: first frame %d outside the %d frames of the cube", f0, nreads);
     const int nframes = nreads - f0;
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t plane_file = (size_t)ny_file * nx_file;
-    const uint16_t *dcube = cube + (size_t)f0 * plane_file + (size_t)y0 * nx_file;
-    size_t plane = plane_file;
-    DevBuf<uint16_t> band(ctx);
-    if (location == RIP_HOST) {   // only the frames and rows that are used travel
-        plane = (size_t)ny * nx_file;
-        int rc;
-        if ((rc = band.alloc((size_t)nframes * plane))) return rc;
-        if (ny == ny_file)
-            RIP_HIP(ctx, hipMemcpyAsync(band.p, dcube, (size_t)nframes * plane * 2, hipMemcpyHostToDevice, ctx->stream));
-        else
-            RIP_HIP(ctx, hipMemcpy2DAsync(band.p, plane * 2, dcube, plane_file * 2, plane * 2, (size_t)nframes, hipMemcpyHostToDevice,
-                                          ctx->stream));
-        dcube = band.p;
-    }
-    const bool w8 = nx_file % 8 == 0 && aligned(dcube, 16);
+    CubeBand band(ctx);
+    if (const int rc = band.in(cube, location, ny_file, nx_file, f0, nframes, y0, ny)) return rc;
+    const bool w8 = nx_file % 8 == 0 && aligned(band.p, 16);
     const int vec_sums = nx % 4 == 0 && aligned(sums, 16);
     const size_t threads = (size_t)nframes * ny * (w8 ? (nx + 7) / 8 : nx);
     if ((threads + 255) / 256 > 0x7FFFFFFFu) return rip_fail(ctx, RIP_EINVAL, "cal_frame_sums: a (%d,%d,%d) set is too large", nframes, ny, nx);
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (w8)
-        hipLaunchKernelGGL(frame_sums_kernel<true>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, nframes, ny, nx, fits_be16,
-                           vec_sums, sums);
-    else
-        hipLaunchKernelGGL(frame_sums_kernel<false>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, nframes, ny, nx, fits_be16,
-                           vec_sums, sums);
+    RIP_LAUNCH_W8(frame_sums_kernel, w8, grid, dim3(256), 0, ctx->stream, band.p, band.plane, nx_file, nframes, ny, nx, fits_be16, vec_sums,
+                  sums);
     RIP_HIP(ctx, hipGetLastError());
     return dev_sync(ctx);
 }

@@ -10,6 +10,7 @@
 // Bounds (x <= 65535, n <= 64 frames, N <= 512 exposures): |S| = |sum (2i - (n-1)) x_i| <= 65535 n^2 / 2, so 512 S^2 <= 2^63.1 fits
 // in u64; sum d^2 <= 63 * 65535^2 per exposure, 512 of them 2^47; the reference-output sum 512 * 64 * 65535 < 2^31.
 #include "rip_host.h"
+#include "rip_samples.h"
 
 namespace {
 
@@ -31,30 +32,6 @@ struct NsAcc {
     uint64_t *c1;
     uint32_t *m33;
 };
-
-__device__ __forceinline__ uint32_t ns_sample(uint32_t raw, bool be16) {
-    // FITS storage: big-endian int16 with BZERO = 32768; the unsigned sample is the swapped word with its top bit flipped
-    if (be16) raw = (((raw & 0xFFu) << 8) | (raw >> 8)) ^ 0x8000u;
-    return raw;
-}
-
-// p[0 .. V-1] += add[0 .. V-1]; for V = 8 in 16-byte pieces (p is 16-byte aligned: the host checks)
-template <typename T, int V>
-__device__ __forceinline__ void ns_rmw(T *__restrict__ p, const T (&add)[V]) {
-    if constexpr (V == 1) {
-        p[0] += add[0];
-    } else {
-        constexpr int PER = 16 / sizeof(T);
-        typedef T vec __attribute__((ext_vector_type(PER)));
-#pragma unroll
-        for (int j = 0; j < V / PER; ++j) {
-            vec v = reinterpret_cast<vec *>(p)[j];
-#pragma unroll
-            for (int e = 0; e < PER; ++e) v[e] += add[j * PER + e];
-            reinterpret_cast<vec *>(p)[j] = v;
-        }
-    }
-}
 
 // A segment is one channel of one row: cw pixels, L = cw / V lanes (V = 8 pixels per lane with W8, one 16-byte load per frame; else
 // 1).  Segments are numbered seg = y * nch + c; a workgroup takes CB = 256 / L consecutive ones, so the lanes of a channel never
@@ -79,7 +56,7 @@ __global__ __launch_bounds__(256) void noise_add_kernel(const uint16_t *__restri
     const size_t y = live ? seg / nch : 0;
     const int c = live ? (int)(seg - y * nch) : 0;
     const uint16_t *src = cube + y * nx_file + (size_t)c * cw + (size_t)lane * V;
-    const bool be = be16 != 0;
+    const int stored = be16 != 0;
     const bool odd = (lane & 1) != 0;   // one-pixel form: cw is even, so the column's parity is the lane's
 
     uint32_t xf[V], xp[V], m[V];
@@ -92,17 +69,7 @@ __global__ __launch_bounds__(256) void noise_add_kernel(const uint16_t *__restri
     for (int i = 0; i < n; ++i) {
         uint32_t x[V];
         if (live) {
-            if constexpr (W8) {
-                const uint4 w4 = *reinterpret_cast<const uint4 *>(src + (size_t)i * plane);
-                const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    x[2 * k] = ns_sample(w[k] & 0xFFFFu, be);
-                    x[2 * k + 1] = ns_sample(w[k] >> 16, be);
-                }
-            } else {
-                x[0] = ns_sample(src[(size_t)i * plane], be);
-            }
+            load_samples<V>(src + (size_t)i * plane, stored, x);
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) x[k] = 0u;
@@ -161,15 +128,15 @@ __global__ __launch_bounds__(256) void noise_add_kernel(const uint16_t *__restri
         s1[k] = (uint64_t)(S[k] * S[k]);
         c0[k] = (int32_t)xp[k] - (int32_t)xf[k];
     }
-    ns_rmw<uint32_t, V>(acc.a0 + px, xf);
-    ns_rmw<uint64_t, V>(acc.a1 + px, a1);
-    ns_rmw<int32_t, V>(acc.b0 + px, d0);
-    ns_rmw<uint64_t, V>(acc.b1 + px, b1);
-    ns_rmw<int64_t, V>(acc.s0 + px, S);
-    ns_rmw<uint64_t, V>(acc.s1 + px, s1);
-    ns_rmw<int32_t, V>(acc.c0 + px, c0);
-    ns_rmw<uint64_t, V>(acc.c1 + px, q);
-    if (ref_out && c == C) ns_rmw<uint32_t, V>(acc.m33 + y * cw + (size_t)lane * V, m);
+    add_results(acc.a0 + px, xf);
+    add_results(acc.a1 + px, a1);
+    add_results(acc.b0 + px, d0);
+    add_results(acc.b1 + px, b1);
+    add_results(acc.s0 + px, S);
+    add_results(acc.s1 + px, s1);
+    add_results(acc.c0 + px, c0);
+    add_results(acc.c1 + px, q);
+    if (ref_out && c == C) add_results(acc.m33 + y * cw + (size_t)lane * V, m);
 }
 
 // ------------------------------------------------------------------------------------------ moment tables of the row sums
@@ -303,25 +270,15 @@ int rip_cal_noise_add(rip_ctx *ctx, const uint16_t *cube, int location, int nrea
     const int64_t nseg = (int64_t)ny * nch;
     if (nseg > 0x7FFFFFFF) return rip_fail(ctx, RIP_EINVAL, "cal_noise_add: a (%d,%ld) frame is too large", ny, (long)nxt);
     RIP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t plane = (size_t)ny * nx_file;
-    const uint16_t *dcube = cube + (size_t)f0 * plane;
-    DevBuf<uint16_t> band(ctx);
-    if (location == RIP_HOST) {   // only the frames that are used travel
-        if (const int rc = band.alloc((size_t)n * plane)) return rc;
-        RIP_HIP(ctx, hipMemcpyAsync(band.p, dcube, (size_t)n * plane * 2, hipMemcpyHostToDevice, ctx->stream));
-        dcube = band.p;
-    }
-    const bool w8 = nx_file % 8 == 0 && cw % 8 == 0 && aligned(dcube, 16) && aligned(a0, 16) && aligned(a1, 16) && aligned(b0, 16) &&
+    CubeBand band(ctx);   // (the whole rows of the frames that are used)
+    if (const int rc = band.in(cube, location, ny, nx_file, f0, n, 0, ny)) return rc;
+    const bool w8 = nx_file % 8 == 0 && cw % 8 == 0 && aligned(band.p, 16) && aligned(a0, 16) && aligned(a1, 16) && aligned(b0, 16) &&
                     aligned(b1, 16) && aligned(s0, 16) && aligned(s1, 16) && aligned(c0, 16) && aligned(c1, 16) && aligned(m33, 16);
     const int L = w8 ? cw / 8 : cw, CB = 256 / L;
     const NsAcc acc{a0, a1, b0, b1, s0, s1, c0, c1, m33};
     const dim3 grid((unsigned)((nseg + CB - 1) / CB));
-    if (w8)
-        hipLaunchKernelGGL(noise_add_kernel<true>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, n, (int)nch, C, cw, ref_out,
-                           (unsigned)nseg, CB, fits_be16, acc, rowsum);
-    else
-        hipLaunchKernelGGL(noise_add_kernel<false>, grid, dim3(256), 0, ctx->stream, dcube, plane, nx_file, n, (int)nch, C, cw, ref_out,
-                           (unsigned)nseg, CB, fits_be16, acc, rowsum);
+    RIP_LAUNCH_W8(noise_add_kernel, w8, grid, dim3(256), 0, ctx->stream, band.p, band.plane, nx_file, n, (int)nch, C, cw, ref_out,
+                  (unsigned)nseg, CB, fits_be16, acc, rowsum);
     RIP_HIP(ctx, hipGetLastError());
     return dev_sync(ctx);
 }

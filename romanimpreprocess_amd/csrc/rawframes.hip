@@ -8,16 +8,10 @@
 // Both kernels move bytes or do exact arithmetic (every product and partial sum is a multiple of 0.5 far below 2^53), so each
 // has two forms that agree bit for bit: W8, one 16-byte load of 8 samples per lane, and one sample (pixel) per lane.
 #include "rip_host.h"
+#include "rip_samples.h"
 
 namespace {
 
-// one dword holding two samples as stored -> two native u16.  stored 1, 2: FITS storage, the bytes of each sample swapped; stored 1
-// also has BZERO = 32768, the top bit of each sample inverted (stored 2: an int16 whose bits numpy's cast to uint16 keeps).
-__device__ __forceinline__ uint32_t rf_decode2(uint32_t w, int stored) {
-    if (stored != 0) w = ((w & 0x00FF00FFu) << 8) | ((w >> 8) & 0x00FF00FFu);
-    if (stored == 1) w ^= 0x80008000u;
-    return w;
-}
 __device__ __forceinline__ uint32_t rf_swap_halves(uint32_t w) { return (w << 16) | (w >> 16); }
 
 // orient 1: columns 0 .. nflip-1 of every row reversed, the others (the reference output) in place; orient 2: the rows reversed;
@@ -37,14 +31,14 @@ __global__ __launch_bounds__(256) void frame_kernel(const uint16_t *__restrict__
     const uint16_t *s = src + (size_t)y * nx + x;
     if constexpr (W8) {
         const uint4 q = *reinterpret_cast<const uint4 *>(s);
-        uint32_t w[4] = {rf_decode2(q.x, stored), rf_decode2(q.y, stored), rf_decode2(q.z, stored), rf_decode2(q.w, stored)};
+        uint32_t w[4] = {decode_pair(q.x, stored), decode_pair(q.y, stored), decode_pair(q.z, stored), decode_pair(q.w, stored)};
         uint4 o = make_uint4(w[0], w[1], w[2], w[3]);
         if (rev) o = make_uint4(rf_swap_halves(w[3]), rf_swap_halves(w[2]), rf_swap_halves(w[1]), rf_swap_halves(w[0]));
         const int xd = rev ? nflip - 8 - x : x;
         *reinterpret_cast<uint4 *>(dst + (size_t)yd * nx + xd) = o;
     } else {
         const int xd = rev ? nflip - 1 - x : x;
-        dst[(size_t)yd * nx + xd] = (uint16_t)rf_decode2(*s, stored);
+        dst[(size_t)yd * nx + xd] = (uint16_t)decode_sample(*s, stored);
     }
 }
 
@@ -69,17 +63,7 @@ __global__ __launch_bounds__(256) void slopes_kernel(const uint16_t *__restrict_
         const bool second = k < nh;   // (wave-uniform)
         const double w0 = w[k], w1 = second ? w[nc + k] : 0.0;
         uint32_t v[V];
-        if constexpr (W8) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(cube + (size_t)k * npix + p);
-            const uint32_t d[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[2 * j] = d[j] & 0xFFFFu;
-                v[2 * j + 1] = d[j] >> 16;
-            }
-        } else {
-            v[0] = cube[(size_t)k * npix + p];
-        }
+        load_samples<V>(cube + (size_t)k * npix + p, 0, v);   // the cube is native
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             const double s = (double)v[j];
@@ -93,15 +77,8 @@ __global__ __launch_bounds__(256) void slopes_kernel(const uint16_t *__restrict_
         o0[j] = (float)(a0[j] / de0);
         o1[j] = (float)(a1[j] / de1);
     }
-    if constexpr (W8) {
-        *reinterpret_cast<float4 *>(slp + p) = make_float4(o0[0], o0[1], o0[2], o0[3]);
-        *reinterpret_cast<float4 *>(slp + p + 4) = make_float4(o0[4], o0[5], o0[6], o0[7]);
-        *reinterpret_cast<float4 *>(slp + npix + p) = make_float4(o1[0], o1[1], o1[2], o1[3]);
-        *reinterpret_cast<float4 *>(slp + npix + p + 4) = make_float4(o1[4], o1[5], o1[6], o1[7]);
-    } else {
-        slp[p] = o0[0];
-        slp[npix + p] = o1[0];
-    }
+    store_results(slp + p, o0);
+    store_results(slp + npix + p, o1);
 }
 
 }   // namespace
@@ -127,10 +104,7 @@ int rip_cal_raw_frame(rip_ctx *ctx, const uint16_t *frame, int location, int ny,
     if (const int rc = src.in(ctx, frame, n, location)) return rc;
     const bool w8 = nx % 8 == 0 && nflip % 8 == 0 && aligned(src.p, 16) && aligned(dst, 16);
     const dim3 grid((unsigned)(((w8 ? n / 8 : n) + 255) / 256));
-    if (w8)
-        hipLaunchKernelGGL(frame_kernel<true>, grid, dim3(256), 0, ctx->stream, src.p, ny, nx, orient, nflip, stored, dst);
-    else
-        hipLaunchKernelGGL(frame_kernel<false>, grid, dim3(256), 0, ctx->stream, src.p, ny, nx, orient, nflip, stored, dst);
+    RIP_LAUNCH_W8(frame_kernel, w8, grid, dim3(256), 0, ctx->stream, src.p, ny, nx, orient, nflip, stored, dst);
     RIP_HIP(ctx, hipGetLastError());
     return dev_sync(ctx);
 }
@@ -154,10 +128,7 @@ int rip_cal_frame_slopes(rip_ctx *ctx, const uint16_t *cube, int n, int nc, size
     if ((rc = d.out(ctx, slp, 2 * npix, out_location))) return rc;
     const bool w8 = npix % 8 == 0 && aligned(cube, 16) && aligned(d.p, 16);
     const dim3 grid((unsigned)(((w8 ? npix / 8 : npix) + 255) / 256));
-    if (w8)
-        hipLaunchKernelGGL(slopes_kernel<true>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d.p);
-    else
-        hipLaunchKernelGGL(slopes_kernel<false>, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d.p);
+    RIP_LAUNCH_W8(slopes_kernel, w8, grid, dim3(256), 0, ctx->stream, cube, npix, nc, w.p, de0, de1, d.p);
     RIP_HIP(ctx, hipGetLastError());
     if ((rc = d.download())) return rc;
     return dev_sync(ctx);

@@ -11,10 +11,10 @@
 // rip_cal_frame_sums, rip_stage_l2_planes, rip_stage_l2_refpix_strips, rip_fpa_bin, rip_fpa_render, rip_stage_fits_encode,
 // rip_stage_decode_reference_read, rip_stage_pixel_area, rip_cal_noise_add, rip_cal_noise_planes, rip_view_ranks,
 // rip_view_plane_diff, rip_view_render, rip_cal_corr_pair.  The exceptions:
-//   partial copies                   rip_cal_group_means copies only its row band of a host cube, rip_cal_frame_sums only the frames
-//                                    and rows it uses (hipMemcpy2DAsync into a DevBuf), rip_cal_noise_add only the frames it
-//                                    uses, rip_view_plane_diff only its two planes, rip_cal_corr_pair only the rows of its four
-//                                    frames of either cube; rip_stage_fits_encode and
+//   partial copies                   the raw-sample cubes of rip_cal_group_means, rip_cal_frame_sums, rip_cal_noise_add and
+//                                    rip_cal_corr_pair are CubeBands below: of a host cube only the frames and rows that are
+//                                    read travel (corr_pair: one band per frame, into one buffer per cube).
+//                                    rip_view_plane_diff copies only its two planes; rip_stage_fits_encode and
 //                                    rip_stage_decode_reference_read turn a host source into the result in place, in the
 //                                    output's buffer
 //   always device pointers           the cube plane of rip_cal_raw_frame, the cube of rip_cal_frame_slopes, the sums of
@@ -114,6 +114,43 @@ private:
     T *host = nullptr;   // where a host output goes back to
     size_t count = 0;
 };
+
+// The part of a (., ny_file, nx_file) cube of 16-bit samples at a checked `location` that an entry reads: the rows y0 .. y0 + ny - 1
+// of the frames f0 .. f0 + nframes - 1.  p: the device pointer of the first sample used; plane: the frame stride in samples.  A
+// RIP_DEVICE cube is read where it is; of a RIP_HOST cube only those frames and rows travel, into a scoped buffer (one copy where
+// the rows are whole, a 2-D copy otherwise) -- or into `into`, room for nframes * ny * nx_file samples that the caller holds
+// (rip_cal_corr_pair: one allocation for the four separate frames of a cube).  Nothing here waits.
+struct CubeBand {
+    const uint16_t *p = nullptr;
+    size_t plane = 0;
+    DevBuf<uint16_t> buf;
+    explicit CubeBand(rip_ctx *c, const char *who = __builtin_FUNCTION()) : buf(c, who) {}
+    int in(const uint16_t *cube, int location, int ny_file, int nx_file, int f0, int nframes, int y0, int ny, uint16_t *into = nullptr) {
+        rip_ctx *ctx = buf.ctx;
+        const size_t plane_file = (size_t)ny_file * nx_file;
+        p = cube + (size_t)f0 * plane_file + (size_t)y0 * nx_file;
+        plane = plane_file;
+        if (location == RIP_DEVICE) return RIP_OK;
+        plane = (size_t)ny * nx_file;
+        if (!into) {
+            if (const int rc = buf.alloc((size_t)nframes * plane)) return rc;
+            into = buf.p;
+        }
+        if (ny == ny_file)
+            RIP_HIP(ctx, hipMemcpyAsync(into, p, (size_t)nframes * plane * 2, hipMemcpyHostToDevice, ctx->stream));
+        else
+            RIP_HIP(ctx, hipMemcpy2DAsync(into, plane * 2, p, plane_file * 2, plane * 2, (size_t)nframes, hipMemcpyHostToDevice,
+                                          ctx->stream));
+        p = into;
+        return RIP_OK;
+    }
+};
+
+// The launch of a kernel template <bool W8> (rip_samples.h: 8 samples or one per lane), stated once: kernel<true> where w8 holds,
+// else kernel<false>.  The entry decides w8 and sizes the grid for it.
+#define RIP_W8_KERNEL(kernel, w8) ((w8) ? kernel<true> : kernel<false>)
+#define RIP_LAUNCH_W8(kernel, w8, grid, block, lds, stream, ...) \
+    hipLaunchKernelGGL(RIP_W8_KERNEL(kernel, w8), grid, block, lds, stream, __VA_ARGS__)
 
 // waits for what an entry point has queued (its downloads among it)
 inline int dev_sync(rip_ctx *ctx, hipStream_t stream = nullptr) {
