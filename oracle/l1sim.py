@@ -67,10 +67,12 @@ def add_read_noise_to_resultants(resultants, tij, read_noise, normals):
     return resultants
 
 
-def make_l1_fullcal(counts, read_pattern, cal, read_time, normals_reset, reads_e, normals_read, nb=4):
+def make_l1_fullcal(counts, read_pattern, cal, read_time, normals_reset, reads_e, normals_read, nb=4, unrounded=False):
     """``make_l1_fullcal``: (rounded resultants f4 (ngrp, na, na), reset-noise image in electrons).  ``counts`` only gives
-    shape and dtype here: its apportioned form ``reads_e`` comes from ``binomial_shares``."""
-    inner = (slice(nb, -nb), slice(nb, -nb))
+    shape and dtype here: its apportioned form ``reads_e`` comes from ``binomial_shares``.  ``unrounded``: a third value, the
+    f4 resultants as they stand just before ``np.round``.  ``nb`` may be 0."""
+    ny, nx = cal["gain"]["data"].shape
+    inner = (slice(nb, ny - nb), slice(nb, nx - nb))
     start = np.array(normals_reset, dtype=counts.dtype)
     start *= cal["read"]["resetnoise"][inner]
     start *= cal["gain"]["data"][inner]
@@ -88,23 +90,26 @@ def make_l1_fullcal(counts, read_pattern, cal, read_time, normals_reset, reads_e
     res = add_read_noise_to_resultants(res, tij, cal["read"]["data"][inner], normals_read)
     if "biascorr" in cal:
         res += cal["biascorr"]["data"]
+    pre = res.copy() if unrounded else None
     res[:, :, :] = np.round(res)
-    return res, start
+    return (res, start, pre) if unrounded else (res, start)
 
 
 def embed(resultants, ny, nx, nb=4):
     """The u16 cube ``romanisim.l1.make_asdf`` builds around the resultants (zero border; values clipped to the u16 range
     here, where romanisim casts)."""
     cube = np.zeros((resultants.shape[0], ny, nx), dtype=np.uint16)
-    cube[:, nb:-nb, nb:-nb] = np.clip(resultants, 0, 65535).astype(np.uint16)
+    cube[:, nb:ny - nb, nb:nx - nb] = np.clip(resultants, 0, 65535).astype(np.uint16)
     return cube
 
 
 def fill_in_refdata_and_1f(im, cal, tij, normals, frames=None, white33=None, amp33=None, nb=4, channelwidth=128):
     """``fill_in_refdata_and_1f`` in place on ``im`` (ngrp, ny, nx) u16 and ``amp33`` (ngrp, ny, channelwidth) u16.
-    ``normals`` (ngrp+1, ny, nx) f4; ``frames`` (ngrp, 34, ny, channelwidth) f4 1/f frames in the order the reference draws
-    them per group (common, channels 0..31, reference output) or None (no banding); ``white33`` (ngrp, ny, channelwidth) f4."""
+    ``normals`` (ngrp+1, ny, nx) f4; ``frames`` (ngrp, nch + 2, ny, channelwidth) f4 1/f frames in the order the reference
+    draws them per group (common, channels 0..nch-1, reference output) or None (no banding); ``white33`` (ngrp, ny,
+    channelwidth) f4.  nch = nx // channelwidth channels: the reference's 32 on its own frame."""
     ngrp, ny, nx = im.shape
+    nch = nx // channelwidth
     work = np.array(normals, dtype=np.float32)
     rd = cal["read"]
     work[:-1] *= rd["data"][None]
@@ -120,14 +125,14 @@ def fill_in_refdata_and_1f(im, cal, tij, normals, frames=None, white33=None, amp
         u_pink, c_pink = float(rd["anc"]["U_PINK"]), float(rd["anc"]["C_PINK"])
         for j in range(len(tij)):
             common = frames[j, 0] * c_pink
-            for ch in range(32):
+            for ch in range(nch):
                 stripe = frames[j, 1 + ch] * u_pink + common
                 if ch % 2 == 1:
                     stripe = stripe[:, ::-1]
                 work[j, :, channelwidth * ch:channelwidth * (ch + 1)] += (stripe / len(tij[j]) ** 0.5).astype(np.float32)
             if info is not None and info["valid"]:
                 white = np.array(white33[j], dtype=np.float32) * info["std"]
-                pink = info["RU_PINK"] * frames[j, 33] + info["M_PINK"] * common
+                pink = info["RU_PINK"] * frames[j, nch + 1] + info["M_PINK"] * common
                 level = info["med"] + (white + pink) / len(tij[j]) ** 0.5
                 amp33[j] = level.astype(np.int64).astype(amp33.dtype)    # a C cast: towards zero, modulo 2**16
     im[:, :, :] = np.clip(np.round(work[:-1]), 0, 2**16 - 1).astype(im.dtype)

@@ -90,7 +90,7 @@ def il_apply(counts, K, gain, coefs, Smin, Smax, Sref, start_e=0.0, electrons=Fa
     g = gain
     if g.shape[0] > nyc:
         b = (g.shape[0] - nyc) // 2
-        g = g[b:-b, b:-b]
+        g = g[b:g.shape[0] - b, b:g.shape[1] - b]
     nb = (8192 - nyc // 2) % 16
     sl = (slice(nb, nb + nyc), slice(nb, nb + nxc))
     S, _ = invlinearity(conv / (g if electrons else 1.0), coefs[(slice(None),) + sl], Smin[sl], Smax[sl])
